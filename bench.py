@@ -1,6 +1,10 @@
 """Benchmark: denoising-steps/sec (train + sample), ddpm-mel-32seq-512, synthetic (B,32,512) latents.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps (one block), optionally writes the outputs of its last step and prints the
+JSON line.  ``--full`` also measures what the headline does not need (the median of 5 blocks unless --repeats says otherwise,
+the roofline microbench, the real 1000-step sampler walks, the extra configurations and the CPU baseline; see below).
 
 ``--gpus N`` with N > 1 and no RANK / WORLD_SIZE in the environment re-launches itself as N ranks under
 ``torch.distributed.run`` (one process per GPU over RCCL, rendezvous on 127.0.0.1); launched by an external
@@ -15,10 +19,20 @@ and output stage of step k; U steps per captured hipGraph, a cross-chain event p
 up to the package default 8: 5 for --steps 20) -- DESIGN.md section 5.  Two denoising evaluations per step, so
 ``value`` = N * 2K / max-over-ranks(time of K steps): whole-job denoising-steps/sec (weak scaling: the
 per-GPU batch is fixed).  Inputs are resident in HBM before the timed region.  The timed region is repeated
-``--repeats`` times (blocks of exactly K train steps + K reverse steps, each bracketed by barrier + synchronize);
-the MEDIAN block is the headline, every block's value and the relative spread are in the line.
+``--repeats`` times (default 1, with --full 5; blocks of exactly K train steps + K reverse steps, each bracketed by barrier +
+synchronize); the MEDIAN block is the headline, every block's value and the relative spread are in the line.  ``ms_per_step`` is
+the milliseconds of one step (train + reverse) of that block.
 
-The JSON line also carries
+``--dump-outputs DIR`` (rank 0) writes what the timed path computed in its last step, after the timed blocks, as float32 .npy:
+  train_loss_per_sample.npy  (B,)        the last train step's per-sequence loss
+  train_metrics.npy          (3,)        its loss, gradient norm and learning rate (float64)
+  params_sample.npy          (4194304,)  the parameters after the last Adam update at fixed indices (numpy default_rng(0),
+                                         sorted, without replacement, over the flat parameter vector)
+  sample_x.npy               (B,32,512)  the reverse-diffusion state after the last reverse step
+(train_* / params_* only when --mode trains, sample_x only when it samples).  The inputs (weights, latents, noise seeds) depend
+on the arguments alone, so two builds run with the same arguments can be compared output for output.
+
+With --full the JSON line also carries
   roofline       the dominant kernel (DenseResBlock GEMM 8192x2048x2048, bf16 MFMA): algorithmic
                  2*M*N*K flops / average launch duration measured with HIP events on the launch
                  stream in this process, against the 2.5 PFLOP/s dense bf16 peak.
@@ -46,6 +60,7 @@ for p in (ROOT, os.path.join(ROOT, "oracle")):
 FLOP_FWD_PER_SEQ = {"base": 1_401_159_680, "large": 2_019_426_304}     # BASELINE.md section 2 (C=512)
 PEAK_BF16_TFLOPS = 2500.0                                              # MI355X_MICROARCH.md dense bf16
 NET_KW = {"base": dict(), "large": dict(num_layers=8, num_heads=16, num_mlp_layers=3)}
+DUMP_PARAMS = 1 << 22                                                  # --dump-outputs: parameters sampled (16 MiB)
 
 
 def parse(argv=None):
@@ -53,7 +68,13 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps; the median block is reported (default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: 5 blocks, roofline microbench, 1000-step sampler walks, "
+                         "extra configurations, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--batch", type=int, default=256, help="sequences per GPU")
     ap.add_argument("--config", choices=["base", "large"], default="base")
     ap.add_argument("--mode", choices=["both", "train", "sample"], default="both")
@@ -90,7 +111,10 @@ def parse(argv=None):
     ap.add_argument("--chain-opt", action="append", default=[], help="engine option key=value for the sampler's chain handles (A/B runs)")
     ap.add_argument("--no-roofline-microbench", action="store_true",
                     help="skip the back-to-back launches of the dominant kernel (profiling runs: the trace then holds the timed loops only)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
+    return a
 
 
 def log(msg: str) -> None:
@@ -172,7 +196,7 @@ def cpu_baseline(cfg_name: str, batch: int):
     64 threads, a bounded sample: the batch shrinks on slower hosts)."""
     import torch
     import ddpm_oracle as O
-    cores = min(os.cpu_count() or 1, 64)
+    cores = min(int(os.environ.get("OMP_NUM_THREADS") or 0) or os.cpu_count() or 1, 64)      # a set OMP_NUM_THREADS is the CPU budget
     torch.set_num_threads(cores)
     ocfg = O.NetConfig(data_channels=512, **NET_KW[cfg_name])
     p = O.init_params(ocfg, 0, torch.float32)
@@ -314,8 +338,9 @@ class Workload:
 
     # ---- the two halves of a step
     def one_train(self):
-        self._train_step(self.N.diffusion_loss, self.x0, self.opt, self.betas, self.key, 1e-3, grad_clip=1.0, comm=self.comm,
-                         lr_gamma=0.98, lr_interval=10000, sample_offset=self.rank * self.B, global_batch=self.B * self.world)
+        _, self.last_metrics = self._train_step(self.N.diffusion_loss, self.x0, self.opt, self.betas, self.key, 1e-3, grad_clip=1.0,
+                                                comm=self.comm, lr_gamma=0.98, lr_interval=10000, sample_offset=self.rank * self.B,
+                                                global_batch=self.B * self.world)
 
     def _reset_t(self):
         """Restart the walk: t = 999 AND a fresh N(0,1) state, as a new diffusion_dynamics call would (the step time depends
@@ -420,6 +445,27 @@ class Workload:
 
     def final_loss(self) -> float:
         return float(self.opt.engine.loss_per_sample().mean())
+
+    def dump_outputs(self, out_dir: str, do_train: bool, do_sample: bool) -> dict:
+        """The outputs of the last timed step (module docstring) as out_dir/<name>.npy; returns {name: shape}."""
+        import numpy as np
+        torch = self.torch
+        torch.cuda.synchronize()
+        arrays = {}
+        if do_train:
+            eng = self.opt.engine
+            arrays["train_loss_per_sample"] = eng.loss_per_sample().float().cpu().numpy()
+            m = self.last_metrics.resolve()
+            arrays["train_metrics"] = np.array([m["loss"], m["grad"], m["lr"]], dtype=np.float64)
+            n = eng.params.numel()
+            idx = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_PARAMS), replace=False))
+            arrays["params_sample"] = eng.params[torch.from_numpy(idx).to(eng.params.device)].float().cpu().numpy()
+        if do_sample:
+            arrays["sample_x"] = self.x.float().cpu().numpy()
+        os.makedirs(out_dir, exist_ok=True)
+        for name, v in arrays.items():
+            np.save(os.path.join(out_dir, f"{name}.npy"), v)
+        return {name: list(v.shape) for name, v in arrays.items()}
 
     def sampler_walk(self, num_samples=None):
         """One real 1000-step ``ncsn.sample`` call on ``num_samples`` (default B) sequences (twice: the first call also pays the
@@ -627,6 +673,9 @@ def main():
         comm.exposed_comm_us()                                     # drop what model set-up recorded
     c0 = comm.collectives if comm is not None else 0
     blocks = run_blocks(w, a, dist, do_train, do_sample, a.steps, a.warmup, a.repeats)
+    if a.dump_outputs and rank == 0:
+        dumped = w.dump_outputs(a.dump_outputs, do_train, do_sample)
+        log(f"outputs of the last timed step -> {a.dump_outputs}: {dumped}")
     dp_stats = {}
     if comm is not None and do_train:
         n_train = (max(a.warmup, 1) + a.steps * max(a.repeats, 1))
@@ -644,17 +693,17 @@ def main():
 
     roof = None
     step_fracs = {"step_frac_train": head["step_frac_train"], "step_frac_sample": head["step_frac_sample"]}
-    if rank == 0 and not a.no_roofline_microbench:
+    if rank == 0 and a.full and not a.no_roofline_microbench:
         roof = roofline_microbench(a, w.cfg, dev, a.dtype)
         roof.update(step_fracs)
     elif rank == 0:
         roof = {"bound": "mfma", "kernel": "gemm_nt256_kernel", "achieved": None, "peak": PEAK_BF16_TFLOPS,
                 "unit": "TFLOP/s", "frac": None, "traffic": None, **step_fracs}
 
-    # ---- single-GPU extras (rank 0 of a one-rank job; outside the headline's timed region)
+    # ---- single-GPU extras (--full, rank 0 of a one-rank job; outside the headline's timed region)
     walk = None
     extra = None
-    if world == 1 and do_sample and not a.no_sampler_walk:
+    if a.full and world == 1 and do_sample and not a.no_sampler_walk:
         ws, arr = w.sampler_walk()
         walk = {"sample_T1000_wall_s": round(ws[-1], 4), "first_call_wall_s": round(ws[0], 4),
                 "steps_per_sec": round(1000.0 / ws[-1], 1), "arrangement": arr,
@@ -668,7 +717,7 @@ def main():
                                     "seq_steps_per_sec": round(1000.0 * 1000 / ws2[-1], 1), "arrangement": arr2}
         walk["seq_steps_per_sec"] = round(1000.0 * a.batch / ws[-1], 1)
         log(f"real 1000-step sampler walk of 1000 sequences: {ws2[-1]:.3f} s ({arr2.get('chain_sizes')})")
-    if world == 1 and not a.no_extra_configs and a.mode == "both":
+    if a.full and world == 1 and not a.no_extra_configs and a.mode == "both":
         extra = {}
         todo = [(c, d) for c in ("base", "large") for d in ("bf16", "fp8") if (c, d) != (a.config, a.dtype)]
         del w
@@ -695,7 +744,7 @@ def main():
         w = None
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         log(f"GPU: train {head['t_train'] / a.steps * 1e3:.3f} ms/step, sample {head['t_sample'] / a.steps * 1e3:.3f} ms/step; CPU baseline next")
         cpu = cpu_baseline(a.config, a.batch)
 

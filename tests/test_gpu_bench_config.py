@@ -370,6 +370,42 @@ def test_bench_script_with_two_ranks_on_one_gpu():
     assert d["config"]["devices"] == dp["devices"] and any(t in dp["devices"][0] for t in ("uuid:", "pci:", "ordinal:"))
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_repeatable_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: one timed block of exactly K steps, none of the --full legs, and
+    the outputs of the last timed step on disk.  Two runs with the same arguments write bitwise the same arrays (same inputs, the
+    training step and the pipelined walk are bitwise repeatable)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "SMD_BENCH_SHARE_DEVICE"):
+        env.pop(k, None)
+    outs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["repeats"] == 1 and len(d["block_values"]) == 1 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3          # value and ms_per_step describe one block
+        assert d["cpu_baseline"] is None and d["extra_configs"] is None and d["sampler_walk"] is None
+        assert d["roofline"]["achieved"] is None
+        outs.append({n: np.load(tmp_path / run / f"{n}.npy")
+                     for n in ("train_loss_per_sample", "train_metrics", "params_sample", "sample_x")})
+    a, b = outs
+    assert a["train_loss_per_sample"].shape == (256,) and a["sample_x"].shape == (256, 32, 512)
+    assert a["params_sample"].shape == (1 << 22,) and a["params_sample"].dtype == np.float32 and a["train_metrics"].dtype == np.float64
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert abs(a["train_metrics"][0] - a["train_loss_per_sample"].mean()) < 1e-5 * a["train_metrics"][0]
+    for n in a:
+        assert np.isfinite(a[n]).all(), n
+        assert np.array_equal(a[n], b[n]), n
+
+
 def test_bench_dp_dry_run_on_one_gpu():
     """`bench.py --dp-dry-run`: the multi-GPU train step on CUDA gradient tensors with a communication stream that runs kernels of a
     collective's shape beside the backward pass (two ranks on cuda:0 over gloo).  The reduced gradient and the parameters after 3

@@ -1,6 +1,7 @@
 """CPU tests of the host logic: flag surface, configs, data transforms, checkpoint naming and the
 data-parallel gradient exchange (gloo, world_size 2)."""
 import glob
+import json
 import os
 import pickle
 
@@ -11,7 +12,9 @@ import torch
 import ddpm_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+# the flags each of the reference's own flagfiles sets (tests/golden/make_reference_config_values.py)
+with open(os.path.join(ROOT, "tests", "golden", "reference_config_values.json")) as _fh:
+    REF_CONFIGS = json.load(_fh)
 
 
 def test_flag_surface_defaults_match_reference_table():
@@ -61,20 +64,19 @@ def test_shipped_configs_parse_and_match_reference():
         a = F.make_flags(True)
         a.parse([f"--flagfile=configs/{os.path.basename(f)}"])
         assert a.loss == "ddpm" and a.sampling == "ddpm" and a.num_sigmas == 1000 and a.schedule_type == "linear"
-        ref = os.path.join(REF, "configs", os.path.basename(f))
-        if os.path.exists(ref):
-            os.chdir(REF)
-            b = F.make_flags(True)
-            b.parse([f"--flagfile=configs/{os.path.basename(f)}"])
-            assert a.flag_values_dict() == b.flag_values_dict(), f
+        want = F.make_flags(True).flag_values_dict()          # the reference's flagfile of the same name, as parsed by F
+        want.update(REF_CONFIGS[f"configs/{os.path.basename(f)}"])
+        assert a.flag_values_dict() == want, f
     os.chdir(cwd)
-    if os.path.isdir(os.path.join(REF, "configs")):       # every reference flagfile parses (surface test)
-        os.chdir(REF)
-        for f in glob.glob("configs/**/*.cfg", recursive=True):
-            if os.path.basename(f).startswith("mdn"):     # train_mdn.py flagfiles: a different flag set
-                continue
-            F.make_flags(True).parse([f"--flagfile={f}"])
-        os.chdir(cwd)
+    # every value the reference's flagfiles set (train_mdn.py's mdn-* excluded: a different flag set) goes through the parser again
+    # (surface test: enum choices such as ToyNCSN / TransformerDDPM4, lists, negated booleans)
+    for f, vals in REF_CONFIGS.items():
+        fl = F.make_flags(True)
+        for k, v in vals.items():
+            setattr(fl, k, v)
+        b = F.make_flags(True)
+        b.parse(fl.flags_into_string().split("\n"))
+        assert b.flag_values_dict() == fl.flag_values_dict(), f
 
 
 def test_data_transforms_match_oracle(tmp_path):
@@ -322,13 +324,17 @@ def _dp_worker(rank, world, port, tmp):
     open(os.path.join(tmp, f"ok{rank}"), "w").write("ok")
 
 
-def test_data_parallel_gradient_exchange_gloo(tmp_path):
+def test_data_parallel_gradient_exchange_gloo(tmp_path, monkeypatch):
     import socket
     import torch.multiprocessing as mp
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
+    # the two ranks are CPU-only processes on any host (gloo, CPU tensors): on a GPU box both would otherwise see cuda:0 and
+    # report the same device identity
+    for k in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
+        monkeypatch.setenv(k, "-1")
     mp.spawn(_dp_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
     assert os.path.exists(tmp_path / "ok0") and os.path.exists(tmp_path / "ok1")
 
@@ -413,6 +419,20 @@ def test_bench_refuses_to_run_fewer_ranks_than_asked():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True,
                        env=dict(env, WORLD_SIZE="4", RANK="0"), timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=4" in (r.stderr + r.stdout) and r.stdout.strip() == ""
+
+
+def test_bench_plain_run_times_steps_once_and_full_keeps_the_extras():
+    """A plain `bench.py --steps K` times one block of exactly K steps; --full restores the five-block median and the extra legs;
+    an explicit --repeats wins either way."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_cli", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.repeats == 1 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--steps", "7", "--full", "--dump-outputs", "out"])
+    assert a.repeats == 5 and a.full and a.dump_outputs == "out"
+    assert bench.parse(["--full", "--repeats", "2"]).repeats == 2 and bench.parse(["--repeats", "3"]).repeats == 3
 
 
 def test_shipped_lds_layouts_are_conflict_free_under_the_real_lane_groups():

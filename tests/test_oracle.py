@@ -10,8 +10,6 @@ import torch
 
 import ddpm_oracle as O
 
-REF = "/root/reference"
-
 
 def test_param_counts_match_paper_and_survey():
     mk = lambda **kw: O.num_params(O.NetConfig(**kw))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collects the evidence files of one round on the GPU box (run through gpurun from the repo root):
 #   tools/collect_profiles.sh <tag>      -> gpurun_out/<tag>_*  (copy what should be judged into profiles/)
-# 1. bench.py JSON line (default run incl. cpu_baseline)     2. rocprofv3 kernel-trace summary of the same command
+# 1. bench.py JSON line (--full run incl. cpu_baseline)     2. rocprofv3 kernel-trace summary of the same command
 # 3. PMC passes on the dominant kernel (separate runs: SQ cycles, MFMA busy, FETCH_SIZE, WRITE_SIZE)  4. kbench table
 set -u
 TAG=${1:-r1}
@@ -9,8 +9,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-python $R/bench.py --steps 50 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o t -- python $R/bench.py --steps 10 --warmup 2 --repeats 1 --no-extra-configs --no-sampler-walk --no-cpu-baseline --no-graph > /dev/null 2> $OUT/${TAG}_kt.err
+python $R/bench.py --full --steps 50 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o t -- python $R/bench.py --full --steps 10 --warmup 2 --repeats 1 --no-extra-configs --no-sampler-walk --no-cpu-baseline --no-graph > /dev/null 2> $OUT/${TAG}_kt.err
 python $R/tools/prof_summary.py $OUT/${TAG}_kt/t_results.db 12 > $OUT/${TAG}_bench_kernel_trace.txt
 # per-mode traces with undistorted per-kernel times: train on ONE stream, sample step eager; the roofline microbench
 # (104 extra launches of the dominant kernel) is left out of these so that calls/step and the shares are the step's own

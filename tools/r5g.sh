@@ -3,7 +3,7 @@
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --mode sample --steps 20 --warmup 5 --repeats 7 --no-cpu-baseline --no-extra-configs --no-roofline-microbench"
+B="python $R/bench.py --full --mode sample --steps 20 --warmup 5 --repeats 7 --no-cpu-baseline --no-extra-configs --no-roofline-microbench"
 for rep in 1 2; do
   for cfg in "s0m128:" "s1m32:--chain-opt sample_split=1 --chain-opt nt256_min_tiles=32" "s1m128:--chain-opt sample_split=1" "s0m32:--chain-opt nt256_min_tiles=32" "free:--sampler-unroll 0"; do
     name=${cfg%%:*}; opts=${cfg#*:}

@@ -8,5 +8,5 @@ timeout 2400 python -m pytest tests -q -m gpu -x --durations=15 > $OUT/r5i_full_
 tail -22 $OUT/r5i_full_gpu_suite.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/r5i_smoke.txt 2>&1; tail -3 $OUT/r5i_smoke.txt
 cd /tmp; export TMPDIR=/tmp
-python $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r5i_bench.json 2> $OUT/r5i_bench.err
+python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r5i_bench.json 2> $OUT/r5i_bench.err
 tail -c 600 $OUT/r5i_bench.err

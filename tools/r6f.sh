@@ -12,7 +12,7 @@ cd /tmp; export TMPDIR=/tmp
 for rg in 8 4 8 4; do
 python $R/bench.py --mode sample --steps 40 --warmup 5 --repeats 3 --no-cpu-baseline --no-roofline-microbench --no-extra-configs --no-sampler-walk --tuning reverse_rg=$rg 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('reverse_rg=$rg sample', d['sample_steps_per_sec'], d['block_values'])"
 done | tee $OUT/r6f_reverse_rg_ab.txt
-python $R/bench.py --steps 20 --warmup 5 > $OUT/r6f_bench.json 2> $OUT/r6f_bench.err
+python $R/bench.py --full --steps 20 --warmup 5 > $OUT/r6f_bench.json 2> $OUT/r6f_bench.err
 python -c "
 import json; d=json.load(open('$OUT/r6f_bench.json'))
 print({k: d[k] for k in ('value','train_steps_per_sec','sample_steps_per_sec','sample_T1000_wall_s')}, d['roofline']['frac'])

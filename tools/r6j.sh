@@ -4,7 +4,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; OUT=$R/gpurun_out; mkdir -p $OUT
 cd $R
 python -c "import __graft_entry__ as g; g.build(); g.smoke(); print('smoke ok')" 2>&1 | tail -3
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r6j_bench.json 2> $OUT/r6j_bench.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r6j_bench.json 2> $OUT/r6j_bench.err
 python -c "
 import json; d=json.load(open('$OUT/r6j_bench.json'))
 print({k: d[k] for k in ('value','train_steps_per_sec','sample_steps_per_sec','sample_T1000_wall_s','ms_per_step')}, d['roofline']['frac'], d['cpu_baseline']['value'])"
