@@ -277,7 +277,9 @@ int smd_mlp_block_fwd_hs(const smd_bf16* a2, const float* h_res, int rows, const
  * forward pack; W2 [hidden][128], W1 [128][hidden]: dgrad packs of fc2 / fc1.  rows % 128 == 0, hidden % 512 == 0. */
 int smd_mlp_block_bwd_hs(const smd_bf16* a2, const smd_bf16* dh, int rows, const smd_bf16* W1t, const smd_bf16* W2,
                          const smd_bf16* W1, const float* b1, int hidden, smd_bf16* u, smd_bf16* dz, float* part, void* stream);
-/* LayerNorm (D = 128) backward with dout = (p0 + p1) + (p2 + p3) (fp32 partial tiles): dx = LN-backward + dres (nullable)
+/* The four *_parts / *_ex / *_bwd_ln entries below read the partial tiles p_k = parts + k*part_stride as float2: part_stride
+ * must be even and >= rows*128 (disjoint tiles), the fp32 row operands 8-byte aligned; anything else returns -1 unlaunched.
+ * LayerNorm (D = 128) backward with dout = (p0 + p1) + (p2 + p3) (fp32 partial tiles): dx = LN-backward + dres (nullable)
  * -> dx_f32 (nullable, may alias dres) / dx_bf16 (nullable); partial [rows/32][2][128] = per-group dgamma / dbeta sums */
 int smd_ln128_bwd_parts(const float* x, const float* parts, int64_t part_stride, int rows, const float* gamma,
                         const float* dres, float* dx_f32, smd_bf16* dx_bf16, float* partial, void* stream);

@@ -16,6 +16,13 @@ struct smd_engine {
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline const bf16_t* B(const smd_bf16* p) { return reinterpret_cast<const bf16_t*>(p); }
 static inline bf16_t* B(smd_bf16* p) { return reinterpret_cast<bf16_t*>(p); }
+// the LayerNorm-128 kernels move fp32 rows as float2: 8-byte aligned operands (nullptr passes; the launcher checks presence)
+static inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+// four partial tiles of `rows` x 128 floats, `part_stride` floats apart, read as float2: disjoint tiles, 8-byte aligned ones
+#define PART_STRIDE_CHECK(fn, parts, part_stride, rows)                                                                       \
+  SMD_ARG_CHECK((part_stride) >= (int64_t)(rows) * 128 && (part_stride) % 2 == 0 && al8(parts),                             \
+                fn ": part_stride=%lld must be even and >= rows*128 = %lld, parts 8-byte aligned", (long long)(part_stride), \
+                (long long)(rows) * 128)
 
 #define NEED(e)                                        \
   do {                                                 \
@@ -254,16 +261,23 @@ int smd_mlp_block_bwd_hs(const smd_bf16* a2, const smd_bf16* dh, int rows, const
 }
 int smd_ln128_bwd_parts(const float* x, const float* parts, int64_t part_stride, int rows, const float* gamma, const float* dres,
                         float* dx_f32, smd_bf16* dx_bf16, float* partial, void* stream) {
+  PART_STRIDE_CHECK("smd_ln128_bwd_parts", parts, part_stride, rows);
+  SMD_ARG_CHECK(al8(x) && al8(gamma) && al8(dres) && al8(dx_f32), "smd_ln128_bwd_parts: x, gamma, dres, dx_f32 must be 8-byte aligned");
   return launch_ln128_bwd_parts(x, parts, (size_t)part_stride, rows, gamma, dres, dx_f32, B(dx_bf16), partial, S(stream));
 }
 int smd_ln128_parts(const float* parts, int64_t part_stride, int rows, const float* gamma, const float* beta, float* x_out,
                     smd_bf16* ln_out, void* stream) {
+  PART_STRIDE_CHECK("smd_ln128_parts", parts, part_stride, rows);
+  SMD_ARG_CHECK(al8(gamma) && al8(beta) && al8(x_out), "smd_ln128_parts: gamma, beta, x_out must be 8-byte aligned");
   return launch_ln128_parts(parts, (size_t)part_stride, rows, gamma, beta, x_out, B(ln_out), S(stream));
 }
 int smd_attn_block_fwd_ex(const float* h_in, const float* h_parts, int64_t part_stride, float* h_comb, float* h_out, int rows,
                           const float* gamma, const float* beta, const smd_bf16* Wqkv_t, const float* b_qkv,
                           const smd_bf16* Wo_t, const float* b_o, int num_heads, const float* gamma2, const float* beta2,
                           smd_bf16* a2_out, smd_bf16* save_a1, smd_bf16* save_qkv, smd_bf16* save_o, void* stream) {
+  if (h_parts) PART_STRIDE_CHECK("smd_attn_block_fwd_ex", h_parts, part_stride, rows);
+  SMD_ARG_CHECK(al8(h_in) && al8(h_comb) && al8(gamma) && al8(beta) && al8(gamma2) && al8(beta2),
+                "smd_attn_block_fwd_ex: h_in, h_comb, gamma, beta, gamma2, beta2 must be 8-byte aligned");
   AttnBlockExtra ex;
   ex.h_parts = h_parts; ex.part_stride = (size_t)part_stride; ex.h_comb = h_comb; ex.gamma2 = gamma2; ex.beta2 = beta2;
   ex.a2_out = B(a2_out);
@@ -284,6 +298,9 @@ int smd_attn_block_bwd_ln(const smd_bf16* qkv, const smd_bf16* Wo, const smd_bf1
                           const float* h_mid, const float* da2_parts, int64_t part_stride, const float* gamma2, float* dh,
                           smd_bf16* dh_mid_out, float* partial2, const float* h, const float* gamma1, smd_bf16* dh_out,
                           float* partial1, int rows, int num_heads, void* stream) {
+  PART_STRIDE_CHECK("smd_attn_block_bwd_ln", da2_parts, part_stride, rows);
+  SMD_ARG_CHECK(al8(h_mid) && al8(gamma2) && al8(dh) && al8(h) && al8(gamma1),
+                "smd_attn_block_bwd_ln: h_mid, gamma2, dh, h, gamma1 must be 8-byte aligned");
   AttnBwdLnArgs a;
   a.qkv = B(qkv); a.Wo = B(Wo); a.Wqkv = B(Wqkv); a.dqkv = B(dqkv); a.da1 = B(da1);
   a.h_mid = h_mid; a.da2_parts = da2_parts; a.part_stride = (size_t)part_stride; a.gamma2 = gamma2; a.dh = dh;

@@ -79,10 +79,11 @@ def _(x, noise_level, params, engine):
 
 @torch.library.custom_op("smd_amd::eps_backward", mutates_args=())
 def eps_backward(dpred: torch.Tensor, engine: int, generation: int) -> torch.Tensor:
-    """The engine's backward pass from d objective / d eps_hat; returns the flat parameter gradient: a fresh tensor object that
-    ALIASES the engine's gradient buffer (no 100 MB copy per step).  The buffer is overwritten by the handle's next backward
-    pass -- one outstanding forward / backward pair per handle, as eps_forward_train already requires; autograd either adopts
-    the alias as ``params.grad`` (trainer._train_step_generic then skips its copy-back) or clones it while accumulating."""
+    """The engine's backward pass from d objective / d eps_hat; returns the flat parameter gradient as a FRESH tensor (a copy of
+    the engine's gradient buffer, which the handle's next backward pass overwrites): autograd may adopt it as ``params.grad``
+    and accumulate later passes into it, and a ``.grad`` reference kept across steps stays what it was.
+    trainer._train_step_generic alone skips the 100 MB copy: it sets ``engine._grad_alias_ok`` around its own backward pass,
+    clears ``params.grad`` before it and consumes the gradient before the next one; only then is the buffer itself returned."""
     _need_gpu(dpred)
     eng = _ENGINES.get(engine)
     if eng is None:
@@ -91,7 +92,7 @@ def eps_backward(dpred: torch.Tensor, engine: int, generation: int) -> torch.Ten
         raise RuntimeError("smd_amd::eps_backward: the engine has run another training forward pass since this one (one "
                            "workspace per handle: call backward() before the next model(x, cond), or use a second handle)")
     eng.backward_from(dpred)
-    return eng.grads.detach()
+    return eng.grads.detach() if getattr(eng, "_grad_alias_ok", False) else eng.grads.clone()
 
 
 @eps_backward.register_fake

@@ -167,11 +167,15 @@ def _train_step_generic(objective, batch, optimizer: Optimizer, sigmas, rng, lea
     if not (torch.is_tensor(loss) and loss.requires_grad and loss.numel() == 1):
         raise ValueError("train_step: objective(batch, model, sigmas, rng, continuous_noise, 'mean') must return a scalar tensor "
                          "computed from model(x, cond)")
-    loss.backward()
+    eng._grad_alias_ok = True               # params.grad is None and is consumed below: eps_backward may hand autograd the buffer itself
+    try:
+        loss.backward()
+    finally:
+        eng._grad_alias_ok = False
     if dm.params.grad is None:
         raise ValueError("train_step: the objective did not reach the model's parameters")
     # the engine's gradient buffer holds the last backward pass; autograd's accumulated leaf gradient is the authoritative one
-    # (it may BE the engine's buffer: eps_backward returns an alias that autograd can adopt)
+    # (it may BE the engine's buffer: under _grad_alias_ok eps_backward returns an alias that autograd can adopt)
     if dm.params.grad.data_ptr() != eng.grads.data_ptr():
         eng.grads.copy_(dm.params.grad)
     dm.params.grad = None

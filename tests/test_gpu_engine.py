@@ -890,17 +890,9 @@ def test_two_chain_sampler_equals_one_chain_and_eager(rng_impl, infill, monkeypa
         assert rel(x2[m], x1[m]) < 5e-3
 
 
-def test_train_step_arbitrary_objective_through_autograd():
-    """train_ncsn.py:279-283 differentiates ANY objective callable with jax.value_and_grad.  Here: a Huber and an L1 denoising
-    objective written in torch against ``model(x, cond)``; ``train_step`` differentiates them through smd_amd::eps_forward_train
-    (forward in the training workspace, backward = the engine's backward pass from d objective / d eps_hat).  Oracle: the same
-    objective on the fp64 restatement under torch autograd.  Tolerances of SURVEY 8c for the smooth objective (loss 5e-3,
-    gradient 1e-2); the L1 objective's d/d eps_hat is sign(residual), so every residual smaller than the bf16 forward error
-    flips a whole +-1/N entry: measured 1.6e-2, bound 3e-2."""
-    import smd_amd.ncsn as N
-    from smd_amd.trainer import create_optimizer, train_step
-    ocfg, p, model = make(C=42, L=2, K=1)
-    B = 8
+def _denoising_objectives(B):
+    """(x0, objective_of): objective_of("huber" | "l1") is a denoising objective written in torch against ``model(x, cond)``,
+    in the trainer's signature, on fixed draws (C = 42 data)."""
     x0, g = data(B, (32, 42))
     eps = torch.randn(B, 32, 42, generator=g)
     a = 0.05 + 0.9 * torch.rand(B, generator=g)
@@ -915,7 +907,21 @@ def test_train_step_arbitrary_objective_through_autograd():
             per = (r.abs() if kind == "l1" else torch.nn.functional.huber_loss(r, torch.zeros_like(r), reduction="none", delta=0.5)).mean(dim=(1, 2))
             return per.mean() if reduction == "mean" else per.sum()
         return objective
+    return x0, objective_of
 
+
+def test_train_step_arbitrary_objective_through_autograd():
+    """train_ncsn.py:279-283 differentiates ANY objective callable with jax.value_and_grad.  Here: a Huber and an L1 denoising
+    objective written in torch against ``model(x, cond)``; ``train_step`` differentiates them through smd_amd::eps_forward_train
+    (forward in the training workspace, backward = the engine's backward pass from d objective / d eps_hat).  Oracle: the same
+    objective on the fp64 restatement under torch autograd.  Tolerances of SURVEY 8c for the smooth objective (loss 5e-3,
+    gradient 1e-2); the L1 objective's d/d eps_hat is sign(residual), so every residual smaller than the bf16 forward error
+    flips a whole +-1/N entry: measured 1.6e-2, bound 3e-2."""
+    import smd_amd.ncsn as N
+    from smd_amd.trainer import create_optimizer, train_step
+    ocfg, p, model = make(C=42, L=2, K=1)
+    B = 8
+    x0, objective_of = _denoising_objectives(B)
     opt = create_optimizer(model, 1e-3, ema=False)
     for kind, tol in (("huber", 1e-2), ("l1", 3e-2)):
         model.engine.load_named(p)                                                 # both objectives from the same parameters
@@ -944,6 +950,97 @@ def test_train_step_arbitrary_objective_through_autograd():
 
     with pytest.raises(RuntimeError, match="another training forward"):
         train_step(twice, x0, opt, BETAS, N.PRNGKey(0), 1e-3)
+
+
+def test_gradient_accumulation_through_the_public_autograd_op():
+    """Model.differentiable() is the public way to train with any objective (train_ncsn.py:279-283).  Its gradient must behave
+    like any torch leaf gradient: a second backward pass ACCUMULATES (g1 + g2), a ``.grad`` reference kept across passes keeps
+    its value, zero_grad(set_to_none=False) followed by one pass gives that pass's gradient.  smd_amd::eps_backward therefore
+    hands autograd fresh storage, not the engine's gradient buffer (which the handle's next backward pass overwrites: with the
+    alias, two passes gave 2 g2).  g1, g2: each objective's gradient from a clean pass; the engine is deterministic, so the
+    accumulated gradient is BITWISE the fp32 sum g1 + g2.  Oracle: the fp64 restatement under torch autograd, bounds of
+    test_train_step_arbitrary_objective_through_autograd (Huber 1e-2, L1 3e-2).  Last: trainer.train_step keeps its zero-copy
+    path (autograd adopts the engine's buffer itself) and leaves no gradient on the leaf."""
+    import smd_amd.ncsn as N
+    from smd_amd.trainer import create_optimizer, train_step
+    ocfg, p, model = make(C=42, L=2, K=1)
+    B = 8
+    x0, objective_of = _denoising_objectives(B)
+    dm = model.differentiable()
+    eng = dm.engine
+    xd = x0.cuda()
+
+    def backward(kind):
+        objective_of(kind)(xd, dm, None, None, True, "mean").backward()
+
+    def clean(kind):
+        dm.params.grad = None
+        backward(kind)
+        out = dm.params.grad.clone()
+        dm.params.grad = None
+        return out
+
+    g1, g2 = clean("huber"), clean("l1")
+    assert torch.equal(clean("huber"), g1)                                          # deterministic, so "bitwise" is meaningful
+    assert not torch.equal(g1, g2)
+    ref = {}
+    for kind in ("huber", "l1"):
+        leaf = {k: v.clone().requires_grad_(True) for k, v in p.items()}
+        objective_of(kind)(x0.double(), O.make_model(leaf, ocfg), None, None, True, "mean").backward()
+        ref[kind] = {k: v.grad for k, v in leaf.items()}
+
+    def vs_oracle(flat, want):
+        gv = eng.named_views(flat)
+        num = sum(float((gv[k].double().cpu() - want[k]).pow(2).sum()) for k in want)
+        den = sum(float(want[k].pow(2).sum()) for k in want)
+        return (num / den) ** 0.5
+
+    e1, e2 = vs_oracle(g1, ref["huber"]), vs_oracle(g2, ref["l1"])
+    # (1) two backward passes without zeroing
+    dm.params.grad = None
+    backward("huber")
+    backward("l1")
+    acc = dm.params.grad.clone()
+    e_sum = vs_oracle(acc, {k: ref["huber"][k] + ref["l1"][k] for k in ref["huber"]})
+    print(f"accumulated gradient: max |acc - (g1 + g2)| {float((acc - (g1 + g2)).abs().max()):.3e} (|g2| max {float(g2.abs().max()):.3e}); "
+          f"vs fp64 oracle: g1 {e1:.3e}, g2 {e2:.3e}, g1 + g2 {e_sum:.3e}")
+    assert torch.equal(acc, g1 + g2), "the second backward pass did not accumulate onto the first"
+    assert e1 < 1e-2 and e2 < 3e-2 and e_sum < 3e-2
+    # (2) a reference kept across passes
+    dm.params.grad = None
+    backward("huber")
+    kept = dm.params.grad
+    dm.params.grad = None
+    backward("l1")
+    assert torch.equal(kept, g1), "a .grad reference kept after backward 1 was overwritten by backward 2"
+    assert torch.equal(dm.params.grad, g2) and dm.params.grad.data_ptr() != kept.data_ptr()
+    # (3) zero_grad(set_to_none=False) -- the optimiser's in-place zeroing -- then one pass
+    sgd = torch.optim.SGD([dm.params], lr=0.0)
+    dm.params.grad = None
+    backward("huber")
+    sgd.zero_grad(set_to_none=False)
+    assert float(dm.params.grad.abs().max()) == 0.0
+    backward("l1")
+    assert torch.equal(dm.params.grad, g2), "after zero_grad(set_to_none=False) one pass did not give that pass's gradient"
+    assert float(eng.grads.abs().max()) > 0                                         # the public path leaves the engine's buffer alone too
+    dm.params.grad = None
+    # (4) the trainer's generic path: oracle parity, no gradient left on the leaf, and NO copy of the gradient
+    model.engine.load_named(p)
+    opt = create_optimizer(model, 1e-3, ema=False)
+    dmt = opt._differentiable = model.differentiable()                              # the handle train_step differentiates through
+    seen = []
+    dmt.params.register_post_accumulate_grad_hook(lambda t: seen.append(t.grad.data_ptr()))
+    _, m = train_step(objective_of("huber"), xd, opt, BETAS, N.PRNGKey(0), 1e-3, grad_clip=1e9)     # the batch of g1
+    m = m.resolve()
+    e4 = vs_oracle(opt.engine.grads, ref["huber"])
+    want = float(objective_of("huber")(x0.double(), O.make_model(p, ocfg), None, None, True, "mean"))
+    print(f"train_step generic: gradient rel {e4:.3e}; loss {m['loss']:.6f} vs {want:.6f}; leaf gradient storage "
+          f"{'IS' if seen == [opt.engine.grads.data_ptr()] else 'is NOT'} the engine's buffer")
+    assert e4 < 1e-2 and abs(m["loss"] - want) / want < 5e-3
+    assert torch.equal(opt.engine.grads, g1)                                        # the step applied exactly the clean-pass gradient
+    assert dmt.params.grad is None
+    assert seen == [opt.engine.grads.data_ptr()], "train_step's generic path no longer hands the engine's buffer to autograd (a copy)"
+    assert not getattr(opt.engine, "_grad_alias_ok", False)
 
 
 @pytest.mark.parametrize("arch,unroll", [("TransformerDDPM", 1), ("TransformerDDPM", 4), ("TransformerDDPM", 8), ("DenseDDPM", 4)])

@@ -7,6 +7,9 @@
     random-init ones every other parity test uses (outlier features, grown FiLM scales: what bf16 trunk storage and the e4m3
     row scales are sensitive to); the trained parameters are exported through named_views and forward / loss / gradient /
     three reverse steps are compared again at B = 256, in bf16 and fp8 (utils/losses.py:250-308, train_ncsn.py:260-288).
+(c) full-length walks of the large network (L8 H16 K3) and of the fp8 networks, and of the production two-chain arrangement
+    (B = 128: two software-pipelined chains of 64) on the fused step's own Philox draws, against the exact fp64 oracle and, for
+    fp8, the e4m3-emulating oracle.
 
 Tolerances: SURVEY section 8(c).  A free-running walk has no per-step bound there (the bf16 eps_hat error of each step is fed
 back into the state); the bound asserted here is the measured divergence with head-room, printed per snapshot.
@@ -54,6 +57,7 @@ def step_noise(B, C, t):
 @pytest.mark.parametrize("name,C,L,H,K,B,odt,tol_state,tol_metric", [
     ("small", 42, 2, 8, 1, 4, torch.float64, 1.5e-2, 2e-3),      # measured (profiles/r5b_full_walk_tests.txt): 5.6e-3 / 2.1e-4
     ("base", 512, 6, 8, 2, 2, torch.float64, 1.5e-2, 2e-3),      # measured: 6.6e-3 / 1.2e-4
+    ("large", 512, 8, 16, 3, 2, torch.float64, 1.5e-2, 2e-3),    # L8 H16 K3 (bench --full's large network): the bounds of the rows above
 ])
 def test_full_T_walk_against_the_fp64_oracle(name, C, L, H, K, B, odt, tol_state, tol_metric):
     import smd_amd.ncsn as N
@@ -349,3 +353,122 @@ def test_sampler_at_the_reference_default_batch_and_at_ragged_batches(B, sizes, 
     # a second call goes through the cached graphs and is bitwise the first
     xa, ca, ma = N.diffusion_dynamics(key, model, BETAS, init, t_stop=t_stop)
     assert torch.equal(xa, x2) and torch.equal(ca, c2) and torch.equal(ma, m2)
+
+
+# ------------------------------------------------------------------ full-length walks: two pipelined chains, fp8
+# Bounds (none fitted to a measurement of these walks): bf16 against the exact fp64 oracle, and fp8 against the e4m3-emulating oracle
+# (oracle/e4m3_emulation.py: the engine's rounding points, so what is left is accumulation order), are those of
+# test_full_T_walk_against_the_fp64_oracle: state and every snapshot 1.5e-2, slope / step metrics 2e-3.  fp8 against the EXACT
+# oracle: SURVEY 8(c)'s fp8 eps_hat tolerance, 5e-2, on the state and the snapshots.
+def _oracle_walk(tag, model_fn, init, noises):
+    """oracle/ddpm_oracle.diffusion_dynamics of ``model_fn`` over all T = 1000 steps, on at most 8 host threads (a handful of rows:
+    the fork / join of every small op dominates on more), host time printed."""
+    import time
+    nthreads = torch.get_num_threads()
+    torch.set_num_threads(min(8, nthreads))
+    t0 = time.perf_counter()
+    try:
+        with torch.no_grad():
+            out = O.diffusion_dynamics(model_fn, BETAS, init, noises)
+    finally:
+        torch.set_num_threads(nthreads)
+    print(f"[{tag}] oracle walk, {init.shape[0]} rows: {time.perf_counter() - t0:.1f} s of host time")
+    return out
+
+
+def _walk_vs(tag, x, coll, ref_x, ref_c, tol):
+    """final state and the 39 written snapshots (slot 1 never written) of an engine walk against an oracle walk of the same rows"""
+    table = O.collection_index_table(1000)
+    slot_t = {O.collection_slot_for_t(1000, t, table): t for t in range(1000) if O.collection_slot_for_t(1000, t, table) >= 0}
+    assert sorted(slot_t) == list(range(2, 41))
+    assert float(coll[1].abs().max()) == 0.0 and float(ref_c[1].abs().max()) == 0.0
+    per_slot = []
+    for k in range(2, 41):
+        assert float(coll[k].abs().max()) > 0
+        per_slot.append(rel(coll[k], ref_c[k]))
+    e_final = rel(x, ref_x)
+    worst = max(range(39), key=lambda i: per_slot[i])
+    print(f"[{tag}] final state rel {e_final:.3e} (bound {tol:.1e}); snapshot rel by t: "
+          + " ".join(f"{slot_t[k]}:{per_slot[k - 2]:.1e}" for k in (2, 8, 14, 20, 27, 33, 39, 40))
+          + f"; worst {per_slot[worst]:.3e} at t = {slot_t[worst + 2]}")
+    assert e_final < tol and max(per_slot) < tol
+    assert float(x.abs().max()) <= 1.0 + 1e-6                      # the t = 0 step returns the clipped x0 (SURVEY 8c)
+
+
+@pytest.mark.parametrize("name,L,H,K", [("base", 6, 8, 2), ("large", 8, 16, 3)])
+def test_full_T_fp8_walk_against_the_e4m3_emulating_and_the_exact_oracle(name, L, H, K):
+    """--dtype=fp8 (BASELINE config 5; bench --full walks the fp8 base and large networks): one chain, explicit per-step noise, all
+    1000 steps, against (i) the e4m3-emulating oracle and (ii) the exact fp64 oracle (bounds: the section comment).
+    B = 8: the engine takes the e4m3 DenseResBlock GEMMs only for R = B * 32 rows that are a multiple of 256 (csrc/engine.hip); at
+    B = 2 an fp8 model walks bitwise its bf16 walk (measured), which would leave the fp8 path untested.  Every per-row quantity of
+    the network -- the e4m3 row scales included -- is per sequence, so the oracles walk two of the eight rows, 0 and 7."""
+    import e4m3_emulation as F8
+    import smd_amd.ncsn as N
+    C, B, rows = 512, 8, [0, 7]
+    ocfg, p, model = make(C, L, H, K, dtype="fp8")
+    init = torch.randn(B, 32, C, generator=torch.Generator().manual_seed(2718))
+    x, coll, met = N.diffusion_dynamics(N.PRNGKey(0), model, BETAS, init, noises=lambda t: step_noise(B, C, t))
+    _, _, model16 = make(C, L, H, K, dtype="bf16")
+    x16, _, m16 = N.diffusion_dynamics(N.PRNGKey(0), model16, BETAS, init, noises=lambda t: step_noise(B, C, t))
+    torch.cuda.synchronize()
+    assert tuple(coll.shape) == (41, B, 32, C) and tuple(met.shape) == (4, 1000, 1)
+    assert torch.equal(coll[0].cpu(), init)
+    print(f"[{name} fp8] B = {B}: final state rel to the bf16 model's walk {rel(x, x16):.3e}")
+    assert not torch.equal(x, x16), "the fp8 model walked bitwise its bf16 walk: the e4m3 path did not engage"
+    xs, cs = x[rows], coll[:, rows]
+    noises = lambda t: step_noise(B, C, t)[rows].double()
+    emu = _oracle_walk(f"{name} fp8 / e4m3 oracle", F8.make_model(p, ocfg), init[rows].double(), noises)
+    _walk_vs(f"{name} fp8 vs e4m3-emulating oracle", xs, cs, emu[0], emu[1], 1.5e-2)
+    ex = _oracle_walk(f"{name} fp8 / exact oracle", O.make_model(p, ocfg), init[rows].double(), noises)
+    _walk_vs(f"{name} fp8 vs exact fp64 oracle", xs, cs, ex[0], ex[1], 5e-2)
+    # ld_metrics are means over all 8 rows, which the oracles' 2-row walks do not restate: the alpha row (table data) against the
+    # oracle, the noise row (norms of the explicit draws, model-independent) against the bf16 model's walk of the same draws
+    assert rel(met[2].cpu().double(), ex[2][2]) < 1e-6 and float(met[3, -1, 0]) == pytest.approx(1e-5, rel=1e-2)
+    assert rel(met[3], m16[3]) < 1e-6
+
+
+@pytest.mark.parametrize("name,L,H,K,dtype", [("base", 6, 8, 2, "bf16"), ("large", 8, 16, 3, "bf16"), ("base", 6, 8, 2, "fp8")])
+def test_full_T_two_pipelined_chains_against_the_fp64_oracle(name, L, H, K, dtype, monkeypatch):
+    """The production arrangement for B >= 128: two software-pipelined chains (64 + 64 here, 8 iterations per captured graph), the
+    fused step's own Philox draws, all 1000 steps.  The oracle walks only the rows at the chain ends and either side of the split,
+    {0, 1, 63, 64, 65, 127}, on the same draws (philox_step_noise): final state and all 39 snapshots of those rows against it
+    (bounds: the section comment).  The ld_metrics are means over all 128 rows, which a 6-row oracle walk does not restate: the
+    alpha row is checked against the oracle's table, slope / step / noise against the one-chain walk of the same batch and draws
+    (bounds of test_sampler_at_the_reference_default_batch_and_at_ragged_batches), whose own metrics the one-chain tests above
+    check against the oracle."""
+    import e4m3_emulation as F8
+    import smd_amd.ncsn as N
+    C, B, seed = 512, 128, 4099
+    ocfg, p, model = make(C, L, H, K, dtype=dtype)
+    init = torch.randn(B, 32, C, generator=torch.Generator().manual_seed(161))
+    for v in ("SMD_SAMPLER_CHAINS", "SMD_SAMPLER_PIPELINE", "SMD_SAMPLER_UNROLL"):
+        monkeypatch.delenv(v, raising=False)
+    x, coll, met = N.diffusion_dynamics(N.PRNGKey(seed), model, BETAS, init)
+    torch.cuda.synchronize()
+    arr = model.sampler_arrangement
+    assert arr["chains"] == 2 and arr["chain_sizes"] == [64, 64] and arr["padded"] == 0 and arr["pipelined_unroll"] == 8 and arr["graphed"]
+    assert tuple(coll.shape) == (41, B, 32, C) and tuple(met.shape) == (4, 1000, 1)
+    assert torch.equal(coll[0].cpu(), init)
+    idx = [0, 1, 63, 64, 65, 127]
+    xs, cs = x[idx], coll[:, idx]
+    noises = lambda t: philox_step_noise(idx, t, seed, 32 * C).view(len(idx), 32, C).double()
+    tag = f"{name} {dtype} two chains"
+    ex = _oracle_walk(f"{tag} / exact oracle", O.make_model({k: v.double() for k, v in p.items()}, ocfg), init[idx].double(), noises)
+    if dtype == "fp8":
+        emu = _oracle_walk(f"{tag} / e4m3 oracle", F8.make_model(p, ocfg), init[idx].double(), noises)
+        _walk_vs(f"{tag} vs e4m3-emulating oracle", xs, cs, emu[0], emu[1], 1.5e-2)
+    _walk_vs(f"{tag} vs exact fp64 oracle", xs, cs, ex[0], ex[1], 5e-2 if dtype == "fp8" else 1.5e-2)
+    per_row = [rel(xs[j], ex[0][j]) for j in range(len(idx))]
+    print(f"[{tag}] final state rel per row {dict(zip(idx, (f'{e:.1e}' for e in per_row)))}")
+    # metrics: the alpha row is table data; the rest against the one-chain walk of the same batch
+    assert rel(met[2].cpu().double(), ex[2][2]) < 1e-6
+    monkeypatch.setenv("SMD_SAMPLER_CHAINS", "1")
+    x1, _c1, m1 = N.diffusion_dynamics(N.PRNGKey(seed), model, BETAS, init)
+    torch.cuda.synchronize()
+    assert model.sampler_arrangement["chains"] == 1
+    e_rows = [rel(met[r], m1[r]) for r in range(4)]
+    print(f"[{tag}] metrics vs the one-chain walk: slope {e_rows[0]:.2e} step {e_rows[1]:.2e} noise {e_rows[3]:.2e} (bound 2e-3); "
+          f"state rel {rel(x, x1):.2e}")
+    assert torch.equal(met[2], m1[2])
+    assert e_rows[0] < 2e-3 and e_rows[1] < 2e-3 and e_rows[3] < 2e-3
+    assert float(met[3, -1, 0]) == pytest.approx(1e-5, rel=1e-2)                    # t = 0: z = 0

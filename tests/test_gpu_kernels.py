@@ -59,7 +59,11 @@ def test_probe_tr_read(L, dev):
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 384, 128), (300, 42, 192), (1000, 4096, 512),
                                    (8192, 2048, 2048), (64, 512, 2048), (512, 128, 2048), (96, 200, 1024),
-                                   (8192, 128, 2048)])      # the last three: 32-row tiles with two K-groups per workgroup
+                                   (8192, 128, 2048), (2080, 512, 2048), (4000, 510, 2048)])
+# default forms (gemm_nt.hip): (64, 512, 2048) one 64-row tile per CU with two K-groups; (512, 128, 2048), (96, 200, 1024)
+# 32-row tiles with two K-groups per workgroup.  The last three take the out_proj form (N <= 512,
+# K >= 2048, M >= 2048: 128-row tiles with two K-groups per workgroup): a full grid, a ragged M (2080 = 16 x 128 + 32) and an N
+# that is not a multiple of 4 (510: every pointer check of the quad epilogue fails, the scalar epilogue writes the tail columns)
 def test_gemm_nt_plain(L, dev, M, N, K):
     g = torch.Generator().manual_seed(M * 7 + N * 3 + K)
     A = bf(torch.randn(M, K, generator=g))
@@ -583,6 +587,118 @@ def test_attn_block_bwd_with_both_layernorm_backwards(L, dev, rows, H):
     assert rel(p2, p23) < 1e-6
     assert rel(dhD, dh3) < 1e-3 and rel(p1[:, 0].sum(0), dg3) < 1e-3 and rel(p1[:, 1].sum(0), db3) < 1e-3      # (inherits those flips)
     assert float((dh_o.float() - o3.float()).abs().max()) <= float(o3.float().abs().max()) * 2 ** -7       # at most one bf16 step apart
+
+
+def test_part_stride_is_validated_and_a_padded_stride_is_honoured(L, dev):
+    """The four entries that read four fp32 partial tiles (parts + k * part_stride, as float2) -- smd_ln128_parts,
+    smd_ln128_bwd_parts, smd_attn_block_fwd_ex, smd_attn_block_bwd_ln -- must refuse (ValueError from lib.check, nothing
+    launched) a stride that would misalign the float2 loads (odd), overlap the tiles (< rows * 128), or point backwards
+    (negative), and a misaligned tile pointer.  The cases that stay inside the allocation come first, so that on a build
+    without the check the test fails before it could launch a wild read.  A padded stride (rows * 128 + 64, the gaps
+    filled with NaN) must give bitwise the result of the dense layout, and that result the fp64 reference."""
+    import smd_amd.lib as lib
+    rows, E, H = 64, 128, 8
+    dense, padded = rows * E, rows * E + 64
+    g = torch.Generator().manual_seed(4242)
+    parts = torch.randn(4, rows, E, generator=g) * 0.7
+    dparts = torch.randn(4, rows, E, generator=g) * 0.02
+    x = torch.randn(rows, E, generator=g) * 1.3 + 0.2
+    h = torch.randn(rows, E, generator=g) * 0.9 - 0.1
+    dres = 0.05 * torch.randn(rows, E, generator=g)
+    gamma, beta = 1 + 0.2 * torch.randn(E, generator=g), 0.1 * torch.randn(E, generator=g)
+    gamma2, beta2 = 1 + 0.2 * torch.randn(E, generator=g), 0.1 * torch.randn(E, generator=g)
+    Wqkv = bf(torch.randn(E, 3 * E, generator=g) * 0.12)
+    bqkv, bo = 0.1 * torch.randn(3 * E, generator=g), 0.1 * torch.randn(E, generator=g)
+    Wo = bf(torch.randn(E, E, generator=g) * 0.09)
+    qkv = bf(torch.randn(rows, 3 * E, generator=g) * 0.8)
+    D = lambda t: t.contiguous().to(dev)
+    xD, hD, gD, bD, g2D, b2D = D(x), D(h), D(gamma), D(beta), D(gamma2), D(beta2)
+    WqtD, WotD, WqD, WoD, bqD, boD, qkvD = D(Wqkv.t()), D(Wo.t()), D(Wqkv), D(Wo), D(bqkv), D(bo), D(qkv)
+
+    def laid_out(tiles, stride):
+        buf = torch.full((4 * stride + 2,), float("nan"), device=dev)          # + 2: room for the misaligned-pointer case
+        for k in range(4):
+            buf[k * stride:k * stride + dense] = tiles[k].reshape(-1).to(dev)
+        return buf
+
+    def ln128_parts(buf, stride, off=0):
+        xo, lo = torch.full((rows, E), float("nan"), device=dev), torch.zeros(rows, E, dtype=torch.bfloat16, device=dev)
+        return L.smd_ln128_parts(P(buf) + 4 * off, stride, rows, P(gD), P(bD), P(xo), P(lo), st()), (xo, lo)
+
+    def ln128_bwd_parts(buf, stride, off=0):
+        dx, dxb = D(dres), torch.zeros(rows, E, dtype=torch.bfloat16, device=dev)
+        partial = torch.zeros(rows // 32, 2, E, device=dev)
+        return L.smd_ln128_bwd_parts(P(xD), P(buf) + 4 * off, stride, rows, P(gD), P(dx), P(dx), P(dxb), P(partial), st()), (dx, dxb, partial)
+
+    def attn_fwd_ex(buf, stride, off=0):
+        comb, out = torch.full((rows, E), float("nan"), device=dev), torch.full((rows, E), float("nan"), device=dev)
+        a2 = torch.zeros(rows, E, dtype=torch.bfloat16, device=dev)
+        return L.smd_attn_block_fwd_ex(None, P(buf) + 4 * off, stride, P(comb), P(out), rows, P(gD), P(bD), P(WqtD), P(bqD), P(WotD),
+                                       P(boD), H, P(g2D), P(b2D), P(a2), None, None, None, st()), (comb, out, a2)
+
+    def attn_bwd_ln(buf, stride, off=0):
+        dq, da1 = torch.zeros(rows, 3 * E, dtype=torch.bfloat16, device=dev), torch.zeros(rows, E, dtype=torch.bfloat16, device=dev)
+        mid, dho = torch.zeros(rows, E, dtype=torch.bfloat16, device=dev), torch.zeros(rows, E, dtype=torch.bfloat16, device=dev)
+        dh = D(dres)
+        p2, p1 = torch.zeros(rows // 32, 2, E, device=dev), torch.zeros(rows // 32, 2, E, device=dev)
+        return L.smd_attn_block_bwd_ln(P(qkvD), P(WoD), P(WqD), P(dq), P(da1), P(xD), P(buf) + 4 * off, stride, P(g2D), P(dh), P(mid),
+                                       P(p2), P(hD), P(g1D), P(dho), P(p1), rows, H, st()), (dq, da1, mid, dho, dh, p2, p1)
+
+    g1D = gD
+    entries = {"smd_ln128_parts": (ln128_parts, parts), "smd_ln128_bwd_parts": (ln128_bwd_parts, dparts),
+               "smd_attn_block_fwd_ex": (attn_fwd_ex, parts), "smd_attn_block_bwd_ln": (attn_bwd_ln, dparts)}
+    # ---- rejection, memory-safe cases first: odd, overlapping, a misaligned tile pointer; only then a negative stride
+    for name, (call, tiles) in entries.items():
+        buf = laid_out(tiles, padded)
+        for stride, off in ((dense + 1, 0), (dense - 2, 0), (dense, 1), (-dense, 0)):
+            rc, _ = call(buf, stride, off)
+            with pytest.raises(ValueError, match="part_stride"):
+                lib.check(rc, name)
+        torch.cuda.synchronize()
+    # ---- a padded stride: bitwise the dense layout, and the fp64 reference
+    got = {}
+    for name, (call, tiles) in entries.items():
+        bd, bp = laid_out(tiles, dense), laid_out(tiles, padded)
+        rd, outs_d = call(bd, dense)
+        rp, outs_p = call(bp, padded)
+        lib.check(rd, name)
+        lib.check(rp, name)
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(outs_d, outs_p)), f"{name}: padded stride != dense stride"
+        got[name] = outs_p
+
+    def ln64(v, gm, bt):
+        mu, var = v.mean(-1, keepdim=True), v.var(-1, unbiased=False, keepdim=True)
+        return (v - mu) / torch.sqrt(var + 1e-6) * gm.double() + bt.double()
+
+    def ln_bwd64(v, gm, dout):
+        vr = v.double().requires_grad_(True)
+        gr, br = gm.double().requires_grad_(True), torch.zeros(E, dtype=torch.float64, requires_grad=True)
+        O.layer_norm(vr, {"n.scale": gr, "n.bias": br}, "n").backward(dout.double())
+        return vr.grad, gr.grad, br.grad
+
+    s = (parts[0] + parts[1]) + (parts[2] + parts[3])                           # the kernels' fixed summation order, fp32
+    ds = dparts.double().sum(0)
+    xo, lo = got["smd_ln128_parts"]
+    e_ln = rel(lo.float(), ln64(s.double(), gamma, beta))
+    dx, dxb, partial = got["smd_ln128_bwd_parts"]
+    dxr, dgr, dbr = ln_bwd64(x, gamma, ds)
+    e_dx, e_dg = rel(dx, dxr + dres.double()), max(rel(partial[:, 0].sum(0), dgr), rel(partial[:, 1].sum(0), dbr))
+    comb, out, a2 = got["smd_attn_block_fwd_ex"]
+    plain = torch.empty(rows, E, device=dev)
+    sD = D(s)
+    lib.check(L.smd_attn_block_fwd(P(sD), P(plain), rows, P(gD), P(bD), P(WqtD), P(bqD), P(WotD), P(boD), H, None, None, None, st()))
+    torch.cuda.synchronize()
+    e_a2 = rel(a2.float(), ln64(out.double().cpu(), gamma2, beta2))
+    mid = got["smd_attn_block_bwd_ln"][2]
+    e_mid = rel(mid.float(), ln_bwd64(x, gamma2, ds)[0] + dres.double())
+    print(f"padded part_stride {padded}: ln128_parts ln {e_ln:.2e}; ln128_bwd_parts dx {e_dx:.2e} dgamma/dbeta {e_dg:.2e}; "
+          f"attn_block_fwd_ex a2 {e_a2:.2e}; attn_block_bwd_ln dh_mid {e_mid:.2e}")
+    assert torch.equal(xo.cpu(), s) and torch.equal(comb.cpu(), s)              # the four tiles, summed in the fixed order
+    assert e_ln < 4e-3                                                          # bf16 output (test_mlp_block_fwd_hidden_split)
+    assert e_dx < 2e-5 and e_dg < 2e-5                                          # fp32 (test_mlp_block_bwd_hidden_split)
+    assert torch.equal(out, plain) and e_a2 < 4e-3                              # test_attn_block_fwd_partial_sum_input_and_ln2
+    assert e_mid < 4e-3                                                         # test_attn_block_bwd_with_both_layernorm_backwards
 
 
 @pytest.mark.parametrize("D,film,swish", [(128, False, False), (2048, False, False), (2048, True, True),
