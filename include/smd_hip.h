@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SMD_ABI_VERSION 6   /* 6: smd_attn_block_bwd_ln (the attention backward with both LayerNorm backwards in the launch), "fused_attn_bwd" 2; 2: smd_ddpm_reverse_step takes T; hidden-split MLP, fp8, loss-side and Langevin entries; 3: smd_langevin_io table mode, debug snapshots; 4: one-sweep optimiser, "opt_overlap", smd_engine_join_update; 5: smd_build_id, smd_engine_sample_step_part, smd_engine_forward_train / backward_from; the lab hooks (tuning knobs, debug tensors, probes) moved to smd_hip_lab.h -- this header is the stable surface */
+#define SMD_ABI_VERSION 7   /* 7: smd_pair_kernel_sums, smd_moments (the evaluation distances of utils/metrics.py); 6: smd_attn_block_bwd_ln (the attention backward with both LayerNorm backwards in the launch), "fused_attn_bwd" 2; 2: smd_ddpm_reverse_step takes T; hidden-split MLP, fp8, loss-side and Langevin entries; 3: smd_langevin_io table mode, debug snapshots; 4: one-sweep optimiser, "opt_overlap", smd_engine_join_update; 5: smd_build_id, smd_engine_sample_step_part, smd_engine_forward_train / backward_from; the lab hooks (tuning knobs, debug tensors, probes) moved to smd_hip_lab.h -- this header is the stable surface */
 
 typedef uint16_t smd_bf16;
 typedef struct smd_engine smd_engine;
@@ -392,6 +392,28 @@ int smd_ddpm_reverse_step(float* x, const float* eps_hat, int B, int S, int C, c
                           const int32_t* t_ptr, const float* z_in, uint32_t seed_lo, uint32_t seed_hi,
                           uint32_t sample_offset, float* metrics_partial, float* collection,
                           const int32_t* slot_table, void* stream);
+
+/* ---- sample-quality distances (utils/metrics.py:24-77, called by sample_ncsn.py:69-186 evaluate()) on exact-fp32 MFMA ----
+ * smd_pair_kernel_sums: utils/metrics.py:57-77 (mmd_rbf, mmd_polynomial through sklearn 0.19 rbf_kernel / polynomial_kernel).
+ *   X (nx x d) and Y (ny x d) are row-major fp32 with row strides ldx, ldy (in floats).  ONE pass over X Y^T writes
+ *   out[0] = sum_ij exp(-gamma_rbf * max(d2_ij, 0)),  d2_ij = (-2 <x_i,y_j> + |x_i|^2) + |y_j|^2 (euclidean_distances' order)
+ *   out[1] = sum_ij (gamma_poly * <x_i,y_j> + coef0)^degree
+ *   as fp64 (device pointer, 2 doubles); the nx x ny kernel matrix is never formed.  symmetric != 0: Y is X (y and ldy are
+ *   ignored, nx == ny), only the upper triangle of tiles runs and d2 is 0 on the diagonal (sklearn's `X is Y`).  Any d >= 1,
+ *   integer degree >= 1.  Deterministic: a second call on the same inputs gives the same bits.  workspace: >=
+ *   smd_pair_kernel_sums_workspace_bytes(nx, ny, symmetric) bytes, 8-byte aligned; x, y 4-byte aligned. */
+int64_t smd_pair_kernel_sums_workspace_bytes(int nx, int ny, int symmetric);
+int smd_pair_kernel_sums(const float* x, int64_t ldx, int nx, const float* y, int64_t ldy, int ny, int d, int symmetric,
+                         float gamma_rbf, float gamma_poly, float coef0, int degree, void* workspace, int64_t workspace_bytes,
+                         double* out, void* stream);
+/* smd_moments: utils/metrics.py:29-30 (np.mean(x, axis=0), np.cov(x, rowvar=False)) for X (n x d, row stride ld): mean [d]
+ *   and the ddof = 1 covariance cov [d][d] row-major, both fp64 (device pointers, 8-byte aligned).  The rows are centred in
+ *   fp64 and rounded to fp32 before their Gram is taken on the MFMA; n >= 2, 1 <= d <= SMD_MOMENTS_MAX_D.  workspace: >=
+ *   smd_moments_workspace_bytes(n, d) bytes, 8-byte aligned. */
+#define SMD_MOMENTS_MAX_D 1024
+int64_t smd_moments_workspace_bytes(int n, int d);
+int smd_moments(const float* x, int64_t ld, int n, int d, void* workspace, int64_t workspace_bytes, double* mean, double* cov,
+                void* stream);
 
 #ifdef __cplusplus
 }

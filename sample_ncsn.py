@@ -125,6 +125,51 @@ def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl,
     return np.stack(gens), np.stack(colls), ncsn.collate_sampling_metrics(ld.cpu().numpy())
 
 
+METRICS_NOT_UPSTREAM = ("precision", "recall", "f1", "improved_precision", "improved_recall", "improved_f1", "ipr_realism", "ndb")
+
+
+def evaluate(writer, real, collection, baseline, valid_real, compute_final_only=False, seed=1):
+    """sample_ncsn.py:69-186: the distance metrics of utils/metrics.py between the eval set ``real`` and 20 points of the
+    sampler's ``collection`` (T, N, *shape), the ``baseline`` (None: skipped), and two controls: ``random`` (standard normals
+    of the sample shape, drawn from a generator seeded by ``seed`` -- unseeded upstream) and ``real`` (``valid_real`` against
+    the eval set).  Scalars go to ``writer`` as {model}/{frechet_distance,mmd_rbf,mmd_polynomial} with step = i.
+
+    Definitions this port fixes: an (N, S, C) set is evaluated as N*S frames of C (upstream hands 3-D
+    arrays to np.cov, which raises); the returned stats are the final ``ncsn`` point (upstream: whatever the last loop
+    iteration left, the real-vs-real control).  The precision/recall, realism and NDB metrics of the reference's evaluate()
+    are not defined in its utils/metrics.py and are not computed."""
+    from smd_amd import metrics as M
+    assert tuple(collection.shape[1:]) == tuple(real.shape), (collection.shape, real.shape)
+    lo, hi = float(collection[-1].min()), float(collection[-1].max())
+    log.info(f"Generated sample range: [{lo}, {hi}]")
+    log.info(f"Test sample range: [{float(real.min())}, {float(real.max())}]")
+    if lo < -1.0 or hi > 1.0 or real.min() < -1 or real.max() > 1.0:
+        log.warning("Normalize test samples and generated samples to [-1, 1] range.")
+
+    gen_test_points = [collection[int(i)] for i in np.linspace(0, len(collection) - 1, 20).astype(np.uint32)]
+    if compute_final_only:
+        gen_test_points = [gen_test_points[-1]]
+    random_points = [np.random.default_rng(seed).standard_normal(tuple(collection[0].shape)).astype(np.float32)]
+    real_points = [valid_real]              # valid_real is real (the driver's call): the symmetric path, sklearn's X is Y
+
+    ref = M.ReferenceSet(real, collection.device if torch.is_tensor(collection) and collection.is_cuda else None)
+    stats = {}
+    for model, test_points in [("baseline", [baseline]), ("ncsn", gen_test_points), ("random", random_points),
+                               ("real", real_points)]:
+        if any(point is None for point in test_points):
+            continue
+        for i, samples in enumerate(test_points):
+            frechet_dist = M.frechet_distance(ref, samples)
+            mmds = M.kernel_mmds(ref, samples)
+            writer.scalar(f"{model}/frechet_distance", frechet_dist, step=i)
+            writer.scalar(f"{model}/mmd_rbf", mmds["mmd_rbf"], step=i)
+            writer.scalar(f"{model}/mmd_polynomial", mmds["mmd_polynomial"], step=i)
+            if model == "ncsn":
+                stats = {"frechet_dist": frechet_dist, "mmd_rbf": mmds["mmd_rbf"], "mmd_polynomial": mmds["mmd_polynomial"]}
+    writer.flush()
+    return stats
+
+
 def main(argv):
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     FLAGS = F.make_flags(include_sample=True)
@@ -138,6 +183,9 @@ def main(argv):
         raise SystemExit(f"Unknown sampling algorithm: {FLAGS.sampling}")
     if FLAGS.interpolate and FLAGS.sampling != "ddpm":
         raise SystemExit("--interpolate is a DDPM mode (sample_ncsn.py:250,270 assert it)")
+    if FLAGS.compute_metrics and FLAGS.interpolate:
+        raise SystemExit("--compute_metrics does not apply to --interpolate: its collection holds 9 interpolation points per "
+                         "sample, not the sample shape evaluate() compares with the eval set (sample_ncsn.py:92 asserts it)")
     torch.cuda.set_device(local_rank)
     dev = f"cuda:{local_rank}"
     if world > 1:
@@ -186,6 +234,9 @@ def main(argv):
         generated, collection, ld_metrics = generate_samples(FLAGS, model, rng, shape, hi - lo, sigmas, sample_offset=lo,
                                                              global_num_samples=num)
 
+    # evaluate() reads the device collection where there is one (a single rank); the shards of several ranks are gathered
+    # on the host below
+    coll_dev = collection if FLAGS.compute_metrics and world == 1 and torch.is_tensor(collection) else None
     generated = generated.cpu().numpy() if torch.is_tensor(generated) else generated
     collection = collection.cpu().numpy() if torch.is_tensor(collection) else collection
     if world > 1:                                                           # host-side gather of the shards
@@ -205,10 +256,17 @@ def main(argv):
             data.save(inv(collection, tmin, tmax), os.path.join(log_dir, "ncsn/collection.pkl"))
         data.save(inv(real, emin, emax), os.path.join(log_dir, "ncsn/real.pkl"))
         data.save(inv(generated, tmin, tmax), os.path.join(log_dir, "ncsn/generated.pkl"))
-        if FLAGS.compute_metrics:
-            log_langevin_dynamics(ld_metrics, 0, log_dir)
-            log.warning("--compute_metrics: the reference's evaluate() calls functions that do not exist in "
-                        "utils/metrics.py (SURVEY section 2); only the sampler scalars were written")
+    if rank == 0 and FLAGS.compute_metrics:                                 # :473-476, independent of --flush
+        from smd_amd import train_utils
+        log_dir = FLAGS.sampling_dir
+        log_langevin_dynamics(ld_metrics, 0, log_dir)
+        log.warning("--compute_metrics: %s of the reference's evaluate() call functions that utils/metrics.py does not define; "
+                    "only frechet_distance, mmd_rbf and mmd_polynomial are computed", ", ".join(METRICS_NOT_UPSTREAM))
+        writer = train_utils.JsonlWriter(log_dir)
+        stats = evaluate(writer, real, collection if coll_dev is None else coll_dev, None, real,
+                         compute_final_only=FLAGS.compute_final_only, seed=FLAGS.sample_seed)
+        writer.close()
+        train_utils.log_metrics(stats, 1, 1)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -54,7 +54,7 @@ class LangevinIO(C.Structure):
                 ("steps_per_level", c_i32), ("n_levels", c_i32)]
 
 
-ABI_VERSION = 6          # SMD_ABI_VERSION of include/smd_hip.h this table was written against
+ABI_VERSION = 7          # SMD_ABI_VERSION of include/smd_hip.h this table was written against
 
 # name -> (restype, argtypes).  Pointers are passed as integers (tensor.data_ptr()) via c_void_p.
 _SIGS = {
@@ -157,6 +157,11 @@ _SIGS = {
     "smd_probe_tr_read": (C.c_int, [c_void, c_void, c_void]),
     "smd_probe_stream_create_cu_mask": (C.c_int, [C.POINTER(c_u32), C.c_int, C.POINTER(c_void)]),
     "smd_probe_stream_destroy": (C.c_int, [c_void]),
+    "smd_pair_kernel_sums_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int]),
+    "smd_pair_kernel_sums": (C.c_int, [c_void, c_i64, C.c_int, c_void, c_i64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                       C.c_float, C.c_int, c_void, c_i64, c_void, c_void]),
+    "smd_moments_workspace_bytes": (c_i64, [C.c_int, C.c_int]),
+    "smd_moments": (C.c_int, [c_void, c_i64, C.c_int, C.c_int, c_void, c_i64, c_void, c_void, c_void]),
     "smd_probe_clock": (C.c_int, [c_void, C.c_int, C.c_int, c_void]),
     "smd_probe_l2_warm": (C.c_int, [c_void, c_i64, c_void, c_void]),
 }
