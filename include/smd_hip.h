@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SMD_ABI_VERSION 7   /* 7: smd_pair_kernel_sums, smd_moments (the evaluation distances of utils/metrics.py); 6: smd_attn_block_bwd_ln (the attention backward with both LayerNorm backwards in the launch), "fused_attn_bwd" 2; 2: smd_ddpm_reverse_step takes T; hidden-split MLP, fp8, loss-side and Langevin entries; 3: smd_langevin_io table mode, debug snapshots; 4: one-sweep optimiser, "opt_overlap", smd_engine_join_update; 5: smd_build_id, smd_engine_sample_step_part, smd_engine_forward_train / backward_from; the lab hooks (tuning knobs, debug tensors, probes) moved to smd_hip_lab.h -- this header is the stable surface */
+#define SMD_ABI_VERSION 8   /* 8: engine option "fp32" (reference-precision inference), smd_gemm_f32, smd_layernorm_f32, smd_attention_f32, smd_noise_embed_f32; 7: smd_pair_kernel_sums, smd_moments (the evaluation distances of utils/metrics.py); 6: smd_attn_block_bwd_ln (the attention backward with both LayerNorm backwards in the launch), "fused_attn_bwd" 2; 2: smd_ddpm_reverse_step takes T; hidden-split MLP, fp8, loss-side and Langevin entries; 3: smd_langevin_io table mode, debug snapshots; 4: one-sweep optimiser, "opt_overlap", smd_engine_join_update; 5: smd_build_id, smd_engine_sample_step_part, smd_engine_forward_train / backward_from; the lab hooks (tuning knobs, debug tensors, probes) moved to smd_hip_lab.h -- this header is the stable surface */
 
 typedef uint16_t smd_bf16;
 typedef struct smd_engine smd_engine;
@@ -78,6 +78,14 @@ int smd_engine_padded_channels(const smd_engine* e);
  *   "resgrad_bf16" 1     DenseResBlock residual-gradient chain in bf16
  *   "trunk_bf16" 2       2048-wide residual stream in bf16 (2: inference + training, 1: inference only, 0: fp32)
  *   "fp8" 0/1            e4m3 DenseResBlock forward GEMMs (BASELINE config 5); "w8_dirty" 1: operand pack changed elsewhere
+ *   "fp32" 0/1           reference precision, INFERENCE ONLY: every activation fp32, every Dense on the exact-fp32 MFMA reading
+ *                        the fp32 master parameters in place (no operand pack, no bf16 state copy is read; "trunk_bf16" is
+ *                        ignored).  Set before bind_workspace (the workspace grows).  Mutually exclusive with "fp8": setting
+ *                        one while the other is on is an argument error.  smd_engine_forward, _forward_level,
+ *                        _prepare_sampler and _sample_step work; smd_engine_sample_step_part with part 1 / 2 (the two-chain
+ *                        pipeline) is an argument error, and so are a training workspace, smd_engine_bind_train,
+ *                        _forward_train, _loss_backward, _backward_from and _optimizer_step ("fp32 is an inference precision
+ *                        in this engine"): train in bf16, audit or publish samples in fp32 from the same parameter buffer.
  *   "label_min" 1/0      Philox labels in [1, T] (continuous_noise) or [0, T);  "loss_kind" 0/1  DDPM / score matching
  *   "grad_memset" 2      0 never / 1 always / 2 only with the tr_path = 0 fallback: zero the gradient buffer before a step
  *                        (every gradient element is written, not accumulated, by the default kernels)
@@ -392,6 +400,26 @@ int smd_ddpm_reverse_step(float* x, const float* eps_hat, int B, int S, int C, c
                           const int32_t* t_ptr, const float* z_in, uint32_t seed_lo, uint32_t seed_hi,
                           uint32_t sample_offset, float* metrics_partial, float* collection,
                           const int32_t* slot_table, void* stream);
+
+/* ---- reference-precision (fp32) kernels of the engine option "fp32" -----------------------------------------------------
+ * smd_gemm_f32: out[m][n] = act(sum_k A[m][k] W[k][n] + bias[n]) + residual[m or m % res_row_mod][n], nn.Dense with A
+ *   (M x K, row stride lda) and W (K x N, row stride ldw: the flax kernel layout, read in place) fp32, on
+ *   v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation in k order.  act: SMD_EPI_*; bias and residual may be NULL;
+ *   residual may alias out; res_row_mod > 0 indexes the residual by m % res_row_mod (positional encoding).  Any M, N, K >= 1
+ *   (edges are masked; no padding is read or written).  All pointers 4-byte aligned (16-byte aligned operands with lda / ldw
+ *   and K / N multiples of 4 take vector loads).  An output element's bits depend on its row of A, its column of W and K only:
+ *   not on M, and two calls agree bitwise. */
+int smd_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int N, int K, const float* bias, int act,
+                 const float* residual, int ld_res, int res_row_mod, float* out, int ld_out, void* stream);
+/* flax LayerNorm (variance E[x^2] - mean^2, eps 1e-6) fp32 -> fp32, optional FiLM scale * ln + shift (row of the sample, or
+ * table row *t_ptr clamped to film_rows when t_ptr != NULL) and swish; any D >= 1 */
+int smd_layernorm_f32(const float* x, int rows, int D, const float* gamma, const float* beta, const float* film_scale,
+                      const float* film_shift, int ld_film, int rows_per_sample, const int32_t* t_ptr, int film_rows, int swish,
+                      float* out, void* stream);
+/* softmax((q / sqrt(d)) k^T) v in fp32: qkv [B*32][3E] = [q | k | v], out [B*32][E]; S == 32, d = E / H in {8, 16, 32} */
+int smd_attention_f32(const float* qkv, float* out, int B, int S, int E, int H, void* stream);
+/* NoiseEncoding (models/ncsn.py:28-41), fp32 rows: [sin | cos]((5000 s) f_i) with full range reduction */
+int smd_noise_embed_f32(const float* s, int n, int channels, float* out, int ld_out, void* stream);
 
 /* ---- sample-quality distances (utils/metrics.py:24-77, called by sample_ncsn.py:69-186 evaluate()) on exact-fp32 MFMA ----
  * smd_pair_kernel_sums: utils/metrics.py:57-77 (mmd_rbf, mmd_polynomial through sklearn 0.19 rbf_kernel / polynomial_kernel).

@@ -105,7 +105,7 @@ int smd_engine_set_option(smd_engine* e, const char* key, int value) {
   if (std::string(key) == "loss_kind") { e->impl.loss_kind = value ? 1 : 0; return 0; }
   if (std::string(key) == "label_min") { e->impl.label_min = value ? 1 : 0; return 0; }
   if (std::string(key) == "mlp_hs") { e->impl.mlp_hs = value ? 1 : 0; return 0; }
-  if (std::string(key) == "fp8") { e->impl.fp8 = value ? 1 : 0; return 0; }
+  if (std::string(key) == "fp8" || std::string(key) == "fp32") return e->impl.set_precision_option(key, value);
   if (std::string(key) == "fp8_dgrad") { e->impl.fp8_dgrad = value ? 1 : 0; return 0; }
   if (std::string(key) == "opt_overlap") { e->impl.opt_overlap = value & 3; return 0; }
   if (std::string(key) == "dp_layer_events") { e->impl.dp_layer_events = value ? 1 : 0; return 0; }

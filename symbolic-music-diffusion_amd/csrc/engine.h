@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "smd_kernels.h"
+#include "f32_kernels.h"
 
 struct SmdModelDesc {
   int arch = 0;              // 0 TransformerDDPM (models/ncsn.py:138-179), 1 DenseDDPM (:122-135)
@@ -76,8 +77,9 @@ class SmdEngine {
   int64_t head_param_offset() const { return head_off_; }   // params >= this belong to the output stage
   int64_t workspace_bytes(int batch, int training) const;
   // K tables [T][2M] fp32 + bf16 scratch for the T-row FiLM generator GEMMs (emb, f1, p)
+  // (option "fp32": the scratch holds fp32 rows, twice the size)
   int64_t film_table_floats() const {
-    return (int64_t)nblocks() * d_.num_timesteps * 2 * d_.mlp_dims + (int64_t)d_.num_timesteps * 9 * d_.film_channels / 2 + 64;
+    return (int64_t)nblocks() * d_.num_timesteps * 2 * d_.mlp_dims + (int64_t)d_.num_timesteps * 9 * d_.film_channels / (fp32 ? 1 : 2) + 64;
   }
   int padded_channels() const { return Cp_; }
 
@@ -195,12 +197,19 @@ class SmdEngine {
   // quantised per row next to the forward layout; the weight gradients and everything 128-wide stay bf16.
   int fp8_dgrad = 1;
   int mlp_hs = 1;              // hidden-split fused MLP half-layers (forward; backward with recompute); 0: the older paths
+  // Reference precision, inference only: every activation fp32, every Dense on the exact-fp32 MFMA reading the fp32 master
+  // parameters in place (gemm_f32.hip, net_f32.hip); the bf16 operand pack and the x_bf16 state copy are not read, trunk_bf16
+  // is ignored.  Mutually exclusive with fp8; set before bind_workspace.  Training entry points return an argument error.
+  int fp32 = 0;
+  int set_precision_option(const char* key, int value);   // "fp8" / "fp32"
 
  private:
   int nblocks() const { return d_.arch == 0 ? d_.num_mlp_layers : d_.num_layers; }
   int rows() const { return batch_ * d_.seq_len; }
   void build_layout();
-  int run_network(const int* t_ptr, hipStream_t st, int part = 0);          // x_bf16 (+ s or table row) -> pred
+  int run_network(const int* t_ptr, hipStream_t st, int part = 0, const float* x_f32 = nullptr);   // x_bf16 (+ s or table row) -> pred
+  int run_network_f32(const float* x, const int* t_ptr, hipStream_t st);    // option "fp32": x fp32 (+ s or table row) -> pred
+  int dense_f32(const DenseP& p, const float* A, int lda, int M, GemmF32Args g, hipStream_t st);
   int backward_head(hipStream_t st);
   int backward_stem(hipStream_t st);
   int dense_fwd(const DenseP& p, const bf16_t* A, int lda, int M, GemmEpilogue ep, hipStream_t st);
@@ -318,6 +327,10 @@ class SmdEngine {
     unsigned* step_arrive = nullptr;      // [64] arrival counter of the fused reverse step
     float* mlp_part = nullptr;            // [4][R][E] partial tiles of the hidden-split MLP kernels
     bf16_t* tn_scratch = nullptr;         // fallback wgrad transposes
+    // option "fp32" (inference workspaces only): LayerNorm output / q|k|v / attention output / MLP hidden of the encoder,
+    // FiLM-LayerNorm output and first Dense output of a DenseResBlock, FiLM generator rows; h[0], y[0], ss[0], pred are shared
+    float *f_a = nullptr, *f_qkv = nullptr, *f_o = nullptr, *f_u = nullptr, *f_ya = nullptr, *f_o1 = nullptr;
+    float *f_emb = nullptr, *f_f1 = nullptr, *f_p = nullptr;
     size_t tn_scratch_elems = 0;
   } W;
   int64_t plan(void* base, int batch, int training, Work* w) const;

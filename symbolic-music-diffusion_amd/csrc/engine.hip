@@ -29,6 +29,8 @@ const char* smd_get_error() { return g_err; }
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+static const char* const kFp32Refusal = "fp32 is an inference precision in this engine";
+
 int launch_pos_encoding(float* pe, int S, int channels, hipStream_t st);
 
 // ------------------------------------------------------------------ layout
@@ -381,6 +383,19 @@ int64_t SmdEngine::plan(void* base, int batch, int training, Work* w) const {
     t.tn_scratch_elems = tr_path ? 0 : (size_t)2 * (2 * M) * Mp;
     t.tn_scratch = t.tn_scratch_elems ? c.take<bf16_t>(t.tn_scratch_elems) : nullptr;
   }
+  if (fp32 && !training) {
+    if (L > 0) {
+      t.f_a = c.take<float>(R * E);
+      t.f_qkv = c.take<float>(R * 3 * E);
+      t.f_o = c.take<float>(R * E);
+      t.f_u = c.take<float>(R * M);
+    }
+    t.f_ya = c.take<float>(R * M);
+    t.f_o1 = c.take<float>(R * M);
+    t.f_emb = c.take<float>(B * F);
+    t.f_f1 = c.take<float>(B * 4 * F);
+    t.f_p = c.take<float>(B * 4 * F);
+  }
   if (w) *w = t;
   return (c.off + 255) / 256 * 256;
 }
@@ -394,11 +409,13 @@ int SmdEngine::bind_params(float* params, bf16_t* wpack) {
   return 0;
 }
 int SmdEngine::bind_train(float* grads, float* m, float* v, float* ema, uint32_t* step_ptr, float* metrics) {
+  SMD_ARG_CHECK(!fp32, "bind_train: %s", kFp32Refusal);
   SMD_ARG_CHECK(grads && m && v && step_ptr && metrics, "bind_train: null pointer");
   grads_ = grads; m_ = m; v_ = v; ema_ = ema; step_ptr_ = step_ptr; metrics_ = metrics;
   return 0;
 }
 int SmdEngine::bind_workspace(void* ws, int64_t bytes, int batch, int training, hipStream_t st) {
+  SMD_ARG_CHECK(!(fp32 && training), "bind_workspace: %s (training workspace)", kFp32Refusal);
   SMD_ARG_CHECK(ws && batch > 0, "bind_workspace: null workspace or batch=%d", batch);
   const int64_t need = plan(nullptr, batch, training, nullptr);
   SMD_ARG_CHECK(bytes >= need, "bind_workspace: %lld bytes given, %lld needed", (long long)bytes, (long long)need);
@@ -498,7 +515,11 @@ int SmdEngine::dense_bwd(const DenseP& p, const bf16_t* X, int ldx, const bf16_t
 // part 0: the whole network; 1: the stem only (x_bf16 -> trunk input: in_proj, encoder layers, final norm, up projection --
 // nothing in it depends on the noise level); 2: the output stage only (DenseResBlocks with their FiLM rows, output norm +
 // Dense).  The split passes serve the sampler's software pipeline (sample_step): one chain's stem beside another's head.
-int SmdEngine::run_network(const int* t_ptr, hipStream_t st, int part) {
+int SmdEngine::run_network(const int* t_ptr, hipStream_t st, int part, const float* x_f32) {
+  if (fp32) {
+    SMD_ARG_CHECK(part == 0, "run_network: the split passes (part=%d) are not available under fp32: walk one chain", part);
+    return run_network_f32(x_f32, t_ptr, st);
+  }
   SMD_ARG_CHECK(params_ && wpack_ && batch_ > 0, "run_network: engine not bound");
   SMD_ARG_CHECK(part == 0 || (part >= 1 && part <= 2 && !training_ && t_ptr), "run_network: split passes belong to the table-driven sampler");
   const int S = d_.seq_len, C = d_.data_channels, E = d_.embed_channels, M = d_.mlp_dims, F = d_.film_channels;
@@ -720,14 +741,90 @@ int SmdEngine::run_network(const int* t_ptr, hipStream_t st, int part) {
   return 0;
 }
 
+// ------------------------------------------------------------------ forward, reference precision (option "fp32")
+int SmdEngine::set_precision_option(const char* key, int value) {
+  const bool want32 = !strcmp(key, "fp32");
+  SMD_ARG_CHECK(!(value && (want32 ? fp8 : fp32)), "set_option: \"fp8\" and \"fp32\" are mutually exclusive");
+  SMD_ARG_CHECK(!(want32 && value && (training_ || grads_)), "set_option: %s", kFp32Refusal);
+  (want32 ? fp32 : fp8) = value ? 1 : 0;
+  return 0;
+}
+
+int SmdEngine::dense_f32(const DenseP& p, const float* A, int lda, int M, GemmF32Args g, hipStream_t st) {
+  g.A = A; g.lda = lda; g.W = P(p.w_off); g.ldw = p.N; g.bias = P(p.b_off); g.M = M; g.N = p.N; g.K = p.K;
+  return launch_gemm_f32(g, st);
+}
+
+// The reference's order (models/ncsn.py:141-179 / 125-135, models/shared.py:61-75), one launch per op, fp32 activations end
+// to end: x is the caller's fp32 state (no bf16 copy is read), the weights are the fp32 master parameters in place.
+int SmdEngine::run_network_f32(const float* x, const int* t_ptr, hipStream_t st) {
+  SMD_ARG_CHECK(params_ && batch_ > 0 && !training_, "run_network: bind the parameters and an inference workspace first");
+  SMD_ARG_CHECK(x, "run_network: null input");
+  SMD_ARG_CHECK(W.f_ya, "run_network: set the \"fp32\" option before bind_workspace");
+  SMD_ARG_CHECK(!t_ptr || film_tables_, "run_network: sampler tables not bound");
+  const int S = d_.seq_len, C = d_.data_channels, E = d_.embed_channels, M = d_.mlp_dims, F = d_.film_channels;
+  const int R = rows(), B = batch_, K = nblocks();
+  RC(join_update(st));
+  float* y = W.y[0];
+  auto ln = [&](const float* in, int D, const LnP& p, float* out) {
+    LnF32Args a;
+    a.x = in; a.rows = R; a.D = D; a.gamma = P(p.g_off); a.beta = P(p.b_off); a.out = out;
+    return a;
+  };
+  if (d_.arch == 0) {
+    float* h = W.h[0];
+    { GemmF32Args g; g.res = W.pe; g.ld_res = E; g.res_row_mod = S; g.out = h; g.ld_out = E;      // models/ncsn.py:152-157
+      RC(dense_f32(in_proj_, x, C, R, g, st)); }
+    for (int l = 0; l < d_.num_layers; ++l) {                                                       // :158-168
+      const EncLayerP& p = enc_[l];
+      RC(launch_layernorm_f32(ln(h, E, p.ln1, W.f_a), st));
+      { GemmF32Args g; g.out = W.f_qkv; g.ld_out = 3 * E; RC(dense_f32(p.qkv, W.f_a, E, R, g, st)); }
+      RC(launch_attention_f32(W.f_qkv, W.f_o, B, S, E, d_.num_heads, st));
+      { GemmF32Args g; g.res = h; g.ld_res = E; g.out = h; g.ld_out = E; RC(dense_f32(p.out, W.f_o, E, R, g, st)); }
+      RC(launch_layernorm_f32(ln(h, E, p.ln2, W.f_a), st));
+      { GemmF32Args g; g.act = SMD_F32_ACT_GELU; g.out = W.f_u; g.ld_out = M; RC(dense_f32(p.fc1, W.f_a, E, R, g, st)); }
+      { GemmF32Args g; g.res = h; g.ld_res = E; g.out = h; g.ld_out = E; RC(dense_f32(p.fc2, W.f_u, M, R, g, st)); }
+    }
+    RC(launch_layernorm_f32(ln(h, E, ln_f_, W.f_a), st));                                          // :170-171
+    { GemmF32Args g; g.out = y; g.ld_out = M; RC(dense_f32(up_, W.f_a, E, R, g, st)); }
+  } else {
+    GemmF32Args g; g.out = y; g.ld_out = M;                                                         // :129
+    RC(dense_f32(in_proj_, x, C, R, g, st));
+  }
+  if (!t_ptr) RC(launch_noise_embed_f32(W.s, B, F, W.f_emb, F, st));
+  for (int k = 0; k < K; ++k) {                                                                     // :173-175 / 130-132
+    const FilmResP& b = blk_[k];
+    const float* scale;
+    if (t_ptr) {
+      scale = film_tables_ + (size_t)k * d_.num_timesteps * 2 * M;
+    } else {
+      { GemmF32Args g; g.act = SMD_F32_ACT_SWISH; g.out = W.f_f1; g.ld_out = 4 * F; RC(dense_f32(b.f1, W.f_emb, F, B, g, st)); }
+      { GemmF32Args g; g.out = W.f_p; g.ld_out = 4 * F; RC(dense_f32(b.f2, W.f_f1, 4 * F, B, g, st)); }
+      { GemmF32Args g; g.out = W.ss[0]; g.ld_out = 2 * M; RC(dense_f32(b.ss, W.f_p, 4 * F, B, g, st)); }
+      scale = W.ss[0];
+    }
+    LnF32Args a = ln(y, M, b.ln1, W.f_ya);
+    a.film_scale = scale; a.film_shift = scale + M; a.ld_film = 2 * M; a.rows_per_sample = S; a.t_ptr = t_ptr;
+    a.film_rows = d_.num_timesteps; a.swish = 1;
+    RC(launch_layernorm_f32(a, st));
+    { GemmF32Args g; g.out = W.f_o1; g.ld_out = M; RC(dense_f32(b.r1, W.f_ya, M, R, g, st)); }
+    a.x = W.f_o1; a.gamma = P(b.ln2.g_off); a.beta = P(b.ln2.b_off);
+    RC(launch_layernorm_f32(a, st));
+    { GemmF32Args g; g.res = y; g.ld_res = M; g.out = y; g.ld_out = M; RC(dense_f32(b.r2, W.f_ya, M, R, g, st)); }
+  }
+  RC(launch_layernorm_f32(ln(y, M, ln_o_, W.f_ya), st));                                            // :177-178 / 133-134
+  { GemmF32Args g; g.out = W.pred; g.ld_out = C; RC(dense_f32(out_proj_, W.f_ya, M, R, g, st)); }
+  return 0;
+}
+
 int SmdEngine::forward(const float* x, const float* noise_level, float* eps_out, hipStream_t st) {
   SMD_ARG_CHECK(x && noise_level && eps_out, "forward: null pointer");
   SMD_ARG_CHECK(batch_ > 0 && !training_, "forward: bind an inference workspace first");
   const int R = rows(), C = d_.data_channels;
-  RC(launch_cast_pad_bf16(x, R, C, W.x_bf16, Cp_, st));
+  if (!fp32) RC(launch_cast_pad_bf16(x, R, C, W.x_bf16, Cp_, st));
   hipError_t e = hipMemcpyAsync(W.s, noise_level, sizeof(float) * batch_, hipMemcpyDeviceToDevice, st);
   if (e != hipSuccess) { smd_set_error("forward: memcpy: %s", hipGetErrorString(e)); return (int)e; }
-  RC(run_network(nullptr, st));
+  RC(run_network(nullptr, st, 0, x));
   e = hipMemcpyAsync(eps_out, W.pred, sizeof(float) * (size_t)R * C, hipMemcpyDeviceToDevice, st);
   if (e != hipSuccess) { smd_set_error("forward: memcpy: %s", hipGetErrorString(e)); return (int)e; }
   return 0;
@@ -737,8 +834,8 @@ int SmdEngine::forward_level(const float* x, const int* level_ptr, float* eps_ou
   SMD_ARG_CHECK(x && level_ptr, "forward_level: null pointer");
   SMD_ARG_CHECK(batch_ > 0 && !training_ && film_tables_, "forward_level: bind an inference workspace and the sampler tables first");
   const int R = rows(), C = d_.data_channels;
-  RC(launch_cast_pad_bf16(x, R, C, W.x_bf16, Cp_, st));
-  RC(run_network(level_ptr, st));
+  if (!fp32) RC(launch_cast_pad_bf16(x, R, C, W.x_bf16, Cp_, st));
+  RC(run_network(level_ptr, st, 0, x));
   if (!eps_out) return 0;                 // the caller reads the engine's own output buffer (smd_engine_pred)
   hipError_t e = hipMemcpyAsync(eps_out, W.pred, sizeof(float) * (size_t)R * C, hipMemcpyDeviceToDevice, st);
   if (e != hipSuccess) { smd_set_error("forward_level: memcpy: %s", hipGetErrorString(e)); return (int)e; }
@@ -1054,6 +1151,7 @@ int SmdEngine::backward_stem(hipStream_t st) {
 int SmdEngine::loss_backward(const float* x0, const int* labels, const float* eps_in, uint32_t seed_lo,
                              uint32_t seed_hi, uint32_t sample_offset, float inv_global_count, int stage,
                              hipStream_t st) {
+  SMD_ARG_CHECK(!fp32, "loss_backward: %s", kFp32Refusal);
   SMD_ARG_CHECK(training_ && alphas_prod_ext_, "loss_backward: bind a training workspace and the schedule first");
   SMD_ARG_CHECK(stage >= 0 && stage <= 3, "loss_backward: stage=%d", stage);
   SMD_ARG_CHECK(stage == 3 || grads_, "loss_backward: bind the optimiser state first");
@@ -1149,6 +1247,7 @@ int SmdEngine::finish_backward(hipStream_t st, bool stem_ran) {
 // The two halves of jax.value_and_grad over an ARBITRARY objective (train_ncsn.py:279-283): model(x, noise_level) in the training
 // workspace with every activation the backward needs saved, then the backward pass from d objective / d eps_hat.
 int SmdEngine::forward_train(const float* x, const float* noise_level, float* eps_out, hipStream_t st) {
+  SMD_ARG_CHECK(!fp32, "forward_train: %s", kFp32Refusal);
   SMD_ARG_CHECK(x && noise_level, "forward_train: null pointer");
   SMD_ARG_CHECK(training_ && batch_ > 0, "forward_train: bind a training workspace first");
   const int R = rows(), C = d_.data_channels;
@@ -1163,6 +1262,7 @@ int SmdEngine::forward_train(const float* x, const float* noise_level, float* ep
 }
 
 int SmdEngine::backward_from(const float* dpred, int stage, hipStream_t st) {
+  SMD_ARG_CHECK(!fp32, "backward_from: %s", kFp32Refusal);
   SMD_ARG_CHECK(training_ && grads_ && batch_ > 0, "backward_from: bind a training workspace and the optimiser state first");
   SMD_ARG_CHECK(stage >= 0 && stage <= 2, "backward_from: stage=%d", stage);
   SMD_ARG_CHECK(stage == 2 || dpred, "backward_from: null gradient");
@@ -1188,6 +1288,7 @@ int SmdEngine::backward_from(const float* dpred, int stage, hipStream_t st) {
 }
 
 int SmdEngine::optimizer_step(const TrainHyper& h, hipStream_t st) {
+  SMD_ARG_CHECK(!fp32, "optimizer_step: %s", kFp32Refusal);
   SMD_ARG_CHECK(grads_ && params_, "optimizer_step: not bound");
   SMD_ARG_CHECK(training_ && W.norm_partial, "optimizer_step: bind a training workspace first");
   RC(join_update(st));
@@ -1241,6 +1342,19 @@ int SmdEngine::prepare_sampler(hipStream_t st) {
   // scale/shift of every block depend on t only, so all T rows are generated once here.
   const int T = d_.num_timesteps, M = d_.mlp_dims, F = d_.film_channels, K = nblocks();
   float* tables_end = film_tables_ + (size_t)K * T * 2 * M;
+  if (fp32) {     // the same three Dense layers per block on the fp32 GEMM, fp32 rows in between
+    float* emb = tables_end;
+    float* f1 = emb + (size_t)T * F;
+    float* p = f1 + (size_t)T * 4 * F;
+    RC(launch_noise_embed_f32(sqrt_ap_, T, F, emb, F, st));
+    for (int k = 0; k < K; ++k) {
+      const FilmResP& b = blk_[k];
+      { GemmF32Args g; g.act = SMD_F32_ACT_SWISH; g.out = f1; g.ld_out = 4 * F; RC(dense_f32(b.f1, emb, F, T, g, st)); }
+      { GemmF32Args g; g.out = p; g.ld_out = 4 * F; RC(dense_f32(b.f2, f1, 4 * F, T, g, st)); }
+      { GemmF32Args g; g.out = film_tables_ + (size_t)k * T * 2 * M; g.ld_out = 2 * M; RC(dense_f32(b.ss, p, 4 * F, T, g, st)); }
+    }
+    return 0;
+  }
   bf16_t* emb = reinterpret_cast<bf16_t*>(tables_end);
   bf16_t* f1 = emb + (size_t)T * F;
   bf16_t* p = f1 + (size_t)T * 4 * F;
@@ -1271,7 +1385,8 @@ int SmdEngine::sample_step(const SampleStepIO& io, hipStream_t st, int part) {
   SMD_ARG_CHECK(io.x && io.t_ptr, "sample_step: null state / t pointer");
   SMD_ARG_CHECK(!training_ && coef_ && film_tables_, "sample_step: bind an inference workspace and the schedule tables first");
   SMD_ARG_CHECK(part >= 0 && part <= 2, "sample_step: part=%d (0 whole step, 1 stem, 2 output stage + reverse update)", part);
-  RC(run_network(io.t_ptr, st, part));
+  SMD_ARG_CHECK(!(fp32 && part != 0), "sample_step: part=%d is not available under fp32 (no two-chain pipeline): walk one chain with part 0", part);
+  RC(run_network(io.t_ptr, st, part, io.x));
   if (part == 1) return 0;
   ReverseStepArgs a;
   a.x = io.x; a.eps_hat = W.pred;

@@ -20,6 +20,10 @@ from . import lib as _lib
 from . import schedule as _sched
 
 ARCH_IDS = {"TransformerDDPM": 0, "TransformerDDPM4": 0, "DenseDDPM": 1}
+DTYPES = ("bf16", "fp8", "fp32")
+# what every training entry point answers on an fp32 engine (the library's argument errors carry the same sentence)
+FP32_REFUSAL = ("fp32 is an inference precision in this engine: train in bf16 or fp8 and load the checkpoint "
+                "(the same fp32 parameters) under dtype='fp32' to sample or audit")
 
 
 @dataclass
@@ -34,7 +38,9 @@ class NetConfig:
     num_mlp_layers: int = 2
     mlp_dims: int = 2048
     num_timesteps: int = 1000
-    dtype: str = "bf16"          # "fp8": e4m3 DenseResBlock forward GEMMs (--dtype=fp8, BASELINE config 5)
+    # "fp8": e4m3 DenseResBlock forward GEMMs (--dtype=fp8, BASELINE config 5); "fp32": reference precision, inference only --
+    # fp32 activations end to end, every Dense on the exact-fp32 MFMA from the fp32 master parameters (--dtype=fp32)
+    dtype: str = "bf16"
 
     @property
     def sample_shape(self) -> Tuple[int, ...]:
@@ -90,10 +96,10 @@ class Engine:
         h = C.c_void_p()
         _lib.check(self.L.smd_engine_create(C.byref(d), C.byref(h)), "smd_engine_create")
         self.h = h
-        if cfg.dtype not in ("bf16", "fp8"):
-            raise ValueError(f"dtype must be 'bf16' or 'fp8', got {cfg.dtype!r}")
-        if cfg.dtype == "fp8":
-            _lib.check(self.L.smd_engine_set_option(h, b"fp8", 1), "set_option fp8")
+        if cfg.dtype not in DTYPES:
+            raise ValueError(f"dtype must be one of {DTYPES}, got {cfg.dtype!r}")
+        if cfg.dtype in ("fp8", "fp32"):
+            _lib.check(self.L.smd_engine_set_option(h, cfg.dtype.encode(), 1), f"set_option {cfg.dtype}")
         self.S = d.seq_len
         self.C = cfg.data_channels
         self.n_params = int(self.L.smd_engine_param_count(h))
@@ -279,6 +285,8 @@ class Engine:
         self.generation += 1
 
     def enable_training(self, ema: bool) -> None:
+        if self.cfg.dtype == "fp32":
+            raise ValueError(FP32_REFUSAL)
         if self.grads is not None:
             return
         z = lambda: torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
@@ -341,6 +349,8 @@ class Engine:
     def forward_train(self, x: torch.Tensor, noise_level: torch.Tensor) -> torch.Tensor:
         """model(x, cond) through the TRAINING workspace (activations saved): the forward half of value_and_grad over an
         arbitrary objective (train_ncsn.py:279-283; include/smd_hip.h smd_engine_forward_train)."""
+        if self.cfg.dtype == "fp32":
+            raise ValueError(FP32_REFUSAL)
         if self.grads is None:
             raise RuntimeError("forward_train: a training handle (Model.train_engine / create_optimizer) is needed")
         x = x.to(self.device, torch.float32).contiguous()

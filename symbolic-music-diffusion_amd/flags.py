@@ -231,7 +231,10 @@ SAMPLE_FLAGS: List[FlagDef] = [
 ENGINE_FLAGS: List[FlagDef] = [
     _D("dtype", "enum", "bf16", "GEMM operand precision of the HIP path: bf16, or fp8 = OCP e4m3 operands with per-row "
        "E8M0 scales for the DenseResBlock forward GEMMs and (training, --fp8_dgrad) their input-gradient GEMMs "
-       "(BASELINE config 5); weight gradients and everything 128-wide stay bf16.", ("bf16", "fp8")),
+       "(BASELINE config 5); weight gradients and everything 128-wide stay bf16.  fp32 (sample_ncsn.py only): reference "
+       "precision -- fp32 activations end to end and every Dense on the exact-fp32 MFMA from the fp32 master parameters; "
+       "a checkpoint trained in bf16 / fp8 loads unchanged.  fp32 is an inference precision: train_ncsn.py refuses it.",
+       ("bf16", "fp8", "fp32")),
     _D("fp8_dgrad", "bool", True, "--dtype=fp8 training: the four DenseResBlock dgrad GEMMs (dX = dY W^T) on e4m3 operands too "
        "(gradient parity 1.6e-2 vs 1.4e-2 with bf16 dgrads; recorded in the checkpoint metadata).  --nofp8_dgrad: bf16 dgrads."),
     _D("trunk_dtype", "enum", "bf16", "Storage type of the 2048-wide residual trunk between the DenseResBlocks DURING TRAINING: "

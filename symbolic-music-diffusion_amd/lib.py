@@ -54,7 +54,7 @@ class LangevinIO(C.Structure):
                 ("steps_per_level", c_i32), ("n_levels", c_i32)]
 
 
-ABI_VERSION = 7          # SMD_ABI_VERSION of include/smd_hip.h this table was written against
+ABI_VERSION = 8          # SMD_ABI_VERSION of include/smd_hip.h this table was written against
 
 # name -> (restype, argtypes).  Pointers are passed as integers (tensor.data_ptr()) via c_void_p.
 _SIGS = {
@@ -162,6 +162,12 @@ _SIGS = {
                                        C.c_float, C.c_int, c_void, c_i64, c_void, c_void]),
     "smd_moments_workspace_bytes": (c_i64, [C.c_int, C.c_int]),
     "smd_moments": (C.c_int, [c_void, c_i64, C.c_int, C.c_int, c_void, c_i64, c_void, c_void, c_void]),
+    "smd_gemm_f32": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, C.c_int,
+                               C.c_int, c_void, C.c_int, c_void]),
+    "smd_layernorm_f32": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void, C.c_int, C.c_int, c_void, C.c_int,
+                                    C.c_int, c_void, c_void]),
+    "smd_attention_f32": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void]),
+    "smd_noise_embed_f32": (C.c_int, [c_void, C.c_int, C.c_int, c_void, C.c_int, c_void]),
     "smd_probe_clock": (C.c_int, [c_void, C.c_int, C.c_int, c_void]),
     "smd_probe_l2_warm": (C.c_int, [c_void, c_i64, c_void, c_void]),
 }

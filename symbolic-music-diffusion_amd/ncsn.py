@@ -130,6 +130,9 @@ class Model:
         return self._chain_engines
 
     def train_engine(self, ema: bool) -> Engine:
+        if self.cfg.dtype == "fp32":           # Model.differentiable(), create_optimizer
+            from .engine import FP32_REFUSAL
+            raise ValueError(FP32_REFUSAL)
         if self._train_engine is None:
             self._train_engine = Engine(self.cfg, str(self.engine.device), share_params_with=self.engine)
             self._train_engine.enable_training(ema)
@@ -594,6 +597,8 @@ def sampler_chain_sizes(model: "Model", B: int, graphed: bool, allow_pad: bool =
     ``allow_pad=False`` (jax.random streams: their counter layout is a function of the true array size): such a batch walks as one chain."""
     eng = model.engine
     if not graphed or os.environ.get("SMD_SAMPLER_CHAINS", "2") != "2" or B < 128 or eng.cfg.mlp_dims % 256:
+        return [B], 0
+    if getattr(eng.cfg, "dtype", "bf16") == "fp32":     # reference precision: no split passes (sample_step part 1 / 2), one chain
         return [B], 0
     gran = 256 // math.gcd(256, eng.S)                  # sequences per 256 token rows: 8 for S = 32, 256 for DenseDDPM
     pad = (-B) % gran

@@ -67,6 +67,9 @@ def eps_forward_train(x: torch.Tensor, noise_level: torch.Tensor, params: torch.
     eng = _ENGINES.get(engine)
     if eng is None:
         raise RuntimeError(f"smd_amd::eps_forward_train: no live engine with id {engine} (ops.register_engine)")
+    if eng.cfg.dtype == "fp32":
+        from .engine import FP32_REFUSAL
+        raise ValueError(FP32_REFUSAL)
     if params.data_ptr() != eng.params.data_ptr() or params.numel() != eng.params.numel():
         raise ValueError("smd_amd::eps_forward_train: `params` is not the engine's parameter buffer")
     return eng.forward_train(x, noise_level)

@@ -178,6 +178,9 @@ def main(argv):
         log.info("Platform: gfx950 HIP engine (smd_amd %s)", smd_amd.__version__)
     if FLAGS.loss not in ("ddpm", "dsm") or FLAGS.sampling not in ("ddpm", "ald", "cas"):
         raise SystemExit("this engine covers --loss=ddpm|dsm and --sampling=ddpm|ald|cas (ssm needs a double backward)")
+    if FLAGS.dtype == "fp32":
+        raise SystemExit("--dtype=fp32: fp32 is an inference precision in this engine; train with --dtype=bf16 or fp8 and "
+                         "sample the checkpoint with sample_ncsn.py --dtype=fp32")
     torch.cuda.set_device(local_rank)
     if world > 1:
         import torch.distributed as dist
