@@ -443,6 +443,27 @@ int64_t smd_moments_workspace_bytes(int n, int d);
 int smd_moments(const float* x, int64_t ld, int n, int d, void* workspace, int64_t workspace_bytes, double* mean, double* cov,
                 void* stream);
 
+/* ---- nearest-neighbour metrics (improved precision / recall and realism, Kynkaanniemi et al. 2019; the reference's
+ * sample_ncsn.py:148-157 logs them, DESIGN.md section 14 defines them) on the same Gram tile, the n x n distances never written ----
+ * smd_knn_radii: r2[i] (fp32, device) = the k-th smallest d2 from row i of X (n x d, row stride ld) to its OTHER rows -- self
+ *   is excluded by index, a duplicated row counts (and gives 0).  d2 = (-2 <x,y> + |x|^2) + |y|^2 clamped at 0, x = row i.
+ *   1 <= k <= SMD_KNN_MAX_K, n >= k + 1, any d >= 1.  No atomics: two calls give the same bits.  workspace: >=
+ *   smd_knn_radii_workspace_bytes(n, k) bytes, 8-byte aligned; x, r2 4-byte aligned. */
+#define SMD_KNN_MAX_K 8
+int64_t smd_knn_radii_workspace_bytes(int n, int k);
+int smd_knn_radii(const float* x, int64_t ld, int n, int d, int k, void* workspace, int64_t workspace_bytes, float* r2, void* stream);
+/* smd_ball_cover: for queries Q (nq x d) against centres X (nx x d) with squared radii r2[nx], ONE Gram pass writes
+ *   covered[j]  = 1 if some centre i has d2(q_j, x_i) <= r2[i], else 0 (uint8)
+ *   realism2[j] = max over the centres with keep[i] != 0 of min(r2[i] / max(d2(q_j, x_i), FLT_MIN), FLT_MAX), 0 if there is none
+ *   with d2 = (-2 <q,x> + |x_i|^2) + |q_j|^2 clamped at 0: the bits smd_knn_radii took r2[i] from when Q is X.  keep (nx bytes)
+ *   may be NULL: every centre is kept; coverage ignores it.  exclude_diagonal != 0 (nq == nx, Q is X): the pair (i, i) takes
+ *   part in neither output (leave-one-out).  OR and max do not depend on order: two calls give the same bits.  workspace: >=
+ *   smd_ball_cover_workspace_bytes(nq, nx) bytes, 8-byte aligned; q, x, r2, realism2 4-byte aligned. */
+int64_t smd_ball_cover_workspace_bytes(int nq, int nx);
+int smd_ball_cover(const float* q, int64_t ldq, int nq, const float* x, int64_t ldx, int nx, int d, const float* r2,
+                   const uint8_t* keep, int exclude_diagonal, void* workspace, int64_t workspace_bytes, uint8_t* covered,
+                   float* realism2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

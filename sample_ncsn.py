@@ -125,10 +125,12 @@ def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl,
     return np.stack(gens), np.stack(colls), ncsn.collate_sampling_metrics(ld.cpu().numpy())
 
 
-METRICS_NOT_UPSTREAM = ("precision", "recall", "f1", "improved_precision", "improved_recall", "improved_f1", "ipr_realism", "ndb")
+NN_METRICS = ("improved_precision", "improved_recall", "improved_f1", "ipr_realism")      # --nn_metrics computes these
+METRICS_KMEANS = ("precision", "recall", "f1", "ndb")                                    # PRD histogram and NDB: not computed
+METRICS_NOT_UPSTREAM = METRICS_KMEANS[:3] + NN_METRICS + METRICS_KMEANS[3:]
 
 
-def evaluate(writer, real, collection, baseline, valid_real, compute_final_only=False, seed=1):
+def evaluate(writer, real, collection, baseline, valid_real, compute_final_only=False, seed=1, nn_metrics=False, nn_k=3):
     """sample_ncsn.py:69-186: the distance metrics of utils/metrics.py between the eval set ``real`` and 20 points of the
     sampler's ``collection`` (T, N, *shape), the ``baseline`` (None: skipped), and two controls: ``random`` (standard normals
     of the sample shape, drawn from a generator seeded by ``seed`` -- unseeded upstream) and ``real`` (``valid_real`` against
@@ -137,7 +139,9 @@ def evaluate(writer, real, collection, baseline, valid_real, compute_final_only=
     Definitions this port fixes: an (N, S, C) set is evaluated as N*S frames of C (upstream hands 3-D
     arrays to np.cov, which raises); the returned stats are the final ``ncsn`` point (upstream: whatever the last loop
     iteration left, the real-vs-real control).  The precision/recall, realism and NDB metrics of the reference's evaluate()
-    are not defined in its utils/metrics.py and are not computed."""
+    are not defined in its utils/metrics.py.  ``nn_metrics``: additionally {model}/{improved_precision,improved_recall,
+    improved_f1,ipr_realism} as DESIGN.md section 14 defines them (radius = distance to the ``nn_k``-th neighbour), for the same
+    points and steps, and the same four keys in the returned stats; the k-means metrics (PRD histogram, NDB) are not computed."""
     from smd_amd import metrics as M
     assert tuple(collection.shape[1:]) == tuple(real.shape), (collection.shape, real.shape)
     lo, hi = float(collection[-1].min()), float(collection[-1].max())
@@ -166,6 +170,12 @@ def evaluate(writer, real, collection, baseline, valid_real, compute_final_only=
             writer.scalar(f"{model}/mmd_polynomial", mmds["mmd_polynomial"], step=i)
             if model == "ncsn":
                 stats = {"frechet_dist": frechet_dist, "mmd_rbf": mmds["mmd_rbf"], "mmd_polynomial": mmds["mmd_polynomial"]}
+            if nn_metrics:
+                nn = M.improved_metrics(ref, samples, nn_k)
+                for name in NN_METRICS:
+                    writer.scalar(f"{model}/{name}", nn[name], step=i)
+                if model == "ncsn":
+                    stats.update(nn)
     writer.flush()
     return stats
 
@@ -186,6 +196,13 @@ def main(argv):
     if FLAGS.compute_metrics and FLAGS.interpolate:
         raise SystemExit("--compute_metrics does not apply to --interpolate: its collection holds 9 interpolation points per "
                          "sample, not the sample shape evaluate() compares with the eval set (sample_ncsn.py:92 asserts it)")
+    if FLAGS.nn_metrics and FLAGS.interpolate:
+        raise SystemExit("--nn_metrics does not apply to --interpolate: there is no collection of the sample shape to compare "
+                         "with the eval set")
+    if FLAGS.nn_metrics and not FLAGS.compute_metrics:
+        raise SystemExit("--nn_metrics adds the nearest-neighbour metrics to the evaluation: it needs --compute_metrics")
+    if FLAGS.nn_metrics and not 1 <= FLAGS.nn_k <= 8:
+        raise SystemExit(f"--nn_k={FLAGS.nn_k}: the radius is the distance to the k-th neighbour for k from 1 to 8")
     torch.cuda.set_device(local_rank)
     dev = f"cuda:{local_rank}"
     if world > 1:
@@ -260,11 +277,17 @@ def main(argv):
         from smd_amd import train_utils
         log_dir = FLAGS.sampling_dir
         log_langevin_dynamics(ld_metrics, 0, log_dir)
-        log.warning("--compute_metrics: %s of the reference's evaluate() call functions that utils/metrics.py does not define; "
-                    "only frechet_distance, mmd_rbf and mmd_polynomial are computed", ", ".join(METRICS_NOT_UPSTREAM))
+        if FLAGS.nn_metrics:
+            log.warning("--compute_metrics: %s of the reference's evaluate() call functions that utils/metrics.py does not define "
+                        "and are not computed; %s are computed as DESIGN.md section 14 defines them (k = %d)",
+                        ", ".join(METRICS_KMEANS), ", ".join(NN_METRICS), FLAGS.nn_k)
+        else:
+            log.warning("--compute_metrics: %s of the reference's evaluate() call functions that utils/metrics.py does not define; "
+                        "only frechet_distance, mmd_rbf and mmd_polynomial are computed", ", ".join(METRICS_NOT_UPSTREAM))
         writer = train_utils.JsonlWriter(log_dir)
         stats = evaluate(writer, real, collection if coll_dev is None else coll_dev, None, real,
-                         compute_final_only=FLAGS.compute_final_only, seed=FLAGS.sample_seed)
+                         compute_final_only=FLAGS.compute_final_only, seed=FLAGS.sample_seed, nn_metrics=FLAGS.nn_metrics,
+                         nn_k=FLAGS.nn_k)
         writer.close()
         train_utils.log_metrics(stats, 1, 1)
     if world > 1:

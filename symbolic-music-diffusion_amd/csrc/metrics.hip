@@ -9,49 +9,10 @@
 //
 // Determinism: every workgroup writes its fp64 partial to a slot of its own and a second launch sums the slots in a fixed
 // order, so two calls on the same inputs give the same bits.  Nothing is allocated and nothing waits on the host.
-#include "smd_common.h"
+#include "gram_tile.h"
 #include "../../include/smd_hip.h"
 
 namespace {
-
-constexpr int MT = 128;        // workgroup tile: MT x MT outputs, 4 waves of 64 x 64 (2 x 2 MFMA tiles of 32 x 32)
-constexpr int BK = 16;         // k per LDS stage
-constexpr int LDP = MT + 4;    // LDS pitch in floats: the transposing stores of the pair loader hit 64 distinct banks
-constexpr int NT = 256;
-constexpr int LOADS = MT * BK / NT;   // 8 floats per operand per thread and stage
-
-// One LDS stage: As / Bs hold [BK][LDP] (k-major), wave (wr, wc) owns rows wr*64.. and columns wc*64.. of the tile.
-// 32x32x2 operand map: lane l supplies A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31].
-__device__ __forceinline__ void mfma_stage(const float* As, const float* Bs, int wr, int wc, int lane, f32x16_t (&acc)[2][2]) {
-  const int li = lane & 31, lk = lane >> 5;
-#pragma unroll
-  for (int kk = 0; kk < BK; kk += 2) {
-    float a[2], b[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) a[m] = As[(kk + lk) * LDP + wr * 64 + m * 32 + li];
-#pragma unroll
-    for (int n = 0; n < 2; ++n) b[n] = Bs[(kk + lk) * LDP + wc * 64 + n * 32 + li];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m], b[n], acc[m][n], 0, 0, 0);
-  }
-}
-
-// C/D map of the 32x32 MFMA: column lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-__device__ __forceinline__ int cd_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
-
-// ---------------------------------------------------------------------------------------------------- row norms
-// |x_i|^2 as ONE fmaf chain in k order from 0 -- the same chain the MFMA forms for <x_i, x_i> (zero padding adds exact
-// zeros), so a row against itself or its duplicate gives d2 = (-2n + n) + n = 0 exactly.
-__global__ __launch_bounds__(256) void row_norms_kernel(const float* __restrict__ x, int n, int d, int64_t ld, float* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float* r = x + (int64_t)i * ld;
-  float s = 0.0f;
-  for (int k = 0; k < d; ++k) s = fmaf(r[k], r[k], s);
-  out[i] = s;
-}
 
 // ---------------------------------------------------------------------------------------------------- pair sums
 struct PairArgs {
@@ -289,10 +250,6 @@ __global__ __launch_bounds__(256) void cov_reduce_kernel(const double* __restric
   for (int s = 0; s < splits; ++s) acc += part[(int64_t)s * dd + e];
   cov[e] = acc / (double)(n - 1);
 }
-
-inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-inline int64_t up8(int64_t b) { return (b + 7) & ~(int64_t)7; }
 
 int64_t pair_tiles(int nx, int ny, int symmetric) {
   const int64_t tx = (nx + MT - 1) / MT, ty = (ny + MT - 1) / MT;

@@ -248,6 +248,9 @@ ENGINE_FLAGS: List[FlagDef] = [
     _D("synthetic", "bool", False, "Use synthetic latents clip(0.25*N(0,1),-1,1) instead of --dataset."),
     _D("synthetic_examples", "int", 4096, "Synthetic examples per epoch."),
     _D("sample_ema", "bool", False, "sample_ncsn: sample from the EMA weights (reference uses raw weights)."),
+    _D("nn_metrics", "bool", False, "sample_ncsn --compute_metrics: also compute the nearest-neighbour metrics improved_precision, "
+       "improved_recall, improved_f1 and ipr_realism (Kynkaanniemi et al. 2019, DESIGN.md section 14)."),
+    _D("nn_k", "int", 3, "--nn_metrics: the neighbour whose distance is a row's radius (1..8)."),
     _D("graph", "bool", True, "Capture the sampling step in a hipGraph."),
     _D("ckpt_format", "enum", "safetensors", "Checkpoint file format written by train_ncsn: safetensors, or the "
        "reference's flax-0.3.0 msgpack state dict (both are recognised when restoring).", ("safetensors", "flax")),

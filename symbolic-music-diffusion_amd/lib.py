@@ -162,6 +162,11 @@ _SIGS = {
                                        C.c_float, C.c_int, c_void, c_i64, c_void, c_void]),
     "smd_moments_workspace_bytes": (c_i64, [C.c_int, C.c_int]),
     "smd_moments": (C.c_int, [c_void, c_i64, C.c_int, C.c_int, c_void, c_i64, c_void, c_void, c_void]),
+    "smd_knn_radii_workspace_bytes": (c_i64, [C.c_int, C.c_int]),
+    "smd_knn_radii": (C.c_int, [c_void, c_i64, C.c_int, C.c_int, C.c_int, c_void, c_i64, c_void, c_void]),
+    "smd_ball_cover_workspace_bytes": (c_i64, [C.c_int, C.c_int]),
+    "smd_ball_cover": (C.c_int, [c_void, c_i64, C.c_int, c_void, c_i64, C.c_int, C.c_int, c_void, c_void, C.c_int, c_void, c_i64,
+                                 c_void, c_void, c_void]),
     "smd_gemm_f32": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, C.c_int,
                                C.c_int, c_void, C.c_int, c_void]),
     "smd_layernorm_f32": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void, C.c_int, C.c_int, c_void, C.c_int,

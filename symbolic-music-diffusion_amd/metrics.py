@@ -10,6 +10,10 @@ diagonal distances are exactly zero (and the MMD is exactly 0).
 The Frechet trace term tr sqrtm(S1 S2) is evaluated on the host in float64 as sum sqrt(max(eig(S1^1/2 S2 S1^1/2), 0)) with
 ``numpy.linalg.eigh``: equal for covariance matrices, and real on rank-deficient inputs where scipy's sqrtm can go complex.
 Only the eigenvalues that a covariance of n <= d rows has to be zero (beyond rank n - 1) are set to zero.
+
+``precision_recall``, ``realism_scores`` and ``f1_score`` are the nearest-neighbour metrics the reference's evaluate() logs as
+improved_precision / improved_recall / improved_f1 / ipr_realism (sample_ncsn.py:148-157) and its utils/metrics.py does not
+define: Kynkaanniemi et al. 2019 as fixed in DESIGN.md section 14, on csrc/nn_metrics.hip (``knn_radii``, ``ball_cover``).
 """
 from __future__ import annotations
 
@@ -80,6 +84,66 @@ def pair_kernel_sums(x: torch.Tensor, y: Optional[torch.Tensor] = None, gamma_rb
     return out
 
 
+def _check_rows(name: str, *ts: torch.Tensor) -> None:
+    for t in ts:
+        if t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or t.device != ts[0].device:
+            raise ValueError(f"{name} takes fp32 (n, d) cuda tensors on one device")
+
+
+def knn_radii(x: torch.Tensor, k: int = 3) -> torch.Tensor:
+    """Device fp32 tensor r2[n]: the squared distance from each row of the fp32 (n, d) cuda tensor ``x`` to its k-th nearest
+    OTHER row (self excluded by index: a duplicated row gives 0).  1 <= k <= 8 and n >= k + 1.  Enqueued on the current
+    stream, nothing waits; two calls give the same bits."""
+    L = _lib.get_lib()
+    _check_rows("knn_radii", x)
+    if int(k) != k:
+        raise ValueError(f"k={k!r}: knn_radii takes an integer k")
+    x = _rows(x)
+    n, d = x.shape
+    ws_bytes = L.smd_knn_radii_workspace_bytes(n, int(k))
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=x.device)
+    r2 = torch.empty(n, dtype=torch.float32, device=x.device)
+    _lib.check(L.smd_knn_radii(x.data_ptr(), x.stride(0), n, d, int(k), ws.data_ptr(), ws_bytes, r2.data_ptr(), _stream(x.device)),
+               "smd_knn_radii")
+    return r2
+
+
+def ball_cover(q: torch.Tensor, x: torch.Tensor, r2: torch.Tensor, keep: Optional[torch.Tensor] = None,
+               exclude_diagonal: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One pass over the pairs of the queries ``q`` (nq, d) and the centres ``x`` (nx, d) with squared radii ``r2`` (nx):
+    (covered, realism2) = (uint8[nq]: some centre j has |q - x_j|^2 <= r2[j];  fp32[nq]: max over the centres with ``keep[j]``
+    (None: all) of r2[j] / max(|q - x_j|^2, FLT_MIN)).  ``exclude_diagonal`` (q is x): pair (i, i) takes no part."""
+    L = _lib.get_lib()
+    _check_rows("ball_cover", q, x)
+    q, x = _rows(q), _rows(x)
+    nq, d = q.shape
+    nx, dx = x.shape
+    if dx != d:
+        raise ValueError(f"ball_cover: d mismatch ({d} vs {dx})")
+    if r2.shape != (nx,) or r2.dtype != torch.float32 or r2.device != x.device:
+        raise ValueError(f"ball_cover: r2 must be an fp32 tensor of {nx} squared radii on the centres' device")
+    r2 = r2.contiguous()
+    if keep is not None:
+        if keep.shape != (nx,) or keep.device != x.device:
+            raise ValueError(f"ball_cover: keep must be a mask of {nx} centres on their device")
+        keep = (keep != 0).to(torch.uint8).contiguous()
+    ws_bytes = L.smd_ball_cover_workspace_bytes(nq, nx)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=x.device)
+    covered = torch.empty(nq, dtype=torch.uint8, device=x.device)
+    realism2 = torch.empty(nq, dtype=torch.float32, device=x.device)
+    _lib.check(L.smd_ball_cover(q.data_ptr(), q.stride(0), nq, x.data_ptr(), x.stride(0), nx, d, r2.data_ptr(),
+                                None if keep is None else keep.data_ptr(), int(bool(exclude_diagonal)), ws.data_ptr(), ws_bytes,
+                                covered.data_ptr(), realism2.data_ptr(), _stream(x.device)), "smd_ball_cover")
+    return covered, realism2
+
+
+def median_keep_mask(r2: torch.Tensor) -> torch.Tensor:
+    """The paper's pruning of the largest spheres for the realism score: uint8 mask of the rows whose radius sqrt(r2) is at
+    most ``numpy.median`` of the radii (the mean of the two middle ones for an even count)."""
+    r = np.sqrt(r2.cpu().numpy().astype(np.float64))
+    return torch.from_numpy((r <= np.median(r)).astype(np.uint8)).to(r2.device)
+
+
 def moments(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """np.mean(x, axis=0), np.cov(x, rowvar=False) (ddof = 1) of an fp32 (n, d) cuda tensor as fp64 device tensors."""
     L = _lib.get_lib()
@@ -148,6 +212,7 @@ class ReferenceSet:
         self._moments = None
         self._sqrt = None
         self._kxx: Dict[tuple, np.ndarray] = {}
+        self._radii: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
 
     def moments(self) -> Tuple[np.ndarray, np.ndarray]:
         if self._moments is None:
@@ -167,6 +232,13 @@ class ReferenceSet:
         if key not in self._kxx:
             self._kxx[key] = pair_kernel_sums(self.frames, None, *key).cpu().numpy()
         return self._kxx[key]
+
+    def radii(self, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(r2, keep): the squared k-NN radii of the frames and the mask of those at most the median radius"""
+        if k not in self._radii:
+            r2 = knn_radii(self.frames, k)
+            self._radii[k] = (r2, median_keep_mask(r2))
+        return self._radii[k]
 
     def is_same(self, other) -> bool:
         return other is self or other is self.source
@@ -223,3 +295,54 @@ def mmd_rbf(real, fake, gamma: float = 1.0) -> float:
 def mmd_polynomial(real, fake, degree: int = 2, gamma: float = 1, coef0: float = 0) -> float:
     """utils/metrics.py:68-77 (lower is better)."""
     return kernel_mmds(real, fake, degree=degree, gamma_poly=gamma, coef0=coef0)["mmd_polynomial"]
+
+
+def f1_score(p: float, r: float) -> float:
+    """2 p r / (p + r), and 0 when p + r = 0."""
+    return 2.0 * p * r / (p + r) if p + r > 0 else 0.0
+
+
+def _against_real_balls(ref: ReferenceSet, fake, k: int):
+    """(covered, realism2, fake frames or None when ``fake`` is the reference set itself): the fake rows against the real rows'
+    k-NN balls, coverage and realism from one pass"""
+    x = ref.frames
+    r2x, keep = ref.radii(k)
+    if ref.is_same(fake):
+        return ball_cover(x, x, r2x, keep, exclude_diagonal=True) + (None,)
+    y = as_frames(fake, x.device)
+    if y.shape[1] != x.shape[1]:
+        raise ValueError(f"nearest-neighbour metrics: d mismatch ({x.shape[1]} vs {y.shape[1]})")
+    return ball_cover(y, x, r2x, keep) + (y,)
+
+
+def _recall(ref: ReferenceSet, y: Optional[torch.Tensor], cov: torch.Tensor, k: int) -> float:
+    if y is None:                       # the reference set against itself: recall is precision
+        return float(cov.double().mean())
+    return float(ball_cover(ref.frames, y, knn_radii(y, k))[0].double().mean())
+
+
+def improved_metrics(real, fake, k: int = 3) -> Dict[str, float]:
+    """improved_precision, improved_recall, improved_f1 and ipr_realism (the mean realism score) of one comparison (DESIGN.md
+    section 14) from three passes: the fake set's radii, fake against the real balls (precision and realism together) and real
+    against the fake balls (recall).  ``real`` may be a ReferenceSet, whose radii and median mask are then computed once for all
+    calls.  When ``fake`` is the reference set itself, pair (i, i) is excluded: the leave-one-out scores of the real data."""
+    ref = _ref(real, _device(real, fake))
+    cov, real2, y = _against_real_balls(ref, fake, int(k))
+    p, r = float(cov.double().mean()), _recall(ref, y, cov, int(k))
+    return {"improved_precision": p, "improved_recall": r, "improved_f1": f1_score(p, r),
+            "ipr_realism": float(np.sqrt(real2.cpu().numpy().astype(np.float64)).mean())}
+
+
+def precision_recall(real, fake, k: int = 3) -> Tuple[float, float]:
+    """(improved_precision, improved_recall): the share of fake rows inside some real row's k-NN ball, and of real rows inside
+    some fake row's (the reference's sample_ncsn.py:148; higher is better)."""
+    ref = _ref(real, _device(real, fake))
+    cov, _, y = _against_real_balls(ref, fake, int(k))
+    return float(cov.double().mean()), _recall(ref, y, cov, int(k))
+
+
+def realism_scores(real, fake, k: int = 3) -> np.ndarray:
+    """Per fake row (float64): max over the real rows of at most the median radius of r_k(x_j) / |q - x_j| (the reference's
+    sample_ncsn.py:153 logs the mean as ipr_realism; higher is better)."""
+    ref = _ref(real, _device(real, fake))
+    return np.sqrt(_against_real_balls(ref, fake, int(k))[1].cpu().numpy().astype(np.float64))
