@@ -464,6 +464,29 @@ int smd_ball_cover(const float* q, int64_t ldq, int nq, const float* x, int64_t 
                    const uint8_t* keep, int exclude_diagonal, void* workspace, int64_t workspace_bytes, uint8_t* covered,
                    float* realism2, void* stream);
 
+/* ---- k-means over latent frames (the primitive of the PRD precision / recall histogram, Sajjadi et al. 2018, and of the NDB
+ * score, Richardson & Weiss 2018; the reference's sample_ncsn.py:141-146,160 logs them, DESIGN.md section 15 defines them) ----
+ * smd_kmeans_assign: ONE Gram pass of X (n x d, row stride ld) against centres (k x d, contiguous), 1 <= k <= SMD_KMEANS_MAX_K:
+ *   labels[i]  = arg min_j s_ij,  s_ij = -2 <x_i, c_j> + |c_j|^2 (dot product on the MFMA in k order, |c_j|^2 one fmaf chain),
+ *                ties to the lowest j (int32); |x_i|^2 takes no part in the order
+ *   min_d2[i]  = max(s_i,label + |x_i|^2, 0) (fp32; may be NULL).  A row whose bits are a centre's gives exactly 0.
+ *   *inertia   = sum_i min_d2[i] as fp64 (device pointer), per-workgroup fp64 partials added in a fixed order
+ *   *changed   = prev != 0: how many labels differ from what the labels buffer held before the call; prev == 0: n (int64, device)
+ *   No atomics: two calls give the same bits.  Any n, d >= 1.  workspace: >= smd_kmeans_assign_workspace_bytes(n, k) bytes,
+ *   8-byte aligned; x, centres, labels, min_d2 4-byte and inertia, changed 8-byte aligned. */
+#define SMD_KMEANS_MAX_K 128
+int64_t smd_kmeans_assign_workspace_bytes(int n, int k);
+int smd_kmeans_assign(const float* x, int64_t ld, int n, int d, const float* centres, int k, int prev, void* workspace,
+                      int64_t workspace_bytes, int32_t* labels, float* min_d2, double* inertia, int64_t* changed, void* stream);
+/* smd_kmeans_update: counts[j] (int64) = the rows of X with labels[i] == j, centres[j] (k x d fp32, contiguous) = their mean,
+ *   or prev_centres[j] bit for bit when there are none (centres may alias prev_centres).  Sums in fp64: 256-row slab partials
+ *   in the workspace, each a row-ordered sum, added in an order fixed by (n, d, k), then one division and one rounding to fp32; no atomics, two
+ *   calls give the same bits.  A label outside [0, k) is counted nowhere.  workspace: >=
+ *   smd_kmeans_update_workspace_bytes(n, d, k) bytes, 8-byte aligned; counts 8-byte, the other pointers 4-byte aligned. */
+int64_t smd_kmeans_update_workspace_bytes(int n, int d, int k);
+int smd_kmeans_update(const float* x, int64_t ld, int n, int d, const int32_t* labels, const float* prev_centres, int k,
+                      void* workspace, int64_t workspace_bytes, float* centres, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

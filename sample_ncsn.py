@@ -130,7 +130,11 @@ METRICS_KMEANS = ("precision", "recall", "f1", "ndb")                           
 METRICS_NOT_UPSTREAM = METRICS_KMEANS[:3] + NN_METRICS + METRICS_KMEANS[3:]
 
 
-def evaluate(writer, real, collection, baseline, valid_real, compute_final_only=False, seed=1, nn_metrics=False, nn_k=3):
+CLUSTER_METRICS = METRICS_KMEANS                                                         # --cluster_metrics computes these
+
+
+def evaluate(writer, real, collection, baseline, valid_real, compute_final_only=False, seed=1, nn_metrics=False, nn_k=3,
+             cluster_metrics=False, prd_clusters=20, prd_runs=10, ndb_bins=50):
     """sample_ncsn.py:69-186: the distance metrics of utils/metrics.py between the eval set ``real`` and 20 points of the
     sampler's ``collection`` (T, N, *shape), the ``baseline`` (None: skipped), and two controls: ``random`` (standard normals
     of the sample shape, drawn from a generator seeded by ``seed`` -- unseeded upstream) and ``real`` (``valid_real`` against
@@ -141,7 +145,10 @@ def evaluate(writer, real, collection, baseline, valid_real, compute_final_only=
     iteration left, the real-vs-real control).  The precision/recall, realism and NDB metrics of the reference's evaluate()
     are not defined in its utils/metrics.py.  ``nn_metrics``: additionally {model}/{improved_precision,improved_recall,
     improved_f1,ipr_realism} as DESIGN.md section 14 defines them (radius = distance to the ``nn_k``-th neighbour), for the same
-    points and steps, and the same four keys in the returned stats; the k-means metrics (PRD histogram, NDB) are not computed."""
+    points and steps, and the same four keys in the returned stats.  ``cluster_metrics``: additionally {model}/{precision,
+    recall,f1,ndb}, the reference's tags (:144-146,160), as DESIGN.md section 15 defines them -- the PRD histogram on
+    ``prd_clusters`` clusters averaged over ``prd_runs`` k-means runs and NDB on ``ndb_bins`` bins, all seeded by ``seed`` -- and
+    the same four keys in the returned stats.  Without it the k-means metrics are not computed."""
     from smd_amd import metrics as M
     assert tuple(collection.shape[1:]) == tuple(real.shape), (collection.shape, real.shape)
     lo, hi = float(collection[-1].min()), float(collection[-1].max())
@@ -176,8 +183,33 @@ def evaluate(writer, real, collection, baseline, valid_real, compute_final_only=
                     writer.scalar(f"{model}/{name}", nn[name], step=i)
                 if model == "ncsn":
                     stats.update(nn)
+            if cluster_metrics:
+                km = M.cluster_metrics(ref, samples, prd_clusters, prd_runs, ndb_bins, seed)
+                for name in CLUSTER_METRICS:
+                    writer.scalar(f"{model}/{name}", km[name], step=i)
+                if model == "ncsn":
+                    stats.update(km)
     writer.flush()
     return stats
+
+
+def check_cluster_flags(FLAGS):
+    """the refusals of --cluster_metrics, before the GPU is touched"""
+    if FLAGS.interpolate:
+        raise SystemExit("--cluster_metrics does not apply to --interpolate: there is no collection of the sample shape to compare "
+                         "with the eval set")
+    if not FLAGS.compute_metrics:
+        raise SystemExit("--cluster_metrics adds the k-means metrics to the evaluation: it needs --compute_metrics")
+    for name, lo, hi in (("prd_clusters", 2, 128), ("prd_runs", 1, 100), ("ndb_bins", 2, 128)):
+        v = getattr(FLAGS, name)
+        if v is None or not lo <= v <= hi:
+            raise SystemExit(f"--{name}={v}: --cluster_metrics takes {name} from {lo} to {hi}")
+    shape = [int(v) for v in FLAGS.data_shape]
+    frames = (FLAGS.sample_size or 0) * (int(np.prod(shape[:-1])) if len(shape) > 1 else 1)
+    k = max(FLAGS.prd_clusters, FLAGS.ndb_bins)
+    if frames < k:
+        raise SystemExit(f"--cluster_metrics: --sample_size={FLAGS.sample_size} examples of shape {tuple(shape)} are {frames} frames, "
+                         f"fewer than the {k} clusters of --prd_clusters={FLAGS.prd_clusters} / --ndb_bins={FLAGS.ndb_bins}")
 
 
 def main(argv):
@@ -203,6 +235,8 @@ def main(argv):
         raise SystemExit("--nn_metrics adds the nearest-neighbour metrics to the evaluation: it needs --compute_metrics")
     if FLAGS.nn_metrics and not 1 <= FLAGS.nn_k <= 8:
         raise SystemExit(f"--nn_k={FLAGS.nn_k}: the radius is the distance to the k-th neighbour for k from 1 to 8")
+    if FLAGS.cluster_metrics:
+        check_cluster_flags(FLAGS)
     torch.cuda.set_device(local_rank)
     dev = f"cuda:{local_rank}"
     if world > 1:
@@ -277,7 +311,14 @@ def main(argv):
         from smd_amd import train_utils
         log_dir = FLAGS.sampling_dir
         log_langevin_dynamics(ld_metrics, 0, log_dir)
-        if FLAGS.nn_metrics:
+        if FLAGS.cluster_metrics and not FLAGS.nn_metrics:
+            log.warning("--compute_metrics: %s of the reference's evaluate() call functions that utils/metrics.py does not define "
+                        "and are not computed (--nn_metrics); %s are computed as DESIGN.md section 15 defines them (%d clusters x %d "
+                        "runs, %d bins)", ", ".join(NN_METRICS), ", ".join(CLUSTER_METRICS), FLAGS.prd_clusters, FLAGS.prd_runs,
+                        FLAGS.ndb_bins)
+        elif FLAGS.cluster_metrics:
+            pass                                                            # every scalar of the reference's evaluate() is computed
+        elif FLAGS.nn_metrics:
             log.warning("--compute_metrics: %s of the reference's evaluate() call functions that utils/metrics.py does not define "
                         "and are not computed; %s are computed as DESIGN.md section 14 defines them (k = %d)",
                         ", ".join(METRICS_KMEANS), ", ".join(NN_METRICS), FLAGS.nn_k)
@@ -287,7 +328,8 @@ def main(argv):
         writer = train_utils.JsonlWriter(log_dir)
         stats = evaluate(writer, real, collection if coll_dev is None else coll_dev, None, real,
                          compute_final_only=FLAGS.compute_final_only, seed=FLAGS.sample_seed, nn_metrics=FLAGS.nn_metrics,
-                         nn_k=FLAGS.nn_k)
+                         nn_k=FLAGS.nn_k, cluster_metrics=FLAGS.cluster_metrics, prd_clusters=FLAGS.prd_clusters,
+                         prd_runs=FLAGS.prd_runs, ndb_bins=FLAGS.ndb_bins)
         writer.close()
         train_utils.log_metrics(stats, 1, 1)
     if world > 1:

@@ -251,6 +251,11 @@ ENGINE_FLAGS: List[FlagDef] = [
     _D("nn_metrics", "bool", False, "sample_ncsn --compute_metrics: also compute the nearest-neighbour metrics improved_precision, "
        "improved_recall, improved_f1 and ipr_realism (Kynkaanniemi et al. 2019, DESIGN.md section 14)."),
     _D("nn_k", "int", 3, "--nn_metrics: the neighbour whose distance is a row's radius (1..8)."),
+    _D("cluster_metrics", "bool", False, "sample_ncsn --compute_metrics: also compute the k-means metrics precision, recall, f1 (the "
+       "PRD histogram of Sajjadi et al. 2018) and ndb (Richardson & Weiss 2018), DESIGN.md section 15."),
+    _D("prd_clusters", "int", 20, "--cluster_metrics: clusters of the PRD histogram (2..128)."),
+    _D("prd_runs", "int", 10, "--cluster_metrics: k-means runs the PRD curve is averaged over (1..100)."),
+    _D("ndb_bins", "int", 50, "--cluster_metrics: bins of the NDB score (2..128)."),
     _D("graph", "bool", True, "Capture the sampling step in a hipGraph."),
     _D("ckpt_format", "enum", "safetensors", "Checkpoint file format written by train_ncsn: safetensors, or the "
        "reference's flax-0.3.0 msgpack state dict (both are recognised when restoring).", ("safetensors", "flax")),

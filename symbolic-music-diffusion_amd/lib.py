@@ -167,6 +167,11 @@ _SIGS = {
     "smd_ball_cover_workspace_bytes": (c_i64, [C.c_int, C.c_int]),
     "smd_ball_cover": (C.c_int, [c_void, c_i64, C.c_int, c_void, c_i64, C.c_int, C.c_int, c_void, c_void, C.c_int, c_void, c_i64,
                                  c_void, c_void, c_void]),
+    "smd_kmeans_assign_workspace_bytes": (c_i64, [C.c_int, C.c_int]),
+    "smd_kmeans_assign": (C.c_int, [c_void, c_i64, C.c_int, C.c_int, c_void, C.c_int, C.c_int, c_void, c_i64, c_void, c_void, c_void,
+                                    c_void, c_void]),
+    "smd_kmeans_update_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int]),
+    "smd_kmeans_update": (C.c_int, [c_void, c_i64, C.c_int, C.c_int, c_void, c_void, C.c_int, c_void, c_i64, c_void, c_void, c_void]),
     "smd_gemm_f32": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, C.c_int,
                                C.c_int, c_void, C.c_int, c_void]),
     "smd_layernorm_f32": (C.c_int, [c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void, C.c_int, C.c_int, c_void, C.c_int,

@@ -14,10 +14,15 @@ Only the eigenvalues that a covariance of n <= d rows has to be zero (beyond ran
 ``precision_recall``, ``realism_scores`` and ``f1_score`` are the nearest-neighbour metrics the reference's evaluate() logs as
 improved_precision / improved_recall / improved_f1 / ipr_realism (sample_ncsn.py:148-157) and its utils/metrics.py does not
 define: Kynkaanniemi et al. 2019 as fixed in DESIGN.md section 14, on csrc/nn_metrics.hip (``knn_radii``, ``ball_cover``).
+
+``precision_recall_distribution``, ``prd_f_beta_score`` and ``ndb_score`` are the remaining four scalars of that evaluate()
+(precision / recall / f1 from the PRD histogram of Sajjadi et al. 2018, sample_ncsn.py:141-146; ndb of Richardson & Weiss 2018,
+:160) as fixed in DESIGN.md section 15, on the full-batch Lloyd ``kmeans`` of csrc/kmeans.hip (``kmeans_assign``,
+``kmeans_update``); the histograms, the PRD curve and the two-proportion test are host float64.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -144,6 +149,138 @@ def median_keep_mask(r2: torch.Tensor) -> torch.Tensor:
     return torch.from_numpy((r <= np.median(r)).astype(np.uint8)).to(r2.device)
 
 
+KMEANS_MAX_K = 128        # SMD_KMEANS_MAX_K of include/smd_hip.h: the centres are one tile of the Gram pass
+
+
+def _check_k(name: str, k) -> int:
+    if int(k) != k or not 1 <= int(k) <= KMEANS_MAX_K:
+        raise ValueError(f"{name}: k={k!r} must be an integer in [1, {KMEANS_MAX_K}]")
+    return int(k)
+
+
+def _check_centres(name: str, x: torch.Tensor, centres: torch.Tensor) -> torch.Tensor:
+    _check_rows(name, x, centres)
+    _check_k(name, centres.shape[0])
+    if centres.shape[1] != x.shape[1]:
+        raise ValueError(f"{name}: d mismatch ({x.shape[1]} vs {centres.shape[1]})")
+    return centres.contiguous()
+
+
+def _kmeans_assign(x: torch.Tensor, centres: torch.Tensor, prev_labels: Optional[torch.Tensor]):
+    """kmeans_assign with (inertia, changed) as they are written: int64[2] on the device, [inertia's fp64 bits, changed]"""
+    L = _lib.get_lib()
+    centres = _check_centres("kmeans_assign", x, centres)
+    x = _rows(x)
+    n, d = x.shape
+    k = centres.shape[0]
+    if prev_labels is not None and (prev_labels.shape != (n,) or prev_labels.dtype != torch.int32 or prev_labels.device != x.device
+                                    or not prev_labels.is_contiguous()):
+        raise ValueError(f"kmeans_assign: prev_labels must be a contiguous int32 tensor of {n} labels on the rows' device")
+    labels = torch.empty(n, dtype=torch.int32, device=x.device) if prev_labels is None else prev_labels
+    ws_bytes = L.smd_kmeans_assign_workspace_bytes(n, k)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=x.device)
+    min_d2 = torch.empty(n, dtype=torch.float32, device=x.device)
+    out = torch.empty(2, dtype=torch.int64, device=x.device)          # [inertia as fp64 bits, changed]
+    _lib.check(L.smd_kmeans_assign(x.data_ptr(), x.stride(0), n, d, centres.data_ptr(), k, int(prev_labels is not None), ws.data_ptr(),
+                                   ws_bytes, labels.data_ptr(), min_d2.data_ptr(), out.data_ptr(), out.data_ptr() + 8,
+                                   _stream(x.device)), "smd_kmeans_assign")
+    return labels, min_d2, out
+
+
+def kmeans_assign(x: torch.Tensor, centres: torch.Tensor, prev_labels: Optional[torch.Tensor] = None):
+    """One Gram pass of the fp32 (n, d) cuda rows ``x`` against the (k, d) ``centres``, k <= 128: (labels int32[n]: arg min_j
+    -2 <x_i, c_j> + |c_j|^2, ties to the lowest j;  min_d2 fp32[n]: the squared distance to that centre;  inertia: their fp64
+    sum;  changed int64: how many labels differ from ``prev_labels``, or n without them), the last two 0-dim device tensors that
+    share one 16-byte buffer.  ``prev_labels`` (int32[n], contiguous) is OVERWRITTEN and returned as ``labels``.  Enqueued on the
+    current stream, nothing waits; two calls give the same bits."""
+    labels, min_d2, out = _kmeans_assign(x, centres, prev_labels)
+    return labels, min_d2, out[:1].view(torch.float64)[0], out[1]
+
+
+def kmeans_update(x: torch.Tensor, labels: torch.Tensor, centres: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(new centres fp32 (k, d), counts int64[k]): the mean of the rows of ``x`` with each label, summed in fp64 in a fixed order;
+    a cluster without rows keeps its row of ``centres`` bit for bit.  Enqueued on the current stream, nothing waits; two calls
+    give the same bits."""
+    L = _lib.get_lib()
+    centres = _check_centres("kmeans_update", x, centres)
+    x = _rows(x)
+    n, d = x.shape
+    k = centres.shape[0]
+    if labels.shape != (n,) or labels.dtype != torch.int32 or labels.device != x.device:
+        raise ValueError(f"kmeans_update: labels must be an int32 tensor of {n} labels on the rows' device")
+    labels = labels.contiguous()
+    ws_bytes = L.smd_kmeans_update_workspace_bytes(n, d, k)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=x.device)
+    new = torch.empty_like(centres)
+    counts = torch.empty(k, dtype=torch.int64, device=x.device)
+    _lib.check(L.smd_kmeans_update(x.data_ptr(), x.stride(0), n, d, labels.data_ptr(), centres.data_ptr(), k, ws.data_ptr(), ws_bytes,
+                                   new.data_ptr(), counts.data_ptr(), _stream(x.device)), "smd_kmeans_update")
+    return new, counts
+
+
+def _seed_words(seed, init: int) -> List[int]:
+    return [int(v) for v in np.atleast_1d(seed).ravel()] + [int(init)]
+
+
+def kmeans_seeds(x: torch.Tensor, k: int, u: np.ndarray) -> torch.Tensor:
+    """k-means++ row indices (int64[k], device) from the uniforms ``u`` (k of them in [0, 1)): the first is row floor(u_0 n);
+    centre j is the row at the inverse CDF of the float64 cumulative D^2 at u_j * total, D^2 the running minimum of min_d2 from
+    a k = 1 assign against the newest centre (a chosen row has D^2 = 0 exactly and is never drawn again); a total of 0 (fewer
+    distinct rows than k) takes the lowest-index row not yet chosen.  Nothing waits."""
+    n = x.shape[0]
+    idx = torch.empty(k, dtype=torch.int64, device=x.device)
+    idx[0] = min(int(u[0] * n), n - 1)
+    chosen = torch.zeros(n, dtype=torch.bool, device=x.device)
+    d2 = None
+    for j in range(1, k):
+        chosen.index_fill_(0, idx[j - 1:j], True)
+        m = _kmeans_assign(x, x.index_select(0, idx[j - 1:j]), None)[1]
+        d2 = m if d2 is None else torch.minimum(d2, m)
+        cum = torch.cumsum(d2.double(), 0)
+        drawn = torch.searchsorted(cum, (cum[-1] * float(u[j])).reshape(1), right=True).clamp_(max=n - 1)[0]
+        free = torch.searchsorted(torch.cumsum((~chosen).to(torch.int64), 0), torch.ones(1, dtype=torch.int64, device=x.device))[0]
+        idx[j] = torch.where(cum[-1] > 0, drawn, free)
+    return idx
+
+
+def kmeans(x: torch.Tensor, k: int, seed=0, n_init: int = 1, max_iter: int = 100, trace: Optional[list] = None):
+    """Full-batch Lloyd k-means of the fp32 (n, d) cuda rows ``x``: (centres fp32 (k, d), labels int32[n], inertia float, n_iter).
+    Run ``init`` of ``n_init`` seeds with k-means++ (``kmeans_seeds``) from numpy.random.default_rng([*seed, init]).random(k), then
+    alternates ``kmeans_assign`` and ``kmeans_update`` until an assignment changes no label (n_iter = the updates done) or
+    ``max_iter`` updates, after which one more assignment makes the labels those of the returned centres.  The run of the lowest
+    inertia wins, ties to the lowest ``init``.  An empty cluster keeps its centre.  The host waits for one scalar pair per
+    iteration.  ``trace`` (a list): receives one dict per assignment -- init, centres, labels (a copy), inertia, changed -- and
+    the seeds of every run as {"init", "seeds"}; for the tests."""
+    _check_rows("kmeans", x)
+    k = _check_k("kmeans", k)
+    n = x.shape[0]
+    if n < k:
+        raise ValueError(f"kmeans: n={n} rows cannot seed k={k} clusters")
+    if n_init < 1 or max_iter < 1:
+        raise ValueError(f"kmeans: n_init={n_init} and max_iter={max_iter} must be >= 1")
+    x = _rows(x)
+    best = None
+    for init in range(int(n_init)):
+        seeds = kmeans_seeds(x, k, np.random.default_rng(_seed_words(seed, init)).random(k))
+        if trace is not None:
+            trace.append({"init": init, "seeds": seeds.cpu().numpy()})
+        centres = x[seeds].contiguous()
+        labels, n_iter = None, 0
+        while True:
+            labels, _, out = _kmeans_assign(x, centres, labels)
+            out = out.cpu()                                     # the one wait of an iteration
+            inertia, changed = float(out[:1].view(torch.float64)[0]), int(out[1])
+            if trace is not None:
+                trace.append({"init": init, "centres": centres, "labels": labels.clone(), "inertia": inertia, "changed": changed})
+            if changed == 0 or n_iter == max_iter:
+                break
+            centres = kmeans_update(x, labels, centres)[0]
+            n_iter += 1
+        if best is None or inertia < best[2]:
+            best = (centres, labels, inertia, n_iter)
+    return best
+
+
 def moments(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """np.mean(x, axis=0), np.cov(x, rowvar=False) (ddof = 1) of an fp32 (n, d) cuda tensor as fp64 device tensors."""
     L = _lib.get_lib()
@@ -213,6 +350,7 @@ class ReferenceSet:
         self._sqrt = None
         self._kxx: Dict[tuple, np.ndarray] = {}
         self._radii: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._bins: Dict[tuple, Tuple[torch.Tensor, np.ndarray]] = {}
 
     def moments(self) -> Tuple[np.ndarray, np.ndarray]:
         if self._moments is None:
@@ -239,6 +377,14 @@ class ReferenceSet:
             r2 = knn_radii(self.frames, k)
             self._radii[k] = (r2, median_keep_mask(r2))
         return self._radii[k]
+
+    def ndb_bins(self, k: int, seed=0) -> Tuple[torch.Tensor, np.ndarray]:
+        """(centres, p_r): the NDB bins of the frames -- kmeans(frames, k, seed, n_init=3) -- and the share of the frames in each"""
+        key = (int(k), tuple(_seed_words(seed, 0)[:-1]))
+        if key not in self._bins:
+            centres, labels, _, _ = kmeans(self.frames, k, seed, n_init=3)
+            self._bins[key] = (centres, label_histogram(labels, k))
+        return self._bins[key]
 
     def is_same(self, other) -> bool:
         return other is self or other is self.source
@@ -346,3 +492,91 @@ def realism_scores(real, fake, k: int = 3) -> np.ndarray:
     sample_ncsn.py:153 logs the mean as ipr_realism; higher is better)."""
     ref = _ref(real, _device(real, fake))
     return np.sqrt(_against_real_balls(ref, fake, int(k))[1].cpu().numpy().astype(np.float64))
+
+
+def label_histogram(labels: torch.Tensor, k: int) -> np.ndarray:
+    """float64[k]: the share of the labels in each of k bins"""
+    return np.bincount(labels.cpu().numpy(), minlength=k).astype(np.float64) / labels.numel()
+
+
+def prd_curve(ref_hist, eval_hist, num_angles: int = 1001, epsilon: float = 1e-10) -> Tuple[np.ndarray, np.ndarray]:
+    """Sajjadi et al. 2018, algorithm 1, in float64: for slopes = tan(linspace(epsilon, pi/2 - epsilon, num_angles)),
+    precision = sum_b min(ref_b slope, eval_b) and recall = precision / slope, both clipped to [0, 1]."""
+    if not 0 < epsilon < 0.1 or not 3 <= num_angles <= 1e6:
+        raise ValueError(f"prd_curve: epsilon={epsilon} must be in (0, 0.1) and num_angles={num_angles} in [3, 1e6]")
+    ref, ev = np.asarray(ref_hist, np.float64), np.asarray(eval_hist, np.float64)
+    slopes = np.tan(np.linspace(epsilon, np.pi / 2 - epsilon, num=num_angles))
+    precision = np.minimum(ref[None, :] * slopes[:, None], ev[None, :]).sum(axis=1)
+    recall = precision / slopes
+    return np.clip(precision, 0.0, 1.0), np.clip(recall, 0.0, 1.0)
+
+
+def precision_recall_distribution(real, samples, num_clusters: int = 20, num_angles: int = 1001, num_runs: int = 10,
+                                  seed=0) -> Tuple[np.ndarray, np.ndarray]:
+    """The PRD curve (precision[num_angles], recall[num_angles]) of ``samples`` with respect to ``real`` (which may be a
+    ReferenceSet): the mean over ``num_runs`` runs of ``prd_curve`` on the two label histograms of
+    kmeans(real frames followed by sample frames, num_clusters, seed=[seed, run])."""
+    ref = _ref(real, _device(real, samples))
+    x = ref.frames
+    y = x if ref.is_same(samples) else as_frames(samples, x.device)
+    if y.shape[1] != x.shape[1]:
+        raise ValueError(f"precision_recall_distribution: d mismatch ({x.shape[1]} vs {y.shape[1]})")
+    k = _check_k("precision_recall_distribution", num_clusters)
+    if num_runs < 1:
+        raise ValueError(f"precision_recall_distribution: num_runs={num_runs} must be >= 1")
+    union = torch.cat((x, y))
+    precision, recall = np.zeros(num_angles), np.zeros(num_angles)
+    for run in range(int(num_runs)):
+        labels = kmeans(union, k, _seed_words(seed, run))[1]
+        p, r = prd_curve(label_histogram(labels[:x.shape[0]], k), label_histogram(labels[x.shape[0]:], k), num_angles)
+        precision += p
+        recall += r
+    return precision / num_runs, recall / num_runs
+
+
+def prd_f_beta_score(prd, beta: float = 8, epsilon: float = 1e-10) -> Tuple[float, float]:
+    """(max F_beta, max F_1/beta) over the curve ``prd`` = (precision, recall), F_b = (1 + b^2) p r / (b^2 p + r + epsilon).  The
+    reference unpacks the pair as (recall, precision) (sample_ncsn.py:142): F_8 weighs recall, F_1/8 precision."""
+    if not beta > 0:
+        raise ValueError(f"prd_f_beta_score: beta={beta} must be positive")
+    p, r = (np.asarray(v, np.float64) for v in prd)
+    f = lambda b: float(((1 + b * b) * p * r / (b * b * p + r + epsilon)).max())
+    return f(float(beta)), f(1.0 / float(beta))
+
+
+Z_TWO_SIDED_05 = 1.959963984540054       # the standard normal's 0.975 quantile
+
+
+def ndb_from_proportions(p_r, p_s, n_r: int, n_s: int, z_threshold: float = Z_TWO_SIDED_05) -> float:
+    """Richardson & Weiss 2018 in float64: the share of the bins whose proportions differ by the pooled two-proportion z-test,
+    P = (n_r p_r + n_s p_s) / (n_r + n_s), SE = sqrt(P (1 - P) (1 / n_r + 1 / n_s)), different when SE > 0 and
+    |p_r - p_s| / SE > z_threshold."""
+    p_r, p_s = np.asarray(p_r, np.float64), np.asarray(p_s, np.float64)
+    pooled = (n_r * p_r + n_s * p_s) / (n_r + n_s)
+    se = np.sqrt(pooled * (1.0 - pooled) * (1.0 / n_r + 1.0 / n_s))
+    z = np.abs(p_r - p_s) / np.where(se > 0, se, 1.0)
+    return float(((se > 0) & (z > z_threshold)).sum()) / len(p_r)
+
+
+def ndb_score(real, samples, k: int = 50, seed=0) -> float:
+    """The number of statistically different bins over k (lower is better; no whitening, the paper's default): the bins are
+    kmeans(real frames, k, seed, n_init=3) -- cached on a ReferenceSet -- p_r the share of the real frames in each and p_s that
+    of the sample frames from one ``kmeans_assign``.  Frames of one sequence are not independent draws: a score, not a test."""
+    ref = _ref(real, _device(real, samples))
+    k = _check_k("ndb_score", k)
+    centres, p_r = ref.ndb_bins(k, seed)
+    y = ref.frames if ref.is_same(samples) else as_frames(samples, ref.frames.device)
+    if y.shape[1] != centres.shape[1]:
+        raise ValueError(f"ndb_score: d mismatch ({centres.shape[1]} vs {y.shape[1]})")
+    p_s = label_histogram(kmeans_assign(y, centres)[0], k)
+    return ndb_from_proportions(p_r, p_s, ref.frames.shape[0], y.shape[0])
+
+
+def cluster_metrics(real, samples, prd_clusters: int = 20, prd_runs: int = 10, ndb_bins: int = 50, seed=0) -> Dict[str, float]:
+    """precision, recall, f1 and ndb of one comparison as the reference's evaluate() names them (sample_ncsn.py:141-146,160;
+    DESIGN.md section 15).  ``real`` may be a ReferenceSet, whose NDB bins are then computed once for all calls."""
+    ref = _ref(real, _device(real, samples))
+    prd = precision_recall_distribution(ref, samples, num_clusters=prd_clusters, num_runs=prd_runs, seed=seed)
+    recall, precision = prd_f_beta_score(prd, beta=8)
+    return {"precision": precision, "recall": recall, "f1": f1_score(precision, recall),
+            "ndb": ndb_score(ref, samples, k=ndb_bins, seed=seed)}
