@@ -111,7 +111,10 @@ int smd_engine_bind_workspace(smd_engine* e, void* workspace, int64_t bytes, int
                               void* stream);
 /* coef [T][8] = (sqrt(1/ap), sqrt(1-ap)/sqrt(ap), mu1, mu2, sigma, ap, sqrt(ap), sqrt(1-ap)) per t
  * (utils/ebm_utils.py:332-358); sqrt_ap [T]; alphas_prod_ext [T+1] = [1, cumprod(1-beta)]
- * (utils/losses.py:277-281); film_tables: smd_engine_film_table_floats() floats or NULL */
+ * (utils/losses.py:277-281); film_tables: smd_engine_film_table_floats() floats or NULL.  smd_engine_prepare_sampler writes
+ * the first blocks * T * 2 * mlp_dims of them (one [T][2 * mlp_dims] scale | shift table per DenseResBlock, every element); the
+ * rest (T * 9 * film_channels bf16, fp32 with option "fp32", + 64 floats of slack) is scratch of the three generator GEMMs and
+ * holds no defined values afterwards */
 int smd_engine_bind_schedule(smd_engine* e, const float* coef, const float* sqrt_ap,
                              const float* alphas_prod_ext, float* film_tables);
 int smd_engine_refresh_weights(smd_engine* e, void* stream);   /* fp32 master -> bf16 operand pack */
@@ -250,7 +253,8 @@ int smd_set_timestep(int32_t* t_ptr, int32_t t, void* stream);
 /* ---- e4m3 (OCP fp8) path: BASELINE config 5.  Operands are e4m3 bytes with one power-of-two (E8M0) scale per row,
  * contracted by v_mfma_scale_f32_32x32x64_f8f6f4; engine option "fp8" = 1 (before bind_workspace) routes the
  * DenseResBlock forward GEMMs (models/shared.py:65,69) through it. ------------------------------------------------ */
-/* rows of a bf16 matrix [rows][ld] (K used) -> out8 [rows][K] e4m3(v * 2^-e), scale[rows] = E8M0 byte e + 127 */
+/* rows of a bf16 matrix [rows][ld] (K used) -> out8 [rows][K] e4m3(v * 2^-e), scale[rows] = E8M0 byte e + 127.  Any rows >= 1;
+ * K % 8 == 0, ld >= K and ld % 8 == 0 (16-byte loads); the columns K .. ld of a row are not read. */
 int smd_quantize_rows_e4m3(const smd_bf16* in, int ld, int rows, int K, uint8_t* out8, uint32_t* scale, void* stream);
 /* C[M,N] = (2^sa[m] A8[m,:]) . (2^sb[n] Bt8[n,:]) + bias (+ fp32 residual) -> fp32 and/or bf16; M, N, K % 256 == 0 */
 int smd_gemm_e4m3_nt(const uint8_t* A8, int lda, const uint32_t* scale_a, const uint8_t* Bt8, int ldb,
@@ -263,7 +267,9 @@ int smd_layernorm_fwd_e4m3(const float* x, int rows, int D, const float* gamma, 
 
 /* ---- single kernels (unit-testable ops) ------------------------------------------------------- */
 enum { SMD_EPI_NONE = 0, SMD_EPI_GELU = 1, SMD_EPI_SWISH = 2 };
-/* C[M,N] = act(A[M,K] Bt[N,K]^T + bias) (+ residual); nn.Dense, models/ncsn.py:155 etc. */
+/* C[M,N] = act(A[M,K] Bt[N,K]^T + bias) (+ residual); nn.Dense, models/ncsn.py:155 etc.  K % 64 == 0; lda, ldb >= K and
+ * multiples of 8 (16-byte rows; anything else returns < 0 unlaunched).  ld_res, ld_out, ld_outb >= N, any value: only the
+ * columns < N of a row are read / written, whatever lies between N and the leading dimension is left alone. */
 int smd_gemm_bf16_nt(const smd_bf16* A, int lda, const smd_bf16* Bt, int ldb, int M, int N, int K,
                      const float* bias, int act, const float* residual, int ld_res, float* out_f32, int ld_out,
                      smd_bf16* out_bf16, int ld_outb, void* stream);
@@ -341,7 +347,9 @@ int smd_layernorm_bwd(const float* x, int rows, int D, const float* gamma, const
                       int swish, const smd_bf16* dout, float* dx, float* dgamma, float* dbeta, float* dscale,
                       float* dshift, float* partial, int64_t partial_elems, void* stream);
 /* flax.nn.SelfAttention core, models/ncsn.py:161 */
-/* (every LayerNorm backward WRITES dgamma / dbeta -- the sum over its row groups -- it does not accumulate into them)
+/* (every LayerNorm backward WRITES dgamma / dbeta -- the sum over its row groups -- it does not accumulate into them;
+ * partial is scratch of partial_elems >= ngroups * 2 * D floats, ngroups = ceil(rows / g) with g = rows_per_sample when FiLM
+ * is given and 32 otherwise: less returns < 0 unlaunched)
  * the engine's form of the LayerNorm backward: optional fp32 residual gradient `dres` added to dx (may alias dx: the
  * in-place residual-gradient stream), optional bf16 copy of dx, bf16 or fp32 input */
 int smd_layernorm_bwd_ex(const float* x, const smd_bf16* x_bf16, int rows, int D, const float* gamma, const float* beta,
@@ -365,7 +373,7 @@ int smd_noise_embed(const float* noise_level, int n, int channels, smd_bf16* out
  *   [label_min, label_min + T) keyed by (seed, b + sample_offset, *step_ptr); used_alphas NULL -> alphas_prod_ext[label - 1]
  *   (label 0: a uniform draw in [alphas_prod_ext[T], 1)); eps_in NULL -> Philox normals.  S*C need not be a multiple of 4.
  * smd_mse_fwd_bwd: :304-305 and d(mean loss)/d pred: loss_per_sample [B], dpred_bf16 [B*S][Cp] = 2 (pred - eps) *
- *   inv_global_count.
+ *   inv_global_count (the columns >= C are not written, as in smd_q_sample: the caller zeroes them once).
  * smd_adam_clip_ema: train_ncsn.py:284-287,340-342,364-365 on flat fp32 buffers of n elements: gradient norm -> clip ->
  *   Adam with the stepped LR evaluated from *step_ptr (incremented by the kernel) -> EMA (ema may be NULL).
  *   norm_partial: >= 1024 floats of scratch; metrics_out [4] = norm before clip, after clip, lr, step. */
@@ -393,6 +401,8 @@ int smd_threefry_normal(float* out, int64_t n_total, int64_t offset, int64_t cou
                         const uint32_t* key_table, const int32_t* idx_ptr, int idx_mul, int idx_add, void* stream);
 int smd_threefry_randint(int32_t* out, int64_t n_total, int64_t offset, int64_t count, uint32_t k0, uint32_t k1,
                          int32_t minval, int32_t maxval, void* stream);
+/* in [rows][cols] fp32 -> out [rows][ld_out] bf16: the columns cols .. ld_out of every row are WRITTEN as +0 (the zero padding
+ * the GEMMs contract over); nothing behind row rows - 1 is touched */
 int smd_cast_pad_bf16(const float* in, int rows, int cols, smd_bf16* out, int ld_out, void* stream);
 /* one reverse step on explicit eps_hat (the elementwise part of utils/ebm_utils.py:327-394); coef is the [T][8]
  * table, *t_ptr outside [0, T) makes the call a no-op */

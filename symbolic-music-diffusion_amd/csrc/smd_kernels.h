@@ -44,7 +44,7 @@ int launch_gemm_nt256(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M
 // arrays, byte 0), v_mfma_scale_f32_32x32x64_f8f6f4: M, N % 256 == 0, K % 256 == 0, lda / ldb in elements (= bytes)
 int launch_gemm_nt256_fp8(const unsigned char* A8, int lda, const uint32_t* scale_a, const unsigned char* Bt8, int ldb,
                           const uint32_t* scale_b, int M, int N, int K, const GemmEpilogue& ep, hipStream_t st);
-// rows of a bf16 matrix -> e4m3 bytes + one E8M0 scale per row (weights of the e4m3 GEMM path): K % 512 == 0
+// rows of a bf16 matrix -> e4m3 bytes + one E8M0 scale per row (weights of the e4m3 GEMM path): any rows, K % 8 == 0, ld % 8 == 0
 int launch_quantize_rows_e4m3(const bf16_t* in, int ld, int rows, int K, unsigned char* out8, uint32_t* scale, hipStream_t st);
 // process-wide kernel-selection knobs (benchmark A/B; defaults are the fast paths). Keys: "gemm_nt256", "gemm_nt256_variant", "gemm_tn256".
 int smd_tuning_set(const char* key, int value);
