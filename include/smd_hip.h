@@ -206,6 +206,32 @@ int smd_engine_sample_step(smd_engine* e, const smd_sample_io* io, void* stream)
  * encoder kernels always sit beside the other's 2048-wide GEMMs (two free-running chains drift INTO phase: DESIGN.md section 5). */
 int smd_engine_sample_step_part(smd_engine* e, const smd_sample_io* io, int part, void* stream);
 
+/* One iteration of a STRIDED walk over the timesteps: the generalised non-Markovian sampler of Song et al. 2021 (DDIM; no
+ * counterpart in the reference) going down a sub-sequence of [0, T), or, going up with sigma = 0, its inversion (a deterministic
+ * encoder).  The eps-net is evaluated at t = *t_ptr as in smd_engine_sample_step; the fused update then reads everything that
+ * depends on the walk from two device tables indexed by t:
+ *   coef[t] = (sqrt(1/ap_t), sqrt(1-ap_t)/sqrt(ap_t), a, b, sigma, clip, sqrt(ap_s), sqrt(1-ap_s))   s = the next timestep
+ *   plan[t] = (next_t, iteration, slot, 0)
+ *   x0 = clamp(coef0 x - coef1 eps_hat, -clip, clip) (clip = inf: none);  x' = a x0 + b x + sigma z;
+ *   (x0 is rounded ONCE: the rounding error of coef1 * eps_hat is carried through the subtraction with two FMAs, so it is the
+ *   same formula as smd_engine_sample_step's but not its bits -- at low noise the two products cancel and b is ~0, and the plain
+ *   form's error would be the whole error of x')
+ *   with infill: x' = x' (1 - mask) + y mask,  y = sqrt(ap_s) samples + sqrt(1-ap_s) zi while next_t is in [0, T), else samples
+ * (the known region at the level of the state being produced).  z is read / drawn only where sigma != 0 -- z_in, else
+ * jax.random.normal of tf_noise_keys row `iteration`, else Philox keyed by t -- and zi likewise from infill_z_in /
+ * tf_infill_keys / Philox.  The new state also goes to the engine's bf16 network input, to collection row `slot` (0..40,
+ * anything else: not collected) and its norm partials to metrics_partial[t]; the launch's last workgroup stores next_t to
+ * *t_ptr.  t outside [0, T), or a row whose iteration is < 0 (a timestep that is not on the walk), makes the update a no-op
+ * that advances nothing, so a walk ends by itself at next_t = -1 (sampling) or T (inversion).  io->slot_table and io->tf_t0 are
+ * not used.  part: 0 the whole iteration, 1 / 2 as in smd_engine_sample_step_part (argument error under option "fp32").
+ * plan->T must be the engine's num_timesteps; the plan rows, and for data_channels % 4 == 0 every fp32 array, 16-byte aligned. */
+typedef struct smd_stride_plan {
+  const float* coef;               /* [T][8] */
+  const int32_t* plan;             /* [T][4] */
+  int32_t T;
+} smd_stride_plan;
+int smd_engine_strided_step(smd_engine* e, const smd_sample_io* io, const smd_stride_plan* plan, int part, void* stream);
+
 /* One Langevin update of annealed_langevin_dynamics / consistent_langevin_dynamics (utils/ebm_utils.py:131-164, 231-253):
  *   next = x + alpha * grad + noise_coef * z;  with infill: next = next (1 - mask) + (infill_samples + infill_sigma * zi) mask.
  * grad = model(state, sigma) comes from smd_engine_forward.  z / zi: explicit arrays, else jax.random.normal(step_rng) /

@@ -1,7 +1,8 @@
 """Drop-in for the reference's ``python sample_ncsn.py --flagfile=... --sample_seed --sample_size
 --sampling_dir`` on the MI355X HIP engine: unconditional generation, infilling (--infill) and
 interpolation (--interpolate) for DDPM checkpoints, writing {sampling_dir}/ncsn/{generated,
-collection,real}.pkl in the reference's layout (sample_ncsn.py:368-471).
+collection,real}.pkl in the reference's layout (sample_ncsn.py:368-471).  --ddim_steps=K walks K of the
+schedule's timesteps with the strided (DDIM) sampler instead of all of them, in all three modes.
 
 Multi-GPU sampling is embarrassingly parallel: under torch.distributed.run each rank generates a
 contiguous shard of the samples (Philox counters are keyed by the GLOBAL sample index, so the
@@ -56,7 +57,7 @@ def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sampl
     generated, collection, ld_metrics = ncsn.sample(
         model, sigmas, sample_rng, sample_shape, num_samples=num_samples, sampling=FLAGS.sampling,
         epsilon=FLAGS.ld_epsilon, steps=FLAGS.ld_steps, denoise=FLAGS.denoise, sample_offset=sample_offset,
-        use_graph=FLAGS.graph, global_num_samples=global_num_samples)
+        use_graph=FLAGS.graph, global_num_samples=global_num_samples, ddim_steps=FLAGS.ddim_steps, ddim_eta=FLAGS.ddim_eta)
     torch.cuda.synchronize()
     log.info("Generated samples in %f seconds", time.time() - t0)
     return generated, collection, ld_metrics
@@ -81,6 +82,11 @@ def infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=0, g
         return generated, collection, ncsn.collate_sampling_metrics(ld_metrics.cpu().numpy())
     if FLAGS.sampling == "cas":                                             # :222-223 -> NotImplementedError (:228-229)
         ncsn.consistent_langevin_dynamics(ld_rng, model, sigmas, init, FLAGS.ld_epsilon, FLAGS.ld_steps, FLAGS.denoise, True)
+    if FLAGS.ddim_steps:
+        generated, collection, ld_metrics = ncsn.strided_dynamics(
+            ld_rng, model, sigmas, init, FLAGS.ddim_steps, FLAGS.ddim_eta, True, infill_samples=samples, infill_masks=masks,
+            use_graph=FLAGS.graph, sample_offset=sample_offset, global_num_samples=global_num_samples)
+        return generated, collection, ncsn.collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = ncsn.diffusion_dynamics(
         ld_rng, model, sigmas, init, FLAGS.ld_epsilon, FLAGS.ld_steps, FLAGS.denoise, True,
         infill_samples=samples, infill_masks=masks, use_graph=FLAGS.graph, sample_offset=sample_offset,
@@ -105,20 +111,31 @@ def diffusion_stochastic_encoder(samples, sigmas, rng, device="cuda:0", sample_o
     return np.sqrt(a_T) * samples + np.sqrt(1 - a_T) * noise
 
 
-def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl, dev, use_graph=True, points=9):
+def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl, dev, use_graph=True, points=9, ddim_steps=0,
+                        ddim_eta=0.0, ddim_encode=False):
     """sample_ncsn.py:425-435 + diffusion_decoder (:269-310) for this rank's rows [lo, hi): goals = roll(starts, 1); both are
     encoded with the same key (the same noise); every one of the 9 interpolated latents is decoded with the SAME
-    ld_rng = split(PRNGKey(sample_seed), 3)[1].  Returns (generated (9, n, ...), collection (9, 41, n, ...), collated metrics)."""
+    ld_rng = split(PRNGKey(sample_seed), 3)[1].  Returns (generated (9, n, ...), collection (9, 41, n, ...), collated metrics).
+    ``ddim_steps`` > 0: the points are decoded with the strided sampler; with ``ddim_encode`` starts and goals are encoded by its
+    deterministic inversion (ncsn.ddim_encode) instead of the single re-noising."""
     from smd_amd import ncsn
     num = len(real)
     starts = real[lo:hi]
     goals = np.roll(real, shift=1, axis=0)[lo:hi]
-    zs, zg = (diffusion_stochastic_encoder(v, sigmas, rng, dev, lo, num) for v in (starts, goals))
+    if ddim_steps and ddim_encode:
+        zs, zg = (ncsn.ddim_encode(model, sigmas, np.ascontiguousarray(v, dtype=np.float32), ddim_steps, use_graph=use_graph).cpu().numpy()
+                  for v in (starts, goals))
+    else:
+        zs, zg = (diffusion_stochastic_encoder(v, sigmas, rng, dev, lo, num) for v in (starts, goals))
     _, ld_rng, _ = ncsn.split(ncsn.make_key(sample_seed, rng_impl), num=3)                 # :271-272 (the root key)
     gens, colls = [], []
     for i, alpha in enumerate(np.linspace(0.0, 1.0, points)):
-        g, c, ld = ncsn.diffusion_dynamics(ld_rng, model, sigmas, ((1 - alpha) * zs + alpha * zg).astype(np.float32),
-                                           use_graph=use_graph, sample_offset=lo, global_num_samples=num)
+        z = ((1 - alpha) * zs + alpha * zg).astype(np.float32)
+        if ddim_steps:
+            g, c, ld = ncsn.strided_dynamics(ld_rng, model, sigmas, z, ddim_steps, ddim_eta, use_graph=use_graph, sample_offset=lo,
+                                             global_num_samples=num)
+        else:
+            g, c, ld = ncsn.diffusion_dynamics(ld_rng, model, sigmas, z, use_graph=use_graph, sample_offset=lo, global_num_samples=num)
         gens.append(g.cpu().numpy())
         colls.append(c.cpu().numpy())
         log.info("Generated samples %i out of %i", i, points)
@@ -212,6 +229,22 @@ def check_cluster_flags(FLAGS):
                          f"fewer than the {k} clusters of --prd_clusters={FLAGS.prd_clusters} / --ndb_bins={FLAGS.ndb_bins}")
 
 
+def check_ddim_flags(FLAGS):
+    """the refusals of --ddim_steps / --ddim_eta / --ddim_encode, before the GPU is touched"""
+    used = [f"--{n}" for n in ("ddim_steps", "ddim_eta", "ddim_encode") if FLAGS.is_present(n) and getattr(FLAGS, n)]
+    if used and FLAGS.sampling != "ddpm":
+        raise SystemExit(f"{', '.join(used)}: the strided sampler walks a DDPM schedule, it needs --sampling=ddpm (got --sampling={FLAGS.sampling})")
+    steps = FLAGS.ddim_steps
+    if steps is None or not (steps == 0 or 2 <= steps <= FLAGS.num_sigmas):
+        raise SystemExit(f"--ddim_steps={steps}: 0 (every timestep) or from 2 to --num_sigmas={FLAGS.num_sigmas} timesteps")
+    if FLAGS.ddim_eta < 0:
+        raise SystemExit(f"--ddim_eta={FLAGS.ddim_eta}: the noise scale is >= 0")
+    if (FLAGS.ddim_eta or FLAGS.ddim_encode) and not steps:
+        raise SystemExit("--ddim_eta / --ddim_encode belong to the strided sampler: give --ddim_steps")
+    if FLAGS.ddim_encode and not FLAGS.interpolate:
+        raise SystemExit("--ddim_encode replaces the encoder of --interpolate: it needs --interpolate")
+
+
 def main(argv):
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     FLAGS = F.make_flags(include_sample=True)
@@ -237,6 +270,7 @@ def main(argv):
         raise SystemExit(f"--nn_k={FLAGS.nn_k}: the radius is the distance to the k-th neighbour for k from 1 to 8")
     if FLAGS.cluster_metrics:
         check_cluster_flags(FLAGS)
+    check_ddim_flags(FLAGS)
     torch.cuda.set_device(local_rank)
     dev = f"cuda:{local_rank}"
     if world > 1:
@@ -280,7 +314,8 @@ def main(argv):
                                                            global_num_samples=num)
     elif FLAGS.interpolate:                                                 # :425-435
         generated, collection, ld_metrics = interpolate_samples(model, sigmas, real, lo, hi, rng, FLAGS.sample_seed, FLAGS.rng_impl,
-                                                                dev, FLAGS.graph)
+                                                                dev, FLAGS.graph, ddim_steps=FLAGS.ddim_steps,
+                                                                ddim_eta=FLAGS.ddim_eta, ddim_encode=FLAGS.ddim_encode)
     else:                                                                   # :437-439
         generated, collection, ld_metrics = generate_samples(FLAGS, model, rng, shape, hi - lo, sigmas, sample_offset=lo,
                                                              global_num_samples=num)

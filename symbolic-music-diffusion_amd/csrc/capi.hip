@@ -197,9 +197,7 @@ int smd_engine_load_state(smd_engine* e, const float* x, void* stream) {
   NEED(e);
   return e->impl.load_state(x, S(stream));
 }
-static int sample_step_part(smd_engine* e, const smd_sample_io* io, int part, void* stream) {
-  NEED(e);
-  SMD_ARG_CHECK(io, "sample_step: null io");
+static SampleStepIO sample_io(const smd_sample_io* io) {
   SampleStepIO s;
   s.x = io->x; s.t_ptr = io->t_ptr; s.z_in = io->z_in; s.seed_lo = io->seed_lo; s.seed_hi = io->seed_hi;
   s.sample_offset = io->sample_offset; s.infill_samples = io->infill_samples; s.infill_masks = io->infill_masks;
@@ -207,12 +205,24 @@ static int sample_step_part(smd_engine* e, const smd_sample_io* io, int part, vo
   s.slot_table = io->slot_table;
   s.tf_noise_keys = io->tf_noise_keys; s.tf_infill_keys = io->tf_infill_keys; s.tf_n_total = io->tf_n_total; s.tf_t0 = io->tf_t0;
   s.key_ptr = io->key_ptr;
-  return e->impl.sample_step(s, S(stream), part);
+  return s;
+}
+static int sample_step_part(smd_engine* e, const smd_sample_io* io, int part, void* stream) {
+  NEED(e);
+  SMD_ARG_CHECK(io, "sample_step: null io");
+  return e->impl.sample_step(sample_io(io), S(stream), part);
 }
 int smd_engine_sample_step(smd_engine* e, const smd_sample_io* io, void* stream) { return sample_step_part(e, io, 0, stream); }
 int smd_engine_sample_step_part(smd_engine* e, const smd_sample_io* io, int part, void* stream) {
   SMD_ARG_CHECK(part == 1 || part == 2, "smd_engine_sample_step_part: part=%d (1 stem, 2 output stage + reverse update)", part);
   return sample_step_part(e, io, part, stream);
+}
+int smd_engine_strided_step(smd_engine* e, const smd_sample_io* io, const smd_stride_plan* plan, int part, void* stream) {
+  NEED(e);
+  SMD_ARG_CHECK(io && plan, "strided_step: null io / plan");
+  StridePlan p;
+  p.coef = plan->coef; p.plan = plan->plan; p.T = plan->T;
+  return e->impl.strided_step(sample_io(io), p, S(stream), part);
 }
 
 // ------------------------------------------------------------------ single kernels

@@ -64,6 +64,12 @@ struct SampleStepIO {
   const uint32_t* key_ptr = nullptr;         // device-resident Philox key (overrides seed_lo / seed_hi)
 };
 
+struct StridePlan {
+  const float* coef = nullptr;        // [T][8], see StridedStepArgs
+  const int32_t* plan = nullptr;      // [T][4]
+  int T = 0;
+};
+
 class SmdEngine {
  public:
   explicit SmdEngine(const SmdModelDesc& d);
@@ -126,6 +132,8 @@ class SmdEngine {
   int forward_train(const float* x, const float* noise_level, float* eps_out, hipStream_t st);   // model(x, cond), activations saved
   int backward_from(const float* dpred, int stage, hipStream_t st);                                 // backward of that pass from d/d eps_hat
   int sample_step(const SampleStepIO& io, hipStream_t st, int part = 0);   // eps-net forward + fused reverse step
+  // eps-net forward + fused strided (DDIM) step: the walk and its coefficients come from the plan (io.slot_table / tf_t0 unused)
+  int strided_step(const SampleStepIO& io, const StridePlan& plan, hipStream_t st, int part = 0);
   int init_state(float* x, uint32_t seed_lo, uint32_t seed_hi, uint32_t sample_offset, hipStream_t st);
   int load_state(const float* x, hipStream_t st);            // explicit state -> bf16 network input
   // device pointers of a few internals (tests / metrics)

@@ -286,6 +286,32 @@ struct ReverseStepArgs {
   const int* slot_table = nullptr;    // [T] slot for timestep t or -1
 };
 int launch_reverse_step(const ReverseStepArgs& a, hipStream_t st);
+
+// fused strided (DDIM) step: the walk (next timestep, iteration, collection slot) and its coefficients from tables
+struct StridedStepArgs {
+  float* x = nullptr;                 // [B][S][C] state, updated in place
+  const float* eps_hat = nullptr;     // [B][S][C]
+  int B = 0, S = 0, C = 0, Cp = 0, T = 0;
+  const float* coef = nullptr;        // [T][8]: sqrt_recip, sqrt_m1, a, b, sigma, clip, sqrt_as, sqrt_1m_as (s = the next timestep)
+  const int32_t* plan = nullptr;      // [T][4]: next_t, iteration, slot, 0; iteration < 0 = not on the walk (a no-op)
+  const int* t_ptr = nullptr;         // device timestep; t outside [0, T) makes the launch a no-op
+  int* t_advance = nullptr;           // non-null: the last workgroup stores plan[t].next_t here (normally == t_ptr)
+  unsigned* arrive = nullptr;         // arrival counter for t_advance: zero before the first launch, reset by the kernel
+  const float* z_in = nullptr;        // explicit N(0,1) draw or null -> threefry / Philox; read or drawn only when sigma != 0
+  RngKey key{0, 0};
+  const uint32_t* key_ptr = nullptr;  // device-resident Philox key [2] (overrides `key`)
+  uint32_t sample_offset = 0;
+  const float* infill_samples = nullptr;  // [B][S][C] or null
+  const float* infill_masks = nullptr;
+  const float* infill_z_in = nullptr;
+  const uint32_t* tf_noise_keys = nullptr;   // jax.random key tables [iterations][2], row plan[t].iteration
+  const uint32_t* tf_infill_keys = nullptr;
+  int64_t tf_n_total = 0;
+  bf16_t* x_bf16 = nullptr;           // [B*S][Cp] next network input (zero padded)
+  float* metrics_partial = nullptr;   // [T][B][3], row t
+  float* collection = nullptr;        // [41][B][S][C] or null, row plan[t].slot
+};
+int launch_strided_step(const StridedStepArgs& a, hipStream_t st);
 int launch_advance_t(int* t_ptr, hipStream_t st);   // *t_ptr -= 1
 int launch_set_t(int* t_ptr, int v, hipStream_t st);   // *t_ptr = v (restart of a walk on the sampler's own stream)
 

@@ -461,6 +461,14 @@ class Engine:
             else:
                 _lib.check(self.L.smd_engine_sample_step_part(self.h, C.byref(io), int(part), _stream()), "sample_step_part")
 
+    def strided_step(self, io: "_lib.SampleIO", plan: "_lib.StridePlan", part: int = 0) -> None:
+        """One iteration of a strided (DDIM) walk or of its inversion: the walk and its coefficients come from ``plan``
+        (include/smd_hip.h smd_engine_strided_step); ``part`` as in sample_step."""
+        self._sync_fp8_weights()
+        self._join_pending()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.smd_engine_strided_step(self.h, C.byref(io), C.byref(plan), int(part), _stream()), "strided_step")
+
     @property
     def slot_table(self) -> torch.Tensor:
         return self._sched_tensors["slot"]

@@ -257,6 +257,12 @@ ENGINE_FLAGS: List[FlagDef] = [
     _D("prd_runs", "int", 10, "--cluster_metrics: k-means runs the PRD curve is averaged over (1..100)."),
     _D("ndb_bins", "int", 50, "--cluster_metrics: bins of the NDB score (2..128)."),
     _D("graph", "bool", True, "Capture the sampling step in a hipGraph."),
+    _D("ddim_steps", "int", 0, "sample_ncsn --sampling=ddpm: walk this many evenly spaced timesteps of the schedule with the strided "
+       "(DDIM, Song et al. 2021) sampler instead of all --num_sigmas of them: 0 (off) or 2..num_sigmas network evaluations per "
+       "sample from the same checkpoint (DESIGN.md section 16)."),
+    _D("ddim_eta", "float", 0.0, "--ddim_steps: noise scale of the strided sampler, 0 = deterministic, 1 = the DDPM posterior's variance."),
+    _D("ddim_encode", "bool", False, "--interpolate with --ddim_steps: encode starts and goals with the deterministic inversion of the "
+       "strided sampler instead of the reference's single re-noising."),
     _D("ckpt_format", "enum", "safetensors", "Checkpoint file format written by train_ncsn: safetensors, or the "
        "reference's flax-0.3.0 msgpack state dict (both are recognised when restoring).", ("safetensors", "flax")),
     _D("rng_impl", "enum", "philox", "Random streams: the engine's fused Philox draws, or jax.random-compatible "

@@ -43,6 +43,10 @@ class SampleIO(C.Structure):
                 ("tf_t0", c_i32), ("key_ptr", c_void)]
 
 
+class StridePlan(C.Structure):
+    _fields_ = [("coef", c_void), ("plan", c_void), ("T", c_i32)]
+
+
 class LangevinIO(C.Structure):
     _fields_ = [("x", c_void), ("grad", c_void), ("alpha", C.c_float), ("noise_coef", C.c_float), ("z_in", c_void),
                 ("seed_lo", c_u32), ("seed_hi", c_u32), ("step", c_u32), ("sample_offset", c_u32), ("use_threefry", c_i32),
@@ -101,6 +105,7 @@ _SIGS = {
     "smd_engine_load_state": (C.c_int, [c_void, c_void, c_void]),
     "smd_engine_sample_step": (C.c_int, [c_void, C.POINTER(SampleIO), c_void]),
     "smd_engine_sample_step_part": (C.c_int, [c_void, C.POINTER(SampleIO), C.c_int, c_void]),
+    "smd_engine_strided_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(StridePlan), C.c_int, c_void]),
     "smd_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "smd_set_timestep": (C.c_int, [c_void, c_i32, c_void]),
     "smd_gemm_bf16_nt": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_int,

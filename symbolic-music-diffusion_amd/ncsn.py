@@ -5,6 +5,7 @@ Same names, argument meaning and error behaviour as the reference seam (SURVEY s
   create_model          train_ncsn.py:193-203        Model.__call__   models/ncsn.py:141-148
   diffusion_loss        utils/losses.py:250-308      reduce_fn        utils/losses.py:22-30
   diffusion_dynamics    utils/ebm_utils.py:280-405   collate_sampling_metrics  :408-428
+  strided_dynamics / ddim_encode: the strided (DDIM) sampler and its inversion, no reference counterpart
   sample                train_ncsn.py:499-551
 
 Every array computation runs in the HIP library (lib.py); this module only allocates tensors,
@@ -625,6 +626,81 @@ def _sampler_pipeline_unroll() -> int:
     return max(1, int(os.environ.get("SMD_SAMPLER_UNROLL", "8")))
 
 
+def _graph_walk(model: "Model", dev, chains: list, replays: int, unroll: int, reuse: bool, step: Callable) -> None:
+    """The graph-replayed part of a walk over ``chains`` (dicts with "eng" and whatever ``step`` reads): one iteration as plain
+    launches, then ``replays`` more from captured graphs -- one chain, two free-running chains (``unroll`` = 0) or the pipelined
+    pair, ``unroll`` iterations per graph and the remainder as plain launches.  ``step(ch, part)`` enqueues one iteration of a
+    chain (part 0) or one of its halves (1: stem, 2: output stage + update) on the current stream: the every-timestep sampler
+    and the strided one differ in nothing else.  ``reuse``: the chains already carry their graphs."""
+    cur = torch.cuda.current_stream(dev)
+
+    def capture(ch, body):
+        ch["stream"].synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=ch["stream"]):
+            body()
+        return g
+
+    # the first iteration as plain launches on the chain's stream: the warm-up of a capture, and whatever a handle does
+    # lazily in front of a forward pass (fp8 mode: e4m3 copies of refreshed weights) happens here, outside the graphs
+    timing = os.environ.get("SMD_SAMPLER_TIMING") == "1"          # diagnostics (tools/sampler_walk_time.py): blocks the host
+    if timing:
+        torch.cuda.synchronize()
+        t_warm = time.perf_counter()
+    streams = model.chain_streams(len(chains))
+    for ch, st in zip(chains, streams):
+        ch["stream"] = st
+        st.wait_stream(cur)
+        with torch.cuda.stream(st):
+            step(ch)
+    if timing:
+        torch.cuda.synchronize()
+        t_capture = time.perf_counter()
+    if not reuse:
+        for c, ch in enumerate(chains):
+            if unroll:          # chain 0: (output stage, next stem) x unroll; chain 1: (stem, output stage) x unroll
+                order = (2, 1) if c == 0 else (1, 2)
+                ch["graph"] = capture(ch, lambda ch=ch, order=order: [step(ch, part) for _ in range(unroll) for part in order])
+            else:
+                ch["graph"] = capture(ch, lambda ch=ch: step(ch))
+    if timing:
+        torch.cuda.synchronize()
+        t_loop = time.perf_counter()
+    if unroll:
+        A, Bc = chains
+        with torch.cuda.stream(A["stream"]):
+            step(A, 1)                                            # the pipeline's prologue: chain A's stem of the next iteration
+        ev = [[torch.cuda.Event() for _ in range(2)] for _ in range(2)]   # [chain][replay parity]
+        q, r = divmod(replays, unroll)
+        for i in range(q):
+            for c, ch in enumerate(chains):
+                with torch.cuda.stream(ch["stream"]):
+                    if i > 0:
+                        ch["stream"].wait_event(ev[1 - c][(i - 1) & 1])     # the other chain's previous replay
+                    ch["graph"].replay()
+                    ev[c][i & 1].record(ch["stream"])
+        for _ in range(r):                                        # the iterations that do not fill a graph, as plain launches
+            with torch.cuda.stream(A["stream"]):
+                step(A, 2)
+                step(A, 1)
+            with torch.cuda.stream(Bc["stream"]):
+                step(Bc, 1)
+                step(Bc, 2)
+        # (chain A ends one stem ahead: a pass over the final state that nothing reads)
+    else:
+        for _ in range(replays):
+            for ch in chains:
+                with torch.cuda.stream(ch["stream"]):
+                    ch["graph"].replay()
+    if timing:
+        t_issued = time.perf_counter()
+        torch.cuda.synchronize()
+        model._sampler_timing = dict(replays=replays, host_issue_s=t_issued - t_loop, loop_s=time.perf_counter() - t_loop, reused=reuse,
+                                     warmup_s=t_capture - t_warm, capture_s=t_loop - t_capture)
+    for ch in chains:
+        cur.wait_stream(ch["stream"])
+
+
 def diffusion_dynamics(rng: PRNGKey, model: Model, betas, init, epsilon=None, T=None, denoise=None, infill=False,
                        infill_samples=None, infill_masks=None, *, noises: Optional[Callable] = None,
                        infill_noises: Optional[Callable] = None, t_start: Optional[int] = None, t_stop: int = 0,
@@ -777,70 +853,10 @@ def diffusion_dynamics(rng: PRNGKey, model: Model, betas, init, epsilon=None, T=
                 izbuf.copy_(torch.as_tensor(infill_noises(t)).to(dev, torch.float32))
             ch["eng"].sample_step(ch["io"])
     elif graphed:
-        cur = torch.cuda.current_stream(dev)
-        replays = len(steps) - 1
-
-        def capture(ch, body):
-            ch["stream"].synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=ch["stream"]):
-                body()
-            return g
-
-        # the first iteration as plain launches on the chain's stream: the warm-up of a capture, and whatever a handle does
-        # lazily in front of a forward pass (fp8 mode: e4m3 copies of refreshed weights) happens here, outside the graphs
-        streams = model.chain_streams(len(chains))
-        for ch, st in zip(chains, streams):
-            ch["stream"] = st
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                ch["eng"].sample_step(ch["io"])
+        _graph_walk(model, dev, chains, len(steps) - 1, unroll, reuse, lambda ch, part=0: ch["eng"].sample_step(ch["io"], part))
         if not reuse:
-            for c, ch in enumerate(chains):
-                e, io = ch["eng"], ch["io"]
-                if unroll:          # chain 0: (output stage, next stem) x unroll; chain 1: (stem, output stage) x unroll
-                    order = (2, 1) if c == 0 else (1, 2)
-                    ch["graph"] = capture(ch, lambda e=e, io=io, order=order: [e.sample_step(io, part) for _ in range(unroll) for part in order])
-                else:
-                    ch["graph"] = capture(ch, lambda e=e, io=io: e.sample_step(io))
             entry["chains"] = chains
             cache["entry"] = entry
-        timing = os.environ.get("SMD_SAMPLER_TIMING") == "1"          # diagnostics (tools/sampler_walk_time.py): blocks the host twice
-        if timing:
-            torch.cuda.synchronize()
-            t_loop = time.perf_counter()
-        if unroll:
-            A, Bc = chains
-            with torch.cuda.stream(A["stream"]):
-                A["eng"].sample_step(A["io"], 1)                      # the pipeline's prologue: chain A's stem of the next iteration
-            ev = [[torch.cuda.Event() for _ in range(2)] for _ in range(2)]   # [chain][replay parity]
-            q, r = divmod(replays, unroll)
-            for i in range(q):
-                for c, ch in enumerate(chains):
-                    with torch.cuda.stream(ch["stream"]):
-                        if i > 0:
-                            ch["stream"].wait_event(ev[1 - c][(i - 1) & 1])     # the other chain's previous replay
-                        ch["graph"].replay()
-                        ev[c][i & 1].record(ch["stream"])
-            for _ in range(r):                                        # the iterations that do not fill a graph, as plain launches
-                with torch.cuda.stream(A["stream"]):
-                    A["eng"].sample_step(A["io"], 2)
-                    A["eng"].sample_step(A["io"], 1)
-                with torch.cuda.stream(Bc["stream"]):
-                    Bc["eng"].sample_step(Bc["io"], 1)
-                    Bc["eng"].sample_step(Bc["io"], 2)
-            # (chain A ends one stem ahead: a pass over the final state that nothing reads)
-        else:
-            for _ in range(replays):
-                for ch in chains:
-                    with torch.cuda.stream(ch["stream"]):
-                        ch["graph"].replay()
-        if timing:
-            t_issued = time.perf_counter()
-            torch.cuda.synchronize()
-            model._sampler_timing = dict(replays=replays, host_issue_s=t_issued - t_loop, loop_s=time.perf_counter() - t_loop, reused=reuse)
-        for ch in chains:
-            cur.wait_stream(ch["stream"])
     else:
         for _ in steps:
             chains[0]["eng"].sample_step(chains[0]["io"])
@@ -863,15 +879,208 @@ def diffusion_dynamics(rng: PRNGKey, model: Model, betas, init, epsilon=None, T=
     return x, collection, ld
 
 
+def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], coef: np.ndarray, plan: np.ndarray, walk_key: tuple, *,
+                  collect: bool, infill: bool = False, infill_samples=None, infill_masks=None, noises: Optional[Callable] = None,
+                  infill_noises: Optional[Callable] = None, use_graph: bool = True, one_chain: bool = False, sample_offset: int = 0,
+                  global_num_samples: Optional[int] = None):
+    """A table-driven walk over the timesteps ``order`` (smd_engine_strided_step) in the arrangement of diffusion_dynamics:
+    eager launches with explicit draws, else one graph-replayed chain, else (B >= 128, bf16 / fp8) the pipelined pair.  Its
+    cached graphs and persistent buffers live in their own ``slot`` of the model's sampler cache, beside diffusion_dynamics'
+    entry, keyed additionally by ``walk_key``.  Returns (state, collection or None, metrics_partial (T, B, 3) indexed by t)."""
+    eng = model.engine
+    dev = eng.device
+    init = torch.as_tensor(init).to(dev, torch.float32).contiguous()
+    B = init.shape[0]
+    if tuple(init.shape[1:]) != eng.cfg.sample_shape:
+        raise ValueError(f"init shape {tuple(init.shape)} != (B, {eng.cfg.sample_shape})")
+    nT = len(betas)
+    if infill:
+        inf_s = torch.as_tensor(infill_samples).to(dev, torch.float32).contiguous()
+        inf_m = torch.as_tensor(infill_masks).to(dev, torch.float32).contiguous()
+        start = init * (1 - inf_m) + inf_s * inf_m
+    else:
+        inf_s = inf_m = None
+        start = init
+    x = init.clone()
+    explicit = noises is not None or infill_noises is not None
+    jax_mode = isinstance(rng, ThreefryKey) and not explicit
+    graphed = use_graph and not explicit and len(order) > 1
+    per = int(np.prod(init.shape[1:]))
+    n_glob = (B + sample_offset if global_num_samples is None else int(global_num_samples)) * per
+    nk_d = ik_d = None
+    if jax_mode:                  # the key splits of the reference's scan, one row per ITERATION (plan[t].iteration picks it)
+        ik, nk = _jr.sampler_key_tables(rng, len(order))
+        nk_d = torch.from_numpy(nk.view(np.int32).copy()).to(dev)
+        ik_d = torch.from_numpy(ik.view(np.int32).copy()).to(dev) if infill else None
+    sizes, pad = sampler_chain_sizes(model, B, graphed and not one_chain, allow_pad=not jax_mode)
+    nchains = len(sizes)
+    offs = [0] + list(np.cumsum(sizes)[:-1])
+    unroll = _sampler_pipeline_unroll() if nchains == 2 else 0
+    engines = model.chain_engines(nchains) if nchains > 1 else [eng]
+    model.sampler_arrangement = dict(batch=B, chains=nchains, chain_sizes=list(sizes), padded=pad, graphed=bool(graphed),
+                                     pipelined_unroll=unroll, rng="threefry" if jax_mode else ("explicit" if explicit else "philox"),
+                                     walk=slot, iterations=len(order))
+    _log.info("%s walk: %d iterations, B=%d as %d chain(s) %s (+%d padding), %s", slot, len(order), B, nchains, list(sizes), pad,
+              f"pipelined, {unroll} steps per graph" if unroll else ("graph replay" if graphed else "eager launches"))
+    if pad:
+        zp = lambda t: None if t is None else torch.cat([t, torch.zeros((pad, *t.shape[1:]), dtype=t.dtype, device=dev)])
+        x, start, inf_s, inf_m = zp(x), zp(start), zp(inf_s), zp(inf_m)
+    for c, e in enumerate(engines):
+        _ensure_schedule(e, betas, with_sampler=True)
+        e.bind(sizes[c], training=False)
+    sig = tuple((id(e), e.generation) for e in engines) + (_lib.tuning_epoch(),)
+    ckey = (walk_key, B, tuple(sizes), pad, nchains, unroll, bool(infill), jax_mode, nT, int(sample_offset), int(n_glob),
+            tuple(init.shape[1:]))
+    cache = model.__dict__.setdefault("_sampler_graphs", {})
+    entry = cache.get(slot) if graphed else None
+    reuse = entry is not None and entry["key"] == ckey and entry["sig"] == sig
+    if reuse:
+        x = entry["x"]
+        x[:B].copy_(init)
+        if pad:
+            x[B:].zero_()
+        chains = entry["chains"]
+        if jax_mode:
+            entry["nk_d"].copy_(nk_d)
+            if ik_d is not None:
+                entry["ik_d"].copy_(ik_d)
+        if infill:
+            entry["inf_s"].copy_(inf_s)
+            entry["inf_m"].copy_(inf_m)
+    else:
+        coef_d, plan_d = torch.from_numpy(coef).to(dev), torch.from_numpy(plan).to(dev)
+        sp = _lib.StridePlan()
+        sp.coef, sp.plan, sp.T = coef_d.data_ptr(), plan_d.data_ptr(), nT
+        if graphed:
+            cache.pop(slot, None)
+        entry = dict(key=ckey, sig=sig, x=x, nk_d=nk_d, ik_d=ik_d, inf_s=inf_s, inf_m=inf_m, coef_d=coef_d, plan_d=plan_d, plan=sp)
+        chains = []
+    sp = entry["plan"]
+    key_words = torch.tensor([rng.seed & 0xFFFFFFFF, (rng.seed >> 32) & 0xFFFFFFFF], dtype=torch.int64).to(torch.int32)
+    for c, e in enumerate(engines):
+        if c == 0:
+            e.refresh_weights()
+        e.prepare_sampler()
+        h = sizes[c]
+        lo, hi = int(offs[c]), int(offs[c]) + h
+        if reuse:
+            ch = chains[c]
+            if collect:
+                ch["coll"].zero_()
+            ch["metrics"].zero_()
+            ch["t_ptr"].fill_(order[0])
+        else:
+            ch = dict(eng=e, x=x[lo:hi], metrics=torch.zeros((nT, h, 3), dtype=torch.float32, device=dev),
+                      coll=torch.zeros((COLLECTION_STEPS + 1, h, *init.shape[1:]), dtype=torch.float32, device=dev) if collect else None,
+                      t_ptr=torch.tensor([order[0]], dtype=torch.int32, device=dev),
+                      key=torch.zeros(2, dtype=torch.int32, device=dev))
+            io = _lib.SampleIO()
+            io.x = ch["x"].data_ptr(); io.t_ptr = ch["t_ptr"].data_ptr()
+            io.seed_lo = rng.seed & 0xFFFFFFFF; io.seed_hi = (rng.seed >> 32) & 0xFFFFFFFF
+            io.key_ptr = ch["key"].data_ptr()
+            io.sample_offset = sample_offset + lo
+            io.infill_samples = None if inf_s is None else inf_s[lo:hi].data_ptr()
+            io.infill_masks = None if inf_m is None else inf_m[lo:hi].data_ptr()
+            io.metrics_partial = ch["metrics"].data_ptr()
+            io.collection = None if not collect else ch["coll"].data_ptr()
+            if jax_mode:
+                io.tf_noise_keys = nk_d.data_ptr()
+                io.tf_infill_keys = None if ik_d is None else ik_d.data_ptr()
+                io.tf_n_total = n_glob
+            ch["io"] = io
+            chains.append(ch)
+        ch["key"].copy_(key_words)
+        if collect:
+            ch["coll"][0] = start[lo:hi]
+        e.load_state(ch["x"])
+
+    step = lambda ch, part=0: ch["eng"].strided_step(ch["io"], sp, part)
+    if explicit:
+        ch = chains[0]
+        zbuf = torch.zeros_like(x)
+        izbuf = torch.zeros_like(x) if infill else None
+        ch["io"].z_in = zbuf.data_ptr()
+        ch["io"].infill_z_in = None if izbuf is None else izbuf.data_ptr()
+        for t in order:
+            if noises is not None and coef[t, 4] != 0:
+                zbuf.copy_(torch.as_tensor(noises(t)).to(dev, torch.float32))
+            if izbuf is not None and infill_noises is not None and 0 <= plan[t, 0] < nT:
+                izbuf.copy_(torch.as_tensor(infill_noises(t)).to(dev, torch.float32))
+            step(ch)
+    elif graphed:
+        _graph_walk(model, dev, chains, len(order) - 1, unroll, reuse, step)
+        if not reuse:
+            entry["chains"] = chains
+            cache[slot] = entry
+    else:
+        for _ in order:
+            step(chains[0])
+
+    if graphed:
+        x = x[:B].clone()                  # the persistent state buffer belongs to the cached graphs
+    collection = None
+    if collect:
+        collection = (chains[0]["coll"].clone() if graphed else chains[0]["coll"]) if nchains == 1 else \
+            torch.cat([ch["coll"] for ch in chains], dim=1)[:, :B]
+    metrics_partial = chains[0]["metrics"] if nchains == 1 else torch.cat([ch["metrics"] for ch in chains], dim=1)[:, :B]
+    return x, collection, metrics_partial
+
+
+def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, infill=False, infill_samples=None,
+                     infill_masks=None, *, noises: Optional[Callable] = None, infill_noises: Optional[Callable] = None,
+                     use_graph: bool = True, sample_offset: int = 0, global_num_samples: Optional[int] = None):
+    """The generalised non-Markovian sampler of Song et al. 2021 (DDIM) on ``steps`` evenly spaced timesteps of the schedule
+    (schedule.stride_timesteps) instead of all of them: ``steps`` network evaluations from the same checkpoint.  ``eta`` scales
+    the noise of every iteration (0: deterministic, 1: the DDPM posterior's variance).  Returns (state, collection (41, ...),
+    ld_metrics (4, steps, 1)) like diffusion_dynamics: row j of ld_metrics is iteration j, its alpha row the cumulative alpha
+    of that iteration's timestep; the collection follows the reference's bookkeeping for a walk of ``steps`` iterations.
+    ``noises(t)`` / ``infill_noises(t)`` supply the draws of the iteration at timestep t explicitly.  With infill the known
+    region is re-noised to the level of the state being PRODUCED (the next timestep of the walk), not to the level of t as
+    utils/ebm_utils.py:346 does: one timestep apart there, a whole stride here."""
+    nT = len(betas)
+    taus = _sched.stride_timesteps(nT, steps)
+    coef, plan = _sched.strided_coefficient_table(betas, taus, eta)
+    order = [int(t) for t in taus]
+    x, collection, mp = _strided_walk("strided", rng, model, betas, init, order, coef, plan, ("strided", len(order), float(eta)),
+                                      collect=True, infill=infill, infill_samples=infill_samples, infill_masks=infill_masks,
+                                      noises=noises, infill_noises=infill_noises, use_graph=use_graph, sample_offset=sample_offset,
+                                      global_num_samples=global_num_samples)
+    eng = model.engine
+    B = x.shape[0]
+    denom = float(B) if eng.S == 1 else float(B * eng.C)
+    idx = torch.tensor(order, device=eng.device, dtype=torch.long)
+    per_t = mp.sum(dim=1)[idx] / denom                                              # (K, 3), row j = iteration j
+    ld = torch.zeros((4, len(order), 1), dtype=torch.float32, device=eng.device)
+    ld[0, :, 0], ld[1, :, 0], ld[3, :, 0] = per_t[:, 0], per_t[:, 1], per_t[:, 2]
+    ld[2, :, 0] = torch.from_numpy(_sched.alphas_cumprod(betas)[taus]).to(eng.device)
+    return x, collection, ld
+
+
+def ddim_encode(model: Model, betas, x0, steps, *, use_graph: bool = True):
+    """The deterministic encoder of the strided sampler: the same update walked UP the ``steps`` timesteps with sigma = 0 (DDIM
+    inversion), ``steps - 1`` network evaluations, one chain, no noise and no collection.  Returns the latent at level T - 1,
+    which ``strided_dynamics(..., steps, eta=0)`` decodes again up to the discretisation error of the two walks."""
+    nT = len(betas)
+    taus = _sched.stride_timesteps(nT, steps)
+    coef, plan = _sched.inversion_coefficient_table(betas, taus)
+    order = sorted(int(t) for t in taus)[:-1]
+    x, _, _ = _strided_walk("encode", PRNGKey(0), model, betas, x0, order, coef, plan, ("encode", len(order)), collect=False,
+                            use_graph=use_graph, one_chain=True)
+    return x
+
+
 def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400, sampling="ald", epsilon=1e-3,
            steps=100, denoise=True, *, sample_offset: int = 0, use_graph: bool = True,
-           global_num_samples: Optional[int] = None):
+           global_num_samples: Optional[int] = None, ddim_steps: int = 0, ddim_eta: float = 0.0):
     """train_ncsn.py:499-551.  'ddpm': N(0,1) init + diffusion_dynamics.  'ald' / 'cas': uniform(-sqrt(12)/2, sqrt(12)/2)
     init (:542-547) + annealed / consistent Langevin dynamics with the score network ``scorenet``.  The reference unpacks
     three values from every sampler although consistent_langevin_dynamics returns two (a ValueError upstream); here 'cas'
-    returns a two-entry collection [init, final state]."""
+    returns a two-entry collection [init, final state].  ``ddim_steps`` > 0 ('ddpm' only): the same initialisation, then the
+    strided walk ``strided_dynamics(..., ddim_steps, ddim_eta)`` instead of every timestep."""
     if sampling not in ("ddpm", "ald", "cas"):
         raise ValueError(f"Unknown sampling algorithm: {sampling}")
+    if ddim_steps and sampling != "ddpm":
+        raise ValueError("ddim_steps is a DDPM option: sampling must be 'ddpm'")
     init_rng, ld_rng = split(rng)                                                    # :536
     eng = scorenet.engine
     if tuple(sample_shape) != eng.cfg.sample_shape:
@@ -905,6 +1114,11 @@ def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400
         _jr.normal(init_rng, init.shape, eng.device, n_total=n_glob, offset=sample_offset * per, out=init)
     else:
         eng.init_state(init, init_rng.seed, sample_offset)                           # :539-540 N(0,1)
+    if ddim_steps:
+        generated, collection, ld_metrics = strided_dynamics(ld_rng, scorenet, sigmas, init, ddim_steps, ddim_eta,
+                                                             sample_offset=sample_offset, use_graph=use_graph,
+                                                             global_num_samples=global_num_samples)
+        return generated, collection, collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = diffusion_dynamics(ld_rng, scorenet, sigmas, init, epsilon, steps, denoise,
                                                            False, sample_offset=sample_offset, use_graph=use_graph,
                                                            global_num_samples=global_num_samples)

@@ -73,3 +73,64 @@ def collection_slot_table(T: int) -> np.ndarray:
             s = int(np.sum(hit)) + 1
             slot[t] = s if s <= COLLECTION_STEPS else -1
     return slot
+
+
+# ------------------------------------------------------------------ strided (DDIM) walks
+def stride_timesteps(T: int, K: int) -> np.ndarray:
+    """The K timesteps of a strided walk over [0, T), descending: evenly spaced, always with T - 1 and 0."""
+    T, K = int(T), int(K)
+    if not 2 <= K <= T:
+        raise ValueError(f"a strided walk takes 2 <= steps <= {T} timesteps, got {K}")
+    return np.unique(np.round(np.linspace(0, T - 1, K)).astype(int))[::-1].copy()
+
+
+def strided_coefficients(betas: np.ndarray, taus, eta: float) -> dict:
+    """float64 (a, b, sigma, sqrt_as, sqrt_1m_as), one entry per iteration of the descending walk ``taus``, of
+    x_s = a x0 + b x_t + sigma z (Song et al. 2021, eq. 12 with eps_hat written as (x_t - sqrt(ap_t) x0) / sqrt(1 - ap_t));
+    ap is the float32 cumulative product the engine's other tables use, and ap_s := 1 on the last iteration."""
+    taus = np.asarray(taus, dtype=np.int64)
+    ap = alphas_cumprod(betas).astype(np.float64)
+    ap_t = ap[taus]
+    ap_s = np.concatenate([ap[taus[1:]], np.ones(1)])
+    sigma = float(eta) * np.sqrt((1 - ap_s) / (1 - ap_t)) * np.sqrt(1 - ap_t / ap_s)
+    c = np.sqrt(np.maximum(1 - ap_s - sigma ** 2, 0.0)) / np.sqrt(1 - ap_t)
+    return dict(a=np.sqrt(ap_s) - c * np.sqrt(ap_t), b=c, sigma=sigma, sqrt_as=np.sqrt(ap_s), sqrt_1m_as=np.sqrt(1 - ap_s))
+
+
+def _walk_tables(betas, order, co, next_t, slots, clip):
+    T = len(betas)
+    base = reverse_coefficient_table(betas)
+    coef = np.zeros((T, 8), dtype=np.float32)
+    plan = np.zeros((T, 4), dtype=np.int32)
+    plan[:, :3] = -1                                       # not on the walk: no next timestep, no iteration, no slot
+    for j, t in enumerate(order):
+        coef[t] = (base[t, 0], base[t, 1], co["a"][j], co["b"][j], co["sigma"][j], clip, co["sqrt_as"][j], co["sqrt_1m_as"][j])
+        plan[t] = (next_t[j], j, slots[j], 0)
+    return coef, plan
+
+
+def strided_coefficient_table(betas: np.ndarray, taus, eta: float, clip: float = 1.0):
+    """Tables of the strided sampler for the descending timesteps ``taus``: float32 [T][8] (sqrt_recip, sqrt_m1, a, b, sigma,
+    clip, sqrt_as, sqrt_1m_as) and int32 [T][4] (next_t, iteration, slot, 0).  Columns 0 / 1 are those of
+    ``reverse_coefficient_table``.  Timesteps that are not in ``taus`` have a zero row and (-1, -1, -1, 0); next_t is -1
+    after the last iteration.  The slots are the reference's collection bookkeeping (``collection_slot_table``) applied to a
+    walk of K = len(taus) iterations, so the collection keeps its 41 rows."""
+    taus = [int(t) for t in taus]
+    K = len(taus)
+    slot_k = collection_slot_table(K)
+    return _walk_tables(betas, taus, strided_coefficients(betas, taus, eta), taus[1:] + [-1],
+                        [int(slot_k[K - 1 - j]) for j in range(K)], clip)
+
+
+def inversion_coefficient_table(betas: np.ndarray, taus):
+    """The same walk ascending with sigma = 0 (DDIM inversion): taus_asc[j] -> taus_asc[j + 1], no clamp (clip = +inf), nothing
+    collected.  len(taus) - 1 steps are executed; the last of them has next_t = T, which is out of range, so the walk stops by
+    itself and no step is executed at T - 1."""
+    asc = sorted(int(t) for t in taus)
+    ap = alphas_cumprod(betas).astype(np.float64)
+    t_, s_ = np.asarray(asc[:-1]), np.asarray(asc[1:])
+    c = np.sqrt(1 - ap[s_]) / np.sqrt(1 - ap[t_])
+    co = dict(a=np.sqrt(ap[s_]) - c * np.sqrt(ap[t_]), b=c, sigma=np.zeros(len(t_)), sqrt_as=np.sqrt(ap[s_]),
+              sqrt_1m_as=np.sqrt(1 - ap[s_]))
+    n = len(t_)
+    return _walk_tables(betas, asc[:-1], co, asc[1:-1] + [len(betas)], [-1] * n, np.inf)
