@@ -232,6 +232,41 @@ typedef struct smd_stride_plan {
 } smd_stride_plan;
 int smd_engine_strided_step(smd_engine* e, const smd_sample_io* io, const smd_stride_plan* plan, int part, void* stream);
 
+/* One iteration of a walk that evaluates the variational bound of Ho et al. 2020 (eq. 5) term by term on held-out examples (no
+ * counterpart in the reference).  At t = *t_ptr:
+ *   smd_bound_noise   x_t = sqrt(ap_t) x0 + sqrt(1-ap_t) eps  -> x_t (fp32) and the engine's bf16 network input
+ *   eps-net           eps_hat = model(x_t, sqrt(ap_t)), FiLM-table row t as in smd_engine_forward_level
+ *   smd_bound_terms   partial[t][b] = (sum (x0 - x0_hat)^2, sum (eps - eps_hat)^2, sum x0^2) over (s, c), fp32, with
+ *                     x0_hat = clamp(sqrt(1/ap_t) x_t - sqrt(1/ap_t - 1) eps_hat, -clip, clip); the launch's last workgroup
+ *                     stores next_t[t] to *t_ptr
+ * Everything that depends on the timestep is read from device memory, so one captured iteration replays for a whole walk; the
+ * host weights the sums (schedule.bound_tables) in float64.  eps: eps_source 0 = the caller put it into `eps`; 1 = the call
+ * first fills `eps` with jax.random.normal(tf_keys[t], (N, S, C)) for this rank's rows [sample_offset, sample_offset + B)
+ * (smd_threefry_normal with the key read on the device: tf_keys [T][2] uint32, tf_n_total = N S C; rows -1 and T of the key
+ * table must be readable -- the draw of an iteration that turns out to be a no-op reads one of them and is discarded);
+ * 2 = Philox keyed by (seed, b + sample_offset, t) on a stream id of its own (5: neither the sampler's nor the loss's draws),
+ * written to `eps`.  t outside [0, T) makes both kernels no-ops that write and advance nothing (a host issues as many
+ * iterations as its walk has timesteps, as for smd_engine_strided_step).  Needs smd_engine_prepare_sampler's FiLM tables and an inference
+ * workspace; works for both architectures and under the options "fp8" and "fp32".  T must be the engine's num_timesteps; table
+ * rows, and for data_channels % 4 == 0 every fp32 array, 16-byte aligned. */
+typedef struct smd_bound_io {
+  const float* x0;                 /* [B][S][C] examples (model space) */
+  float* x_t;                      /* [B][S][C] scratch: the noised examples of the current timestep */
+  float* eps;                      /* [B][S][C] the draw (read or written, see eps_source) */
+  int32_t* t_ptr;                  /* device timestep; replaced by next_t[t] */
+  const float* table;              /* [T][4] (sqrt(ap), sqrt(1-ap), sqrt(1/ap), sqrt(1/ap - 1)) */
+  const int32_t* next_t;           /* [T] the walk: next timestep after t, -1 ends it */
+  int32_t T;
+  float clip;                      /* > 0; inf = no clamp */
+  int32_t eps_source;              /* 0 explicit, 1 jax.random (threefry), 2 Philox */
+  uint32_t seed_lo, seed_hi, sample_offset;
+  const uint32_t* key_ptr;         /* Philox key in device memory ([2] words) or NULL = seed_lo / seed_hi */
+  const uint32_t* tf_keys;         /* eps_source 1: [T][2] key table */
+  int64_t tf_n_total;
+  float* partial;                  /* [T][B][3] */
+} smd_bound_io;
+int smd_engine_bound_step(smd_engine* e, const smd_bound_io* io, void* stream);
+
 /* One Langevin update of annealed_langevin_dynamics / consistent_langevin_dynamics (utils/ebm_utils.py:131-164, 231-253):
  *   next = x + alpha * grad + noise_coef * z;  with infill: next = next (1 - mask) + (infill_samples + infill_sigma * zi) mask.
  * grad = model(state, sigma) comes from smd_engine_forward.  z / zi: explicit arrays, else jax.random.normal(step_rng) /
@@ -436,6 +471,21 @@ int smd_ddpm_reverse_step(float* x, const float* eps_hat, int B, int S, int C, c
                           const int32_t* t_ptr, const float* z_in, uint32_t seed_lo, uint32_t seed_hi,
                           uint32_t sample_offset, float* metrics_partial, float* collection,
                           const int32_t* slot_table, void* stream);
+/* The two kernels of smd_engine_bound_step on explicit arrays.  table is the [T][4] table of smd_bound_io (16-byte aligned);
+ * *t_ptr outside [0, T) makes either call a no-op that writes nothing.
+ * smd_bound_noise: x_t [B][S][C] = sqrt(ap_t) x0 + sqrt(1-ap_t) eps (one FMA per element) and, with xt_bf16 != NULL, its bf16
+ *   rounding at [B*S][Cp] (the columns >= C are not written).  draw 0: eps is read; draw != 0: eps is WRITTEN with Philox
+ *   normals, counter (e/4, b + sample_offset, 5, t), key = key_ptr[0..1] if key_ptr != NULL else (seed_lo, seed_hi).
+ * smd_bound_terms: partial[t][b][0..2] = (sum (x0 - x0_hat)^2, sum (eps - eps_hat)^2, sum x0^2), partial [T][B][3] fp32, only row
+ *   t is written.  x0 - x0_hat is sqrt_m1 (eps_hat - eps) plus the two O(1e-7) terms the rounding of the table rows leaves
+ *   where the reconstruction is inside [-clip, clip], x0 -/+ clip elsewhere.  No atomics on floats, a fixed summation order:
+ *   a sample's sums depend on its own rows only (not on B or the other samples), and two calls agree bitwise.  next_t != NULL:
+ *   the launch's last workgroup stores next_t[t] to *t_ptr (arrive: one zeroed uint32, reset by the kernel). */
+int smd_bound_noise(const float* x0, int B, int S, int C, int Cp, const float* table, int T, const int32_t* t_ptr, float* eps,
+                    int draw, uint32_t seed_lo, uint32_t seed_hi, const uint32_t* key_ptr, uint32_t sample_offset, float* x_t,
+                    smd_bf16* xt_bf16, void* stream);
+int smd_bound_terms(const float* x0, const float* eps, const float* eps_hat, int B, int S, int C, const float* table, int T,
+                    float clip, int32_t* t_ptr, const int32_t* next_t, uint32_t* arrive, float* partial, void* stream);
 
 /* ---- reference-precision (fp32) kernels of the engine option "fp32" -----------------------------------------------------
  * smd_gemm_f32: out[m][n] = act(sum_k A[m][k] W[k][n] + bias[n]) + residual[m or m % res_row_mod][n], nn.Dense with A

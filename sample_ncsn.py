@@ -2,7 +2,8 @@
 --sampling_dir`` on the MI355X HIP engine: unconditional generation, infilling (--infill) and
 interpolation (--interpolate) for DDPM checkpoints, writing {sampling_dir}/ncsn/{generated,
 collection,real}.pkl in the reference's layout (sample_ncsn.py:368-471).  --ddim_steps=K walks K of the
-schedule's timesteps with the strided (DDIM) sampler instead of all of them, in all three modes.
+schedule's timesteps with the strided (DDIM) sampler instead of all of them, in all three modes.  --compute_bound
+evaluates the per-timestep variational bound on the eval examples first (--bound_only: and stops there).
 
 Multi-GPU sampling is embarrassingly parallel: under torch.distributed.run each rank generates a
 contiguous shard of the samples (Philox counters are keyed by the GLOBAL sample index, so the
@@ -245,6 +246,63 @@ def check_ddim_flags(FLAGS):
         raise SystemExit("--ddim_encode replaces the encoder of --interpolate: it needs --interpolate")
 
 
+def check_bound_flags(FLAGS):
+    """the refusals of --compute_bound / --bound_steps / --bound_only, before the GPU is touched"""
+    if not FLAGS.compute_bound:
+        used = [f"--{n}" for n in ("bound_steps", "bound_only") if FLAGS.is_present(n) and getattr(FLAGS, n)]
+        if used:
+            raise SystemExit(f"{', '.join(used)}: options of the variational bound, give --compute_bound")
+        return
+    if FLAGS.sampling != "ddpm":
+        raise SystemExit(f"--compute_bound: the variational bound is that of a DDPM schedule, it needs --sampling=ddpm (got --sampling={FLAGS.sampling})")
+    if FLAGS.loss != "ddpm":
+        raise SystemExit(f"--compute_bound: the network must be an eps-predictor trained with --loss=ddpm (got --loss={FLAGS.loss})")
+    steps = FLAGS.bound_steps
+    if steps is None or not (steps == 0 or 2 <= steps <= FLAGS.num_sigmas):
+        raise SystemExit(f"--bound_steps={steps}: 0 (every timestep) or from 2 to --num_sigmas={FLAGS.num_sigmas} timesteps")
+
+
+def compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world):
+    """The variational bound over this rank's rows [lo, hi) of the eval set; rank 0 gathers and writes
+    {sampling_dir}/ncsn/bound.json (scalars, per-timestep means) and bound_terms.pkl (the per-example arrays)."""
+    import json
+
+    from smd_amd import data, ncsn
+    rng = ncsn.split(ncsn.make_key(FLAGS.sample_seed, FLAGS.rng_impl), num=4)[3]
+    t0 = time.time()
+    out = ncsn.variational_bound(rng, model, sigmas, np.ascontiguousarray(real[lo:hi], dtype=np.float32), FLAGS.bound_steps,
+                                 sample_offset=lo, global_num_samples=len(real), use_graph=FLAGS.graph)
+    model.drop_sampler_cache()
+    parts = [out]
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.gather_object(out, parts if rank == 0 else None, dst=0)
+    if rank != 0:
+        return
+    terms = np.concatenate([p["terms"] for p in parts], axis=1)
+    eps_mse = np.concatenate([p["eps_mse"] for p in parts], axis=1)
+    prior = np.concatenate([p["prior"] for p in parts])
+    exact = out["total"] is not None
+    total = np.concatenate([p["total"] for p in parts]) if exact else None
+    per = int(np.prod(real.shape[1:]))
+    nats = float(total.mean() / per) if exact else None
+    bits = float(total.mean() / (per * np.log(2.0))) if exact else None
+    summary = dict(nats_per_dim=nats, bits_per_dim=bits, total=float(total.mean()) if exact else None, prior=float(prior.mean()),
+                   timesteps=[int(t) for t in out["timesteps"]], terms=[float(v) for v in terms.mean(axis=1)],
+                   eps_mse=[float(v) for v in eps_mse.mean(axis=1)], dtype=FLAGS.dtype, num_examples=int(len(real)), clip=1.0,
+                   var_0=float(out["var_0"]), exact=bool(exact))
+    log_dir = FLAGS.sampling_dir
+    os.makedirs(os.path.join(log_dir, "ncsn"), exist_ok=True)
+    with open(os.path.join(log_dir, "ncsn/bound.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    data.save(dict(timesteps=out["timesteps"], terms=terms, eps_mse=eps_mse, prior=prior, total=total),
+              os.path.join(log_dir, "ncsn/bound_terms.pkl"))
+    log.info("variational bound on %d examples (%s, %d timesteps, %.1f s): %s, prior %.4f nats", len(real), FLAGS.dtype,
+             len(out["timesteps"]), time.time() - t0,
+             f"{bits:.4f} bits/dim ({nats:.4f} nats/dim)" if exact else "a sub-sequence of the timesteps, no total", prior.mean())
+
+
 def main(argv):
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     FLAGS = F.make_flags(include_sample=True)
@@ -271,6 +329,7 @@ def main(argv):
     if FLAGS.cluster_metrics:
         check_cluster_flags(FLAGS)
     check_ddim_flags(FLAGS)
+    check_bound_flags(FLAGS)
     torch.cuda.set_device(local_rank)
     dev = f"cuda:{local_rank}"
     if world > 1:
@@ -298,6 +357,14 @@ def main(argv):
     num = len(real)
     lo, hi = shard_bounds(num, world, rank)
     model, rng = load_model(FLAGS, shape, dev)
+
+    if FLAGS.compute_bound:
+        compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world)
+        if FLAGS.bound_only:
+            if world > 1:
+                import torch.distributed as dist
+                dist.destroy_process_group()
+            return
 
     if FLAGS.infill:                                                        # :405-423
         samples = np.copy(real[lo:hi])

@@ -224,6 +224,16 @@ int smd_engine_strided_step(smd_engine* e, const smd_sample_io* io, const smd_st
   p.coef = plan->coef; p.plan = plan->plan; p.T = plan->T;
   return e->impl.strided_step(sample_io(io), p, S(stream), part);
 }
+int smd_engine_bound_step(smd_engine* e, const smd_bound_io* io, void* stream) {
+  NEED(e);
+  SMD_ARG_CHECK(io, "bound_step: null io");
+  BoundStepIO b;
+  b.x0 = io->x0; b.x_t = io->x_t; b.eps = io->eps; b.t_ptr = io->t_ptr; b.table = io->table; b.next_t = io->next_t; b.T = io->T;
+  b.clip = io->clip; b.eps_source = io->eps_source; b.seed_lo = io->seed_lo; b.seed_hi = io->seed_hi;
+  b.sample_offset = io->sample_offset; b.key_ptr = io->key_ptr; b.tf_keys = io->tf_keys; b.tf_n_total = io->tf_n_total;
+  b.partial = io->partial;
+  return e->impl.bound_step(b, S(stream));
+}
 
 // ------------------------------------------------------------------ single kernels
 int smd_set_tuning(const char* key, int value) { return smd_tuning_set(key, value); }
@@ -459,6 +469,22 @@ int smd_ddpm_reverse_step(float* x, const float* eps_hat, int Bn, int Sn, int C,
   a.key = RngKey{lo, hi}; a.sample_offset = off; a.metrics_partial = metrics_partial; a.collection = collection;
   a.slot_table = slot_table;
   return launch_reverse_step(a, S(stream));
+}
+
+int smd_bound_noise(const float* x0, int Bn, int Sn, int C, int Cp, const float* table, int T, const int32_t* t_ptr, float* eps,
+                    int draw, uint32_t lo, uint32_t hi, const uint32_t* key_ptr, uint32_t off, float* x_t, smd_bf16* xt_bf16,
+                    void* stream) {
+  BoundNoiseArgs a;
+  a.x0 = x0; a.eps = eps; a.draw = draw ? 1 : 0; a.B = Bn; a.S = Sn; a.C = C; a.Cp = Cp; a.T = T; a.table = table; a.t_ptr = t_ptr;
+  a.key = RngKey{lo, hi}; a.key_ptr = key_ptr; a.sample_offset = off; a.x_t = x_t; a.xt_bf16 = B(xt_bf16);
+  return launch_bound_noise(a, S(stream));
+}
+int smd_bound_terms(const float* x0, const float* eps, const float* eps_hat, int Bn, int Sn, int C, const float* table, int T,
+                    float clip, int32_t* t_ptr, const int32_t* next_t, uint32_t* arrive, float* partial, void* stream) {
+  BoundTermsArgs a;
+  a.x0 = x0; a.eps = eps; a.eps_hat = eps_hat; a.B = Bn; a.S = Sn; a.C = C; a.T = T; a.table = table; a.clip = clip;
+  a.t_ptr = t_ptr; a.next_t = next_t; a.arrive = arrive; a.partial = partial;
+  return launch_bound_terms(a, S(stream));
 }
 
 int smd_probe_tr_read(const smd_bf16* image, smd_bf16* out, void* stream) { return launch_probe_tr_read(B(image), B(out), S(stream)); }

@@ -70,6 +70,23 @@ struct StridePlan {
   int T = 0;
 };
 
+struct BoundStepIO {                   // include/smd_hip.h smd_bound_io
+  const float* x0 = nullptr;
+  float* x_t = nullptr;
+  float* eps = nullptr;
+  int* t_ptr = nullptr;
+  const float* table = nullptr;       // [T][4], see BoundNoiseArgs
+  const int32_t* next_t = nullptr;    // [T]
+  int T = 0;
+  float clip = 1.0f;
+  int eps_source = 0;                 // 0 explicit, 1 jax.random (threefry), 2 Philox
+  uint32_t seed_lo = 0, seed_hi = 0, sample_offset = 0;
+  const uint32_t* key_ptr = nullptr;
+  const uint32_t* tf_keys = nullptr;  // [T][2]
+  int64_t tf_n_total = 0;
+  float* partial = nullptr;           // [T][B][3]
+};
+
 class SmdEngine {
  public:
   explicit SmdEngine(const SmdModelDesc& d);
@@ -134,6 +151,8 @@ class SmdEngine {
   int sample_step(const SampleStepIO& io, hipStream_t st, int part = 0);   // eps-net forward + fused reverse step
   // eps-net forward + fused strided (DDIM) step: the walk and its coefficients come from the plan (io.slot_table / tf_t0 unused)
   int strided_step(const SampleStepIO& io, const StridePlan& plan, hipStream_t st, int part = 0);
+  // one iteration of the variational-bound walk: noise an example to level t, eps-net forward at table row t, the three sums
+  int bound_step(const BoundStepIO& io, hipStream_t st);
   int init_state(float* x, uint32_t seed_lo, uint32_t seed_hi, uint32_t sample_offset, hipStream_t st);
   int load_state(const float* x, hipStream_t st);            // explicit state -> bf16 network input
   // device pointers of a few internals (tests / metrics)

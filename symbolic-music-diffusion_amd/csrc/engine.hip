@@ -1423,3 +1423,31 @@ int SmdEngine::strided_step(const SampleStepIO& io, const StridePlan& plan, hipS
   a.t_advance = io.t_ptr; a.arrive = W.step_arrive;      // *t_ptr = plan[t].next_t by the step's last workgroup
   return launch_strided_step(a, st);
 }
+
+int SmdEngine::bound_step(const BoundStepIO& io, hipStream_t st) {
+  SMD_ARG_CHECK(io.x0 && io.x_t && io.eps && io.t_ptr && io.partial, "bound_step: null example / scratch / t pointer / partial");
+  SMD_ARG_CHECK(io.table && io.next_t, "bound_step: null table / next_t");
+  SMD_ARG_CHECK(io.T == d_.num_timesteps, "bound_step: the tables have T=%d rows, the engine %d timesteps", io.T, d_.num_timesteps);
+  SMD_ARG_CHECK(!training_ && batch_ > 0 && film_tables_, "bound_step: bind an inference workspace and the schedule tables first");
+  SMD_ARG_CHECK(io.eps_source >= 0 && io.eps_source <= 2, "bound_step: eps_source=%d (0 explicit, 1 threefry, 2 Philox)", io.eps_source);
+  const int S = d_.seq_len, C = d_.data_channels;
+  if (io.eps_source == 1) {
+    const int64_t per = (int64_t)S * C;
+    SMD_ARG_CHECK(io.tf_keys, "bound_step: eps_source 1 needs the key table");
+    SMD_ARG_CHECK(io.tf_n_total >= ((int64_t)io.sample_offset + batch_) * per && io.tf_n_total <= (1ll << 32),
+                  "bound_step: tf_n_total=%lld must cover this rank's window and be <= 2^32", (long long)io.tf_n_total);
+    RC(launch_threefry_normal(io.eps, io.tf_n_total, (int64_t)io.sample_offset * per, (int64_t)batch_ * per, 0u, 0u, io.tf_keys,
+                              io.t_ptr, 1, 0, st));
+  }
+  BoundNoiseArgs n;
+  n.x0 = io.x0; n.eps = io.eps; n.draw = io.eps_source == 2; n.B = batch_; n.S = S; n.C = C; n.Cp = Cp_; n.T = io.T;
+  n.table = io.table; n.t_ptr = io.t_ptr; n.key = RngKey{io.seed_lo, io.seed_hi}; n.key_ptr = io.key_ptr;
+  n.sample_offset = io.sample_offset; n.x_t = io.x_t;
+  n.xt_bf16 = fp32 ? nullptr : W.x_bf16;      // reference precision reads the fp32 x_t itself
+  RC(launch_bound_noise(n, st));
+  RC(run_network(io.t_ptr, st, 0, io.x_t));
+  BoundTermsArgs a;
+  a.x0 = io.x0; a.eps = io.eps; a.eps_hat = W.pred; a.B = batch_; a.S = S; a.C = C; a.T = io.T; a.table = io.table;
+  a.clip = io.clip; a.t_ptr = io.t_ptr; a.next_t = io.next_t; a.arrive = W.step_arrive; a.partial = io.partial;
+  return launch_bound_terms(a, st);
+}

@@ -315,6 +315,38 @@ int launch_strided_step(const StridedStepArgs& a, hipStream_t st);
 int launch_advance_t(int* t_ptr, hipStream_t st);   // *t_ptr -= 1
 int launch_set_t(int* t_ptr, int v, hipStream_t st);   // *t_ptr = v (restart of a walk on the sampler's own stream)
 
+// ------------------------------------------------------------------ variational bound (bound.hip)
+// Both kernels read the timestep from device memory; t outside [0, T) makes them no-ops.  table [T][4] float32 rows
+// (sqrt(ap), sqrt(1-ap), sqrt(1/ap), sqrt(1/ap - 1)), 16-byte aligned.
+struct BoundNoiseArgs {
+  const float* x0 = nullptr;          // [B][S][C] examples
+  float* eps = nullptr;               // [B][S][C]: read (draw == 0: explicit / filled by launch_threefry_normal) or written (draw == 1)
+  int draw = 0;                       // 1: Philox normals keyed by (key, b + sample_offset, t) on SMD_STREAM_BOUND
+  int B = 0, S = 0, C = 0, Cp = 0, T = 0;
+  const float* table = nullptr;
+  const int* t_ptr = nullptr;
+  RngKey key{0, 0};
+  const uint32_t* key_ptr = nullptr;  // device-resident Philox key [2] (overrides `key`)
+  uint32_t sample_offset = 0;
+  float* x_t = nullptr;               // [B][S][C] sqrt(ap_t) x0 + sqrt(1-ap_t) eps
+  bf16_t* xt_bf16 = nullptr;          // [B*S][Cp] network input or null; the columns >= C are not written
+};
+int launch_bound_noise(const BoundNoiseArgs& a, hipStream_t st);
+
+struct BoundTermsArgs {
+  const float* x0 = nullptr;          // [B][S][C]
+  const float* eps = nullptr;         // [B][S][C] the draw x_t was made from
+  const float* eps_hat = nullptr;     // [B][S][C] model(x_t, sqrt(ap_t))
+  int B = 0, S = 0, C = 0, T = 0;
+  const float* table = nullptr;
+  float clip = 1.0f;                  // x0_hat is clamped to [-clip, clip]; inf = no clamp
+  int* t_ptr = nullptr;               // device timestep
+  const int32_t* next_t = nullptr;    // [T] or null: the last workgroup stores next_t[t] to *t_ptr (-1 ends a walk)
+  unsigned* arrive = nullptr;         // arrival counter for that store: zero before the first launch, reset by the kernel
+  float* partial = nullptr;           // [T][B][3]: row t receives (sum (x0 - x0_hat)^2, sum (eps - eps_hat)^2, sum x0^2)
+};
+int launch_bound_terms(const BoundTermsArgs& a, hipStream_t st);
+
 // Langevin update of annealed_langevin_dynamics / consistent_langevin_dynamics (utils/ebm_utils.py:131-164, 231-253)
 struct LangevinStepArgs {
   float* x = nullptr;                 // [B][S][C] state, updated in place

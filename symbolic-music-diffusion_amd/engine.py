@@ -469,6 +469,14 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.L.smd_engine_strided_step(self.h, C.byref(io), C.byref(plan), int(part), _stream()), "strided_step")
 
+    def bound_step(self, io: "_lib.BoundIO") -> None:
+        """One iteration of the variational-bound walk: noise the examples to the level of the device timestep, eps-net
+        forward at that table row, the three per-example sums (include/smd_hip.h smd_engine_bound_step)."""
+        self._sync_fp8_weights()
+        self._join_pending()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.smd_engine_bound_step(self.h, C.byref(io), _stream()), "bound_step")
+
     @property
     def slot_table(self) -> torch.Tensor:
         return self._sched_tensors["slot"]

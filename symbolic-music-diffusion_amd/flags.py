@@ -263,6 +263,11 @@ ENGINE_FLAGS: List[FlagDef] = [
     _D("ddim_eta", "float", 0.0, "--ddim_steps: noise scale of the strided sampler, 0 = deterministic, 1 = the DDPM posterior's variance."),
     _D("ddim_encode", "bool", False, "--interpolate with --ddim_steps: encode starts and goals with the deterministic inversion of the "
        "strided sampler instead of the reference's single re-noising."),
+    _D("compute_bound", "bool", False, "sample_ncsn --sampling=ddpm: evaluate the variational bound of Ho et al. 2020 on the eval "
+       "examples, term by term, and write {sampling_dir}/ncsn/bound.json and bound_terms.pkl (DESIGN.md section 17)."),
+    _D("bound_steps", "int", 0, "--compute_bound: 0 = every timestep (the bound itself, in bits/dim), else the per-timestep terms at "
+       "2..num_sigmas evenly spaced timesteps only (the curve; no total)."),
+    _D("bound_only", "bool", False, "--compute_bound: stop after writing the bound (no sampling run)."),
     _D("ckpt_format", "enum", "safetensors", "Checkpoint file format written by train_ncsn: safetensors, or the "
        "reference's flax-0.3.0 msgpack state dict (both are recognised when restoring).", ("safetensors", "flax")),
     _D("rng_impl", "enum", "philox", "Random streams: the engine's fused Philox draws, or jax.random-compatible "

@@ -47,6 +47,12 @@ class StridePlan(C.Structure):
     _fields_ = [("coef", c_void), ("plan", c_void), ("T", c_i32)]
 
 
+class BoundIO(C.Structure):
+    _fields_ = [("x0", c_void), ("x_t", c_void), ("eps", c_void), ("t_ptr", c_void), ("table", c_void), ("next_t", c_void),
+                ("T", c_i32), ("clip", C.c_float), ("eps_source", c_i32), ("seed_lo", c_u32), ("seed_hi", c_u32),
+                ("sample_offset", c_u32), ("key_ptr", c_void), ("tf_keys", c_void), ("tf_n_total", c_i64), ("partial", c_void)]
+
+
 class LangevinIO(C.Structure):
     _fields_ = [("x", c_void), ("grad", c_void), ("alpha", C.c_float), ("noise_coef", C.c_float), ("z_in", c_void),
                 ("seed_lo", c_u32), ("seed_hi", c_u32), ("step", c_u32), ("sample_offset", c_u32), ("use_threefry", c_i32),
@@ -106,6 +112,11 @@ _SIGS = {
     "smd_engine_sample_step": (C.c_int, [c_void, C.POINTER(SampleIO), c_void]),
     "smd_engine_sample_step_part": (C.c_int, [c_void, C.POINTER(SampleIO), C.c_int, c_void]),
     "smd_engine_strided_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(StridePlan), C.c_int, c_void]),
+    "smd_engine_bound_step": (C.c_int, [c_void, C.POINTER(BoundIO), c_void]),
+    "smd_bound_noise": (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, C.c_int, c_u32, c_u32,
+                                  c_void, c_u32, c_void, c_void, c_void]),
+    "smd_bound_terms": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_float, c_void, c_void,
+                                  c_void, c_void, c_void]),
     "smd_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "smd_set_timestep": (C.c_int, [c_void, c_i32, c_void]),
     "smd_gemm_bf16_nt": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_int,

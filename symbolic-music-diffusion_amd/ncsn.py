@@ -6,6 +6,7 @@ Same names, argument meaning and error behaviour as the reference seam (SURVEY s
   diffusion_loss        utils/losses.py:250-308      reduce_fn        utils/losses.py:22-30
   diffusion_dynamics    utils/ebm_utils.py:280-405   collate_sampling_metrics  :408-428
   strided_dynamics / ddim_encode: the strided (DDIM) sampler and its inversion, no reference counterpart
+  variational_bound: the per-timestep variational bound on held-out examples, no reference counterpart
   sample                train_ncsn.py:499-551
 
 Every array computation runs in the HIP library (lib.py); this module only allocates tensors,
@@ -1067,6 +1068,94 @@ def ddim_encode(model: Model, betas, x0, steps, *, use_graph: bool = True):
     x, _, _ = _strided_walk("encode", PRNGKey(0), model, betas, x0, order, coef, plan, ("encode", len(order)), collect=False,
                             use_graph=use_graph, one_chain=True)
     return x
+
+
+def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip: float = 1.0, eps_in=None, sample_offset: int = 0,
+                      global_num_samples: Optional[int] = None, use_graph: bool = True) -> dict:
+    """The variational bound of Ho et al. 2020 (eq. 5) on the examples ``batch`` (model space), term by term: no reference
+    counterpart.  ``steps`` = 0: every timestep, the bound itself; else the terms at
+    ``schedule.stride_timesteps(T, steps)`` only -- the curve, no total (no stride estimates the sum honestly).  One eps-net
+    forward per (timestep, example) on one graph-replayed chain (smd_engine_bound_step); the kernels' fp32 sums are weighted
+    and added here in float64.  ``eps_in``: the draws, explicitly -- an array [K][N][...] in the order of ``timesteps``, or a
+    callable of t (eager launches).  Otherwise Philox keyed by (rng, global sample index, t), or with a ThreefryKey
+    ``normal(split(rng, T)[t], (N_global, ...))``, this rank's window starting at ``sample_offset``: sharded callers get the
+    single-process values.  Returns ``timesteps`` (ascending), ``terms`` / ``eps_mse`` [K][N] float64 (nats per example;
+    mean squared error of eps_hat), ``prior`` [N], ``total`` [N] or None, ``nats_per_dim`` / ``bits_per_dim`` (means over the
+    examples, or None) and ``var_0``.  The t = 0 term is a DENSITY of continuous latents, so it -- and the total -- is negative."""
+    eng = model.engine
+    dev = eng.device
+    x0 = torch.as_tensor(batch).to(dev, torch.float32).contiguous()
+    B = x0.shape[0]
+    if tuple(x0.shape[1:]) != eng.cfg.sample_shape:
+        raise ValueError(f"batch shape {tuple(x0.shape)} != (B, {eng.cfg.sample_shape})")
+    nT = len(betas)
+    steps = int(steps)
+    ts = np.arange(nT) if steps == 0 else _sched.stride_timesteps(nT, steps)
+    tab = _sched.bound_tables(betas, ts, clip)
+    order = [int(t) for t in tab["timesteps"]]
+    K = len(order)
+    per = int(np.prod(x0.shape[1:]))
+    explicit = eps_in is not None
+    jax_mode = isinstance(rng, ThreefryKey) and not explicit
+    graphed = use_graph and not explicit and K > 1
+    n_glob = (B + sample_offset if global_num_samples is None else int(global_num_samples)) * per
+    _ensure_schedule(eng, betas, with_sampler=True)
+    eng.bind(B, training=False)
+    sig = ((id(eng), eng.generation), _lib.tuning_epoch())
+    ckey = (tuple(order), float(clip), B, jax_mode, nT, int(sample_offset), int(n_glob), tuple(x0.shape[1:]))
+    cache = model.__dict__.setdefault("_sampler_graphs", {})
+    entry = cache.get("bound") if graphed else None
+    reuse = entry is not None and entry["key"] == ckey and entry["sig"] == sig
+    if reuse:
+        entry["x0"].copy_(x0)
+        entry["partial"].zero_()
+        entry["t_ptr"].fill_(order[0])
+    else:
+        if graphed:
+            cache.pop("bound", None)
+        # jax.random keys: one row per TIMESTEP, between two spare rows (smd_bound_io: rows -1 and T must be readable)
+        entry = dict(key=ckey, sig=sig, x0=x0.clone(), x_t=torch.zeros_like(x0), eps=torch.zeros_like(x0),
+                     partial=torch.zeros((nT, B, 3), dtype=torch.float32, device=dev),
+                     t_ptr=torch.tensor([order[0]], dtype=torch.int32, device=dev), pkey=torch.zeros(2, dtype=torch.int32, device=dev),
+                     table=torch.from_numpy(tab["table"]).to(dev), next_t=torch.from_numpy(tab["next_t"]).to(dev),
+                     tf_keys=torch.zeros((nT + 2, 2), dtype=torch.int32, device=dev) if jax_mode else None)
+        io = _lib.BoundIO()
+        io.x0, io.x_t, io.eps = entry["x0"].data_ptr(), entry["x_t"].data_ptr(), entry["eps"].data_ptr()
+        io.t_ptr, io.table, io.next_t = entry["t_ptr"].data_ptr(), entry["table"].data_ptr(), entry["next_t"].data_ptr()
+        io.T, io.clip = nT, float(clip)
+        io.eps_source = 0 if explicit else (1 if jax_mode else 2)
+        io.seed_lo = rng.seed & 0xFFFFFFFF; io.seed_hi = (rng.seed >> 32) & 0xFFFFFFFF
+        io.sample_offset = sample_offset
+        io.key_ptr = entry["pkey"].data_ptr()
+        if jax_mode:
+            io.tf_keys = entry["tf_keys"][1:].data_ptr()
+            io.tf_n_total = n_glob
+        io.partial = entry["partial"].data_ptr()
+        entry["io"] = io
+        entry["chains"] = [dict(eng=eng)]
+    entry["pkey"].copy_(torch.tensor([rng.seed & 0xFFFFFFFF, (rng.seed >> 32) & 0xFFFFFFFF], dtype=torch.int64).to(torch.int32))
+    if jax_mode:
+        keys = np.array([[k.k0, k.k1] for k in split(rng, nT)], dtype=np.uint32)
+        entry["tf_keys"][1:nT + 1].copy_(torch.from_numpy(keys.view(np.int32).copy()))
+    eng.refresh_weights()
+    eng.prepare_sampler()
+    eng.load_state(entry["x0"])            # zeroes the padding columns of the bf16 network input; the walk writes the rest
+    io = entry["io"]
+    step = lambda ch, part=0: ch["eng"].bound_step(io)
+    if explicit:
+        for k, t in enumerate(order):
+            e = eps_in(t) if callable(eps_in) else eps_in[k]
+            entry["eps"].copy_(torch.as_tensor(e).to(dev, torch.float32).reshape(x0.shape))
+            step(entry["chains"][0])
+    elif graphed:
+        _graph_walk(model, dev, entry["chains"], K - 1, 0, reuse, step)
+        if not reuse:
+            cache["bound"] = entry
+    else:
+        for _ in order:
+            step(entry["chains"][0])
+    sums = entry["partial"][torch.tensor(order, device=dev)].double().cpu().numpy()          # [K][B][3] (q, e, n)
+    return _sched.bound_from_sums(tab, sums, per)
 
 
 def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400, sampling="ald", epsilon=1e-3,

@@ -12,6 +12,8 @@ tensors out, launched on torch's current HIP stream; fake-tensor (meta) rules ar
   smd_amd::gemm_bf16_nt(a, bt, bias)                    nn.Dense, bf16 operands, fp32 accumulate -> bf16
   smd_amd::ddpm_reverse_step_(x, eps_hat, coef, t, ...) utils/ebm_utils.py:327-394, in place
   smd_amd::q_sample(x0, alphas_prod_ext, labels, eps)   utils/losses.py:271-296
+  smd_amd::bound_noise(x0, eps, table, t)               x_t of the variational bound at the device timestep t (DESIGN.md 17)
+  smd_amd::bound_terms(x0, eps, eps_hat, table, t, clip)   its three per-example sums [B][3]
 
 ``engine`` is the integer id of a live ``smd_amd.engine.Engine`` (``register_engine``); custom-op schemas carry tensors
 and scalars only.
@@ -181,3 +183,57 @@ def _(x0, alphas_prod_ext, labels, eps):
     B = x0.shape[0]
     rows = B if x0.dim() == 2 else B * x0.shape[1]
     return x0.new_empty((rows, x0.shape[-1]), dtype=torch.bfloat16), x0.new_empty((B,), dtype=torch.float32)
+
+
+def _bsc(x: torch.Tensor):
+    return (x.shape[0], 1, x.shape[1]) if x.dim() == 2 else tuple(x.shape)
+
+
+@torch.library.custom_op("smd_amd::bound_noise", mutates_args=())
+def bound_noise(x0: torch.Tensor, eps: torch.Tensor, table: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """x_t = sqrt(ap_t) x0 + sqrt(1-ap_t) eps at the device timestep ``t`` (int32[1]); ``table`` is schedule.bound_tables' [T][4]
+    float32 table.  ``t`` outside [0, T) leaves the result zero."""
+    _need_gpu(x0, eps, table, t)
+    if x0.dtype != torch.float32 or eps.dtype != torch.float32 or eps.shape != x0.shape or x0.dim() not in (2, 3):
+        raise ValueError("bound_noise: x0, eps fp32 (B, S, C) or (B, C) tensors of one shape")
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 4 or t.dtype != torch.int32:
+        raise ValueError("bound_noise: table fp32 [T][4], t int32[1]")
+    x0, eps, table = x0.contiguous(), eps.contiguous(), table.contiguous()
+    B, S, Cn = _bsc(x0)
+    xt = torch.zeros_like(x0)
+    with torch.cuda.device(x0.device):
+        _lib.check(_lib.get_lib().smd_bound_noise(x0.data_ptr(), B, S, Cn, Cn, table.data_ptr(), table.shape[0], t.data_ptr(),
+                                                  eps.data_ptr(), 0, 0, 0, None, 0, xt.data_ptr(), None, _stream()), "bound_noise")
+    return xt
+
+
+@bound_noise.register_fake
+def _(x0, eps, table, t):
+    return torch.empty_like(x0)
+
+
+@torch.library.custom_op("smd_amd::bound_terms", mutates_args=())
+def bound_terms(x0: torch.Tensor, eps: torch.Tensor, eps_hat: torch.Tensor, table: torch.Tensor, t: torch.Tensor,
+                clip: float) -> torch.Tensor:
+    """[B][3] = per-example (sum (x0 - x0_hat)^2, sum (eps - eps_hat)^2, sum x0^2) at the device timestep ``t`` (int32[1], left
+    as it is); ``t`` outside [0, T) leaves the result zero."""
+    _need_gpu(x0, eps, eps_hat, table, t)
+    if x0.dtype != torch.float32 or eps.shape != x0.shape or eps_hat.shape != x0.shape or x0.dim() not in (2, 3):
+        raise ValueError("bound_terms: x0, eps, eps_hat fp32 (B, S, C) or (B, C) tensors of one shape")
+    if eps.dtype != torch.float32 or eps_hat.dtype != torch.float32:
+        raise ValueError("bound_terms: eps, eps_hat fp32")
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 4 or t.dtype != torch.int32:
+        raise ValueError("bound_terms: table fp32 [T][4], t int32[1]")
+    x0, eps, eps_hat, table = x0.contiguous(), eps.contiguous(), eps_hat.contiguous(), table.contiguous()
+    B, S, Cn = _bsc(x0)
+    T = table.shape[0]
+    partial = torch.zeros((T, B, 3), dtype=torch.float32, device=x0.device)
+    with torch.cuda.device(x0.device):
+        _lib.check(_lib.get_lib().smd_bound_terms(x0.data_ptr(), eps.data_ptr(), eps_hat.data_ptr(), B, S, Cn, table.data_ptr(), T,
+                                                  float(clip), t.data_ptr(), None, None, partial.data_ptr(), _stream()), "bound_terms")
+    return partial.sum(dim=0)
+
+
+@bound_terms.register_fake
+def _(x0, eps, eps_hat, table, t, clip):
+    return x0.new_empty((x0.shape[0], 3), dtype=torch.float32)

@@ -134,3 +134,59 @@ def inversion_coefficient_table(betas: np.ndarray, taus):
               sqrt_1m_as=np.sqrt(1 - ap[s_]))
     n = len(t_)
     return _walk_tables(betas, asc[:-1], co, asc[1:-1] + [len(betas)], [-1] * n, np.inf)
+
+
+# ------------------------------------------------------------------ variational bound
+def bound_tables(betas: np.ndarray, timesteps, clip: float = 1.0) -> dict:
+    """Everything the per-timestep variational bound (Ho et al. 2020, eq. 5) needs from the schedule, for the timesteps
+    ``timesteps`` -- all of [0, T), or ``stride_timesteps(T, K)`` -- in any order; they are walked ascending.  Built in float64
+    from the float32 ``alphas_cumprod`` (as the strided tables are), with ap_prev[0] = 1, and rounded once:
+
+      w [T] float64          L_t = w_t * sum (x0 - x0_hat)^2 for t >= 1, w_t = mu1_t^2 / (2 bt_t); w[0] = 1 / (2 var_0)
+      var_0                  the decoder's variance, bt_1 (the reference's posterior variance at t = 0 is 0)
+      decoder_const          (D / 2) log(2 pi var_0) per DIMENSION, i.e. 0.5 log(2 pi var_0): multiply by D
+      prior_a, prior_c       L_T = 0.5 (prior_a * sum x0^2 + D * prior_c), prior_a = ap_{T-1}, prior_c = -ap_{T-1} - log(1 - ap_{T-1})
+      table [T][4] float32   (sqrt(ap), sqrt(1-ap), sqrt(1/ap), sqrt(1/ap - 1)): the kernels' rows
+      next_t [T] int32       the ascending walk: next_t[t] = the next timestep, -1 after the last and for timesteps off the walk
+      timesteps              the walk, ascending (int64);  clip is passed through
+    """
+    betas64 = np.asarray(betas, dtype=np.float32).astype(np.float64)
+    T = len(betas64)
+    ts = np.unique(np.asarray(timesteps, dtype=np.int64))
+    if len(ts) == 0 or ts[0] < 0 or ts[-1] >= T:
+        raise ValueError(f"bound_tables: timesteps must lie in [0, {T})")
+    if not float(clip) > 0:
+        raise ValueError(f"bound_tables: clip={clip} must be positive (inf: no clamp)")
+    ap = alphas_cumprod(betas).astype(np.float64)
+    ap_prev = np.concatenate([np.ones(1), ap[:-1]])
+    bt = betas64 * (1 - ap_prev) / (1 - ap)                       # posterior variance; bt[0] = 0
+    mu1 = betas64 * np.sqrt(ap_prev) / (1 - ap)
+    var_0 = float(bt[1]) if T > 1 else float(betas64[0])
+    w = np.empty(T, dtype=np.float64)
+    w[1:] = mu1[1:] ** 2 / (2 * bt[1:])
+    w[0] = 1.0 / (2 * var_0)
+    table = np.stack([np.sqrt(ap), np.sqrt(1 - ap), np.sqrt(1 / ap), np.sqrt(1 / ap - 1)], axis=1)
+    next_t = np.full((T,), -1, dtype=np.int32)
+    next_t[ts[:-1]] = ts[1:]
+    return dict(w=w, var_0=var_0, decoder_const=0.5 * np.log(2 * np.pi * var_0), prior_a=float(ap[-1]),
+                prior_c=float(-ap[-1] - np.log(1 - ap[-1])), table=np.ascontiguousarray(table.astype(np.float32)),
+                next_t=next_t, timesteps=ts, clip=float(clip))
+
+
+def bound_from_sums(tab: dict, sums: np.ndarray, D: int) -> dict:
+    """The bound from the kernels' per-example sums: ``sums`` [K][N][3] = (sum (x0 - x0_hat)^2, sum (eps - eps_hat)^2, sum x0^2)
+    for the K ascending timesteps of ``tab`` (bound_tables), D = S * C.  Weighted and added in float64:
+    L_t = w_t q_t (+ D * decoder_const at t = 0), L_T = 0.5 (prior_a n + D prior_c), total = L_T + sum_t L_t -- only when the
+    walk covers every timestep; a sub-sequence gives ``total`` (and the per-dimension scalars) None, never an interpolation."""
+    ts = np.asarray(tab["timesteps"], dtype=np.int64)
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.ndim != 3 or sums.shape[0] != len(ts) or sums.shape[2] != 3:
+        raise ValueError(f"bound_from_sums: sums of shape {sums.shape} for {len(ts)} timesteps")
+    terms = tab["w"][ts][:, None] * sums[:, :, 0]
+    if ts[0] == 0:
+        terms[0] += D * tab["decoder_const"]
+    prior = 0.5 * (tab["prior_a"] * sums[0, :, 2] + D * tab["prior_c"])
+    total = prior + terms.sum(axis=0) if len(ts) == len(tab["w"]) else None
+    return dict(timesteps=ts, terms=terms, eps_mse=sums[:, :, 1] / D, prior=prior, total=total,
+                nats_per_dim=None if total is None else float(total.mean() / D),
+                bits_per_dim=None if total is None else float(total.mean() / (D * np.log(2.0))), var_0=tab["var_0"])
