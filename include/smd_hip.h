@@ -423,6 +423,18 @@ int smd_layernorm_bwd_film(const float* x, const smd_bf16* x_bf16, int rows, int
                            const smd_bf16* dout, const float* dres, const smd_bf16* dres_bf16, float* dx,
                            smd_bf16* dx_bf16, float* dgamma, float* dbeta, float* dscale, float* dshift,
                            int dfilm_accumulate, float* partial, int64_t partial_elems, void* stream);
+/* ... and with saved row statistics, as the engine's training step runs its output-stage LayerNorms: smd_layernorm_fwd_stats is smd_layernorm_fwd_ex / _fwd_e4m3 in one call (out and/or out8 + out_scale)
+ * that also writes (mean, rstd) of every row to stats_out, fp32 [rows][2], when it is non-NULL; smd_layernorm_bwd_stats is
+ * smd_layernorm_bwd_film reading those statistics instead of recomputing them (D = 2048 8-wave kernel; every other kernel and a
+ * NULL pointer recompute them from x). */
+int smd_layernorm_fwd_stats(const float* x, const smd_bf16* x_bf16, int rows, int D, const float* gamma, const float* beta,
+                            const float* film_scale, const float* film_shift, int ld_film, int rows_per_sample, int swish,
+                            smd_bf16* out, uint8_t* out8, uint32_t* out_scale, float* stats_out, void* stream);
+int smd_layernorm_bwd_stats(const float* x, const smd_bf16* x_bf16, int rows, int D, const float* gamma, const float* beta,
+                            const float* film_scale, const float* film_shift, int ld_film, int rows_per_sample, int swish,
+                            const smd_bf16* dout, const float* dres, const smd_bf16* dres_bf16, float* dx,
+                            smd_bf16* dx_bf16, float* dgamma, float* dbeta, float* dscale, float* dshift,
+                            int dfilm_accumulate, float* partial, int64_t partial_elems, const float* stats, void* stream);
 int smd_attention_fwd(const smd_bf16* qkv, smd_bf16* out, int B, int S, int E, int H, void* stream);
 int smd_attention_bwd(const smd_bf16* qkv, const smd_bf16* dout, smd_bf16* dqkv, int B, int S, int E, int H,
                       void* stream);

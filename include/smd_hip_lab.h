@@ -20,7 +20,8 @@ int smd_engine_debug_snapshots(smd_engine* e, void* buf, int64_t bytes);
 
 /* Debugging aid (layer-by-layer parity): device pointer, shape and element type (0 fp32, 1 bf16) of an activation the training
  * forward pass saved in the bound workspace: "x_bf16", "h"/"h_mid"/"a1"/"qkv"/"o"/"a2" [encoder layer], "h_last", "af",
- * "y" [0..K], "ya1"/"o1"/"ya2"/"f1"/"p"/"ss" [block], "emb", "ao", "pred", "s"; and of the last backward pass the operands of
+ * "y" [0..K], "ya1"/"o1"/"ya2"/"f1"/"p"/"ss" [block], "emb", "ao", "pred", "s", "ln_stats" [0..2K: the saved (mean, rstd) rows of
+ * ln1 / ln2 of block k at 2k / 2k + 1 and of the output norm at 2K]; and of the last backward pass the operands of
  * every weight-gradient GEMM: "dpred", "dyb" [0..K], "do1"/"dss"/"dss_bf16"/"dp"/"df1"/"zf1" [block], "dhb" [0..2L], "dqkv"/"dz1"/"u" [encoder
  * layer].  Valid until the next call on the handle. */
 int smd_engine_debug_tensor(const smd_engine* e, const char* name, int index, const void** ptr, int64_t* rows, int64_t* cols,

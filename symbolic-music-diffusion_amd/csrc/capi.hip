@@ -91,6 +91,7 @@ int smd_engine_set_option(smd_engine* e, const char* key, int value) {
   if (std::string(key) == "side_wgrad") return e->impl.set_side_stream(value);
   if (std::string(key) == "fused_attn_bwd") { e->impl.fused_attn_bwd = value < 0 ? 0 : (value > 2 ? 2 : value); return 0; }
   if (std::string(key) == "resgrad_bf16") { e->impl.resgrad_bf16 = value ? 1 : 0; return 0; }
+  if (std::string(key) == "ln_saved_stats") { e->impl.ln_saved_stats = value ? 1 : 0; return 0; }
   if (std::string(key) == "film_side") { e->impl.film_side = value; return 0; }
   if (std::string(key) == "pair_wgrad") { e->impl.pair_wgrad = value ? 1 : 0; return 0; }
   if (std::string(key) == "wgrad256_group") { e->impl.wgrad256_group = value < 1 ? 1 : (value > 4 ? 4 : value); return 0; }
@@ -386,6 +387,29 @@ int smd_layernorm_bwd_film(const float* x, const smd_bf16* x_bf16, int rows, int
   b.dout = B(dout); b.dres = dres; b.dres_bf16 = B(dres_bf16); b.dx = dx; b.dx_bf16 = B(dx_bf16);
   b.dgamma = dgamma; b.dbeta = dbeta; b.dscale = dscale; b.dshift = dshift; b.dfilm_accumulate = dfilm_accumulate;
   b.partial = partial; b.partial_elems = (size_t)partial_elems;
+  return launch_layernorm_bwd(b, S(stream));
+}
+int smd_layernorm_fwd_stats(const float* x, const smd_bf16* x_bf16, int rows, int D, const float* gamma, const float* beta,
+                            const float* film_scale, const float* film_shift, int ld_film, int rows_per_sample, int swish,
+                            smd_bf16* out, uint8_t* out8, uint32_t* out_scale, float* stats_out, void* stream) {
+  LnArgs a;
+  a.x = x; a.x_bf16 = B(x_bf16); a.rows = rows; a.D = D; a.gamma = gamma; a.beta = beta; a.film_scale = film_scale;
+  a.film_shift = film_shift; a.ld_film = ld_film; a.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1; a.swish = swish;
+  a.out = B(out); a.out_f8 = out8; a.out_scale = out_scale; a.stats_out = stats_out;
+  return launch_layernorm_fwd(a, S(stream));
+}
+int smd_layernorm_bwd_stats(const float* x, const smd_bf16* x_bf16, int rows, int D, const float* gamma, const float* beta,
+                            const float* film_scale, const float* film_shift, int ld_film, int rows_per_sample, int swish,
+                            const smd_bf16* dout, const float* dres, const smd_bf16* dres_bf16, float* dx,
+                            smd_bf16* dx_bf16, float* dgamma, float* dbeta, float* dscale, float* dshift,
+                            int dfilm_accumulate, float* partial, int64_t partial_elems, const float* stats, void* stream) {
+  LnBwdArgs b;
+  b.f.x = x; b.f.x_bf16 = B(x_bf16); b.f.rows = rows; b.f.D = D; b.f.gamma = gamma; b.f.beta = beta;
+  b.f.film_scale = film_scale; b.f.film_shift = film_shift; b.f.ld_film = ld_film; b.f.rows_per_sample = rows_per_sample;
+  b.f.swish = swish;
+  b.dout = B(dout); b.dres = dres; b.dres_bf16 = B(dres_bf16); b.dx = dx; b.dx_bf16 = B(dx_bf16);
+  b.dgamma = dgamma; b.dbeta = dbeta; b.dscale = dscale; b.dshift = dshift; b.dfilm_accumulate = dfilm_accumulate;
+  b.partial = partial; b.partial_elems = (size_t)partial_elems; b.stats = stats;
   return launch_layernorm_bwd(b, S(stream));
 }
 int smd_attention_fwd(const smd_bf16* qkv, smd_bf16* out, int Bn, int Sn, int E, int H, void* stream) {

@@ -214,6 +214,7 @@ class SmdEngine {
   int fused_attn_bwd = 2;                                     // attn_block_bwd kernel: 2 = with the LayerNorm backwards either side of it in the
                                                               // launch (hidden-split dataflow), 1 = attention only, 0 = three separate launches
   int resgrad_bf16 = 1;   // ResBlock residual-gradient chain kept in bf16 (the GEMM operand copy) instead of fp32 + bf16
+  int ln_saved_stats = 1; // the training forward saves (mean, rstd) of every output-stage LayerNorm row for its backward (0: recomputed)
   int fused_encoder = 1;                                      // encoder_fused.hip half-layer kernels (0: separate launches)
   int side_wgrad = 0;
   // e4m3 (OCP fp8) operands with per-row E8M0 scales for the DenseResBlock GEMMs of the FORWARD pass (77 % of its flops),
@@ -253,6 +254,7 @@ class SmdEngine {
   int flush_pending256(hipStream_t st);
   std::vector<LnReduceEntry> ln_pending_;
   size_t ln_slot_off_ = 0;
+  bool ln_stats_valid_ = false;   // the last training forward filled W.ln_stats
   float* P(int64_t off) const { return params_ + off; }
   float* G(int64_t off) const { return grads_ + off; }
 
@@ -343,6 +345,7 @@ class SmdEngine {
     std::vector<bf16_t*> dss_bf16;        // [K] x [B][2M]
     std::vector<bf16_t*> dp;              // [K] x [B][4F]
     std::vector<bf16_t*> df1;             // [K] x [B][4F]
+    std::vector<float*> ln_stats;   // training: (mean, rstd) fp32 [rows][2] of ln1 / ln2 of block k at 2k / 2k + 1, ln_o at 2K
     float* ln_partial = nullptr;
     size_t ln_partial_elems = 0;
     float* tn_slab = nullptr;             // split-K partial tiles of the wgrad kernel (main stream)

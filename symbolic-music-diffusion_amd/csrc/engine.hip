@@ -374,6 +374,8 @@ int64_t SmdEngine::plan(void* base, int batch, int training, Work* w) const {
       t.ln_partial_elems = (size_t)(2 * K + 1) * groups * 2 * M + (size_t)(L > 0 ? 2 * L + 1 : 0) * groups * 2 * E + 2 * (size_t)M;
     }
     t.ln_partial = c.take<float>(t.ln_partial_elems);
+    t.ln_stats.resize(2 * K + 1);
+    for (auto& p : t.ln_stats) p = c.take<float>(R * 2);
     t.tn_slab_elems = gemm_tn_slab_elems();
     t.tn_slab = c.take<float>(t.tn_slab_elems);
     t.tn_slab_side = c.take<float>(t.tn_slab_elems);
@@ -422,6 +424,7 @@ int SmdEngine::bind_workspace(void* ws, int64_t bytes, int batch, int training, 
   RC(join_update(st));                     // a deferred update reads the optimiser constants of the OLD workspace
   plan(ws, batch, training, &W);
   batch_ = batch; training_ = training;
+  ln_stats_valid_ = false;
   w8_dirty_ = true;
   hipError_t e = hipMemsetAsync(ws, 0, (size_t)need, st);   // zero pads / zero page / padded operand columns
   if (e != hipSuccess) { smd_set_error("bind_workspace: memset: %s", hipGetErrorString(e)); return (int)e; }
@@ -651,6 +654,9 @@ int SmdEngine::run_network(const int* t_ptr, hipStream_t st, int part, const flo
     if (e != hipSuccess) { smd_set_error("run_network: event: %s", hipGetErrorString(e)); return (int)e; }
   }
   const bool f8 = fp8 && W.w8 && R % 256 == 0 && M % 256 == 0 && (M == 1024 || M == 2048);
+  // training: every output-stage LayerNorm saves its row statistics for backward_head (inference and the sampler store nothing)
+  const bool save_stats = tr && ln_saved_stats && (int)W.ln_stats.size() == 2 * K + 1;
+  if (tr) ln_stats_valid_ = save_stats;
   if (f8 && w8_dirty_) {           // e4m3 copies of the ResBlock weights (per output row), once per weight refresh
     for (int k = 0; k < K; ++k) {
       const FilmResP& b = blk_[k];
@@ -690,6 +696,7 @@ int SmdEngine::run_network(const int* t_ptr, hipStream_t st, int part, const flo
     LnArgs ln;
     ln.rows = R; ln.D = M; ln.film_scale = scale; ln.film_shift = scale + M; ln.ld_film = ld_film;
     ln.rows_per_sample = S; ln.t_ptr = t_ptr; ln.film_rows = d_.num_timesteps; ln.swish = 1;
+    auto stats = [&](int hb) { return save_stats ? W.ln_stats[hb] : nullptr; };
     if (f8) {
       // e4m3 forward GEMMs: the LayerNorm writes the A operand as e4m3 + row scales (and, when training, the bf16 copy
       // the weight gradient contracts), the weights were quantised per output row above
@@ -697,14 +704,14 @@ int SmdEngine::run_network(const int* t_ptr, hipStream_t st, int part, const flo
       if (runs_hb(2 * k)) {
         if (tb) { ln.x = nullptr; ln.x_bf16 = ybk(k); } else ln.x = y_in;
         ln.gamma = P(b.ln1.g_off); ln.beta = P(b.ln1.b_off);
-        ln.out = tr ? W.ya1[i] : nullptr; ln.out_f8 = W.ya1_f8[i]; ln.out_scale = W.sa1[i];
+        ln.out = tr ? W.ya1[i] : nullptr; ln.out_f8 = W.ya1_f8[i]; ln.out_scale = W.sa1[i]; ln.stats_out = stats(2 * k);
         RC(launch_layernorm_fwd(ln, st));
         { GemmEpilogue ep; ep.bias = P(b.r1.b_off); ep.out_bf16 = W.o1[i]; ep.ld_outb = M;
           RC(launch_gemm_nt256_fp8(W.ya1_f8[i], M, W.sa1[i], W.w8 + wo, M, W.w8s + so, R, M, M, ep, st)); }
       }
       if (runs_hb(2 * k + 1)) {
         ln.x = nullptr; ln.x_bf16 = W.o1[i]; ln.gamma = P(b.ln2.g_off); ln.beta = P(b.ln2.b_off);
-        ln.out = tr ? W.ya2[i] : nullptr; ln.out_f8 = W.ya2_f8[i]; ln.out_scale = W.sa2[i];
+        ln.out = tr ? W.ya2[i] : nullptr; ln.out_f8 = W.ya2_f8[i]; ln.out_scale = W.sa2[i]; ln.stats_out = stats(2 * k + 1);
         RC(launch_layernorm_fwd(ln, st));
         { GemmEpilogue ep; ep.bias = P(b.r2.b_off);
           if (tb) { ep.res_bf16 = ybk(k); ep.ld_resb = M; ep.out_bf16 = ybk(k + 1); ep.ld_outb = M; }
@@ -715,12 +722,13 @@ int SmdEngine::run_network(const int* t_ptr, hipStream_t st, int part, const flo
     }
     if (runs_hb(2 * k)) {
       if (tb) { ln.x = nullptr; ln.x_bf16 = ybk(k); } else ln.x = y_in;
-      ln.gamma = P(b.ln1.g_off); ln.beta = P(b.ln1.b_off); ln.out = W.ya1[i];
+      ln.gamma = P(b.ln1.g_off); ln.beta = P(b.ln1.b_off); ln.out = W.ya1[i]; ln.stats_out = stats(2 * k);
       RC(launch_layernorm_fwd(ln, st));
       { GemmEpilogue ep; ep.out_bf16 = W.o1[i]; ep.ld_outb = M; RC(dense_fwd(b.r1, W.ya1[i], M, R, ep, st)); }
     }
     if (runs_hb(2 * k + 1)) {
       ln.x = nullptr; ln.x_bf16 = W.o1[i]; ln.gamma = P(b.ln2.g_off); ln.beta = P(b.ln2.b_off); ln.out = W.ya2[i];
+      ln.stats_out = stats(2 * k + 1);
       RC(launch_layernorm_fwd(ln, st));
       { GemmEpilogue ep;
         if (tb) { ep.res_bf16 = ybk(k); ep.ld_resb = M; ep.out_bf16 = ybk(k + 1); ep.ld_outb = M; }
@@ -733,7 +741,7 @@ int SmdEngine::run_network(const int* t_ptr, hipStream_t st, int part, const flo
     LnArgs ln;
     if (tb) ln.x_bf16 = ybk(K); else ln.x = tr ? W.y[K] : W.y[0];
     ln.rows = R; ln.D = M; ln.gamma = P(ln_o_.g_off); ln.beta = P(ln_o_.b_off);
-    ln.out = W.ao;
+    ln.out = W.ao; ln.stats_out = save_stats ? W.ln_stats[2 * K] : nullptr;
     RC(launch_layernorm_fwd(ln, st));
     GemmEpilogue ep; ep.out_f32 = W.pred; ep.ld_out = C;
     RC(dense_fwd(out_proj_, W.ao, M, R, ep, st));
@@ -898,6 +906,7 @@ int SmdEngine::backward_head(hipStream_t st) {
     const bool tbk = trunk_bf16_on();
     b.f = tbk ? ln_args(nullptr, reinterpret_cast<bf16_t*>(W.y[K]), R, ln_o_, params_) : ln_args(W.y[K], nullptr, R, ln_o_, params_);
     b.dout = W.dA_M; b.dx = use_bf16_chain ? nullptr : W.dy; b.dx_bf16 = W.dyb[K];
+    if (ln_stats_valid_) b.stats = W.ln_stats[2 * K];
     b.dgamma = G(ln_o_.g_off); b.dbeta = G(ln_o_.b_off);
     RC(ln_bwd(b, st));
   }
@@ -923,6 +932,7 @@ int SmdEngine::backward_head(hipStream_t st) {
       b.f.film_scale = W.ss[k]; b.f.film_shift = W.ss[k] + M; b.f.ld_film = 2 * M; b.f.rows_per_sample = S;
       b.f.swish = 1;
       b.dout = W.dA_M; b.dx_bf16 = W.do1[k];
+      if (ln_stats_valid_) b.stats = W.ln_stats[2 * k + 1];
       b.dgamma = G(p.ln2.g_off); b.dbeta = G(p.ln2.b_off);
       b.dscale = W.dss[k]; b.dshift = W.dss[k] + M; b.dfilm_accumulate = 0;
       RC(ln_bwd(b, st));
@@ -936,6 +946,7 @@ int SmdEngine::backward_head(hipStream_t st) {
       b.f.film_scale = W.ss[k]; b.f.film_shift = W.ss[k] + M; b.f.ld_film = 2 * M; b.f.rows_per_sample = S;
       b.f.swish = 1;
       b.dout = W.dA_M; b.dx_bf16 = W.dyb[k];
+      if (ln_stats_valid_) b.stats = W.ln_stats[2 * k];
       if (use_bf16_chain) b.dres_bf16 = W.dyb[k + 1];          // y[k+1] = y[k] + block(y[k]): dy[k] = dy[k+1] + ...
       else { b.dres = W.dy; b.dx = W.dy; }
       b.dgamma = G(p.ln1.g_off); b.dbeta = G(p.ln1.b_off);
@@ -1007,6 +1018,7 @@ int SmdEngine::debug_tensor(const char* name, int index, const void** ptr, int64
   if (n == "f1" && layer(K)) return set(W.f1[index], B, 4 * F, 1);
   if (n == "p" && layer(K)) return set(W.p[index], B, 4 * F, 1);
   if (n == "ss" && layer(K)) return set(W.ss[index], B, 2 * M, 0);
+  if (n == "ln_stats" && layer(2 * K + 1) && (int)W.ln_stats.size() == 2 * K + 1) return set(W.ln_stats[index], R, 2, 0);
   // gradient activations of the last loss_backward: every dY / X operand of a weight-gradient GEMM has its own slot (the side
   // stream reads them late), so each weight gradient can be re-derived from exactly the operands the engine used
   if (n == "dpred") return set(W.dpred, R, Cp_, 1);

@@ -113,6 +113,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(LnArgs a) {
   load_vec<D>(a.beta, lane, b);
   float mean, rstd;
   row_stats<D>(x, mean, rstd);
+  if (a.stats_out && lane == 0) *reinterpret_cast<float2*>(a.stats_out + (size_t)row * 2) = make_float2(mean, rstd);
   float y[L::PER_LANE];
 #pragma unroll
   for (int i = 0; i < L::PER_LANE; ++i) y[i] = (x[i] - mean) * rstd * g[i] + b[i];
@@ -147,13 +148,16 @@ template <int D, bool XBF> struct WideRow {
 // shift) from the L2 for every row -- 4x the bytes of the row itself.  Here a workgroup of 8 waves owns one row group
 // (a sample's rows with per-sample FiLM, else 32 rows), keeps the parameters in LDS and walks the group's rows
 // (SGPR row bases, all of a row's loads issued up front).  FS: FiLM + swish (ResBlock norms) or neither.
+// A group's rows share one FiLM row, so the two affine maps are folded once per workgroup: the LDS holds A = scale * gamma
+// and C = scale * beta + shift (gamma and beta without FiLM), and an element costs xhat = x * rstd - mean * rstd (one FMA,
+// the offset hoisted per row) and xhat * A + C (one more).  stats_out: lane 0 also saves the row's (mean, rstd).
 // F8: also (or only) write the row as e4m3 with a per-row E8M0 scale (the A operand of the e4m3 GEMM); the row's outputs
 // then wait in registers for the row maximum.
 template <int D, bool XBF, bool FS, int NW, bool F8 = false, bool PF = false>
 __global__ __launch_bounds__(64 * NW) void layernorm_fwd_wide_kernel(LnArgs a, int group_rows) {
   typedef RowLayout<D> L;
   constexpr int NV = L::NV;
-  __shared__ __attribute__((aligned(16))) float prm[FS ? 4 : 2][D];
+  __shared__ __attribute__((aligned(16))) float prm[2][D];      // A, C
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r_begin = blockIdx.x * group_rows;
@@ -161,12 +165,20 @@ __global__ __launch_bounds__(64 * NW) void layernorm_fwd_wide_kernel(LnArgs a, i
   r_end = r_end < a.rows ? r_end : a.rows;
   {
     const int frow = FS ? (a.t_ptr ? smd_clamp_t(*a.t_ptr, a.film_rows) : r_begin / a.rows_per_sample) : 0;
-    const float* src[4] = {a.gamma, a.beta, FS ? a.film_scale + (size_t)frow * a.ld_film : nullptr,
-                           FS ? a.film_shift + (size_t)frow * a.ld_film : nullptr};
-#pragma unroll
-    for (int q = 0; q < (FS ? 4 : 2); ++q)
-      for (int c = threadIdx.x * 4; c < D; c += 256 * NW)
-        *reinterpret_cast<float4*>(&prm[q][c]) = *reinterpret_cast<const float4*>(src[q] + c);
+    const float* fsc = FS ? a.film_scale + (size_t)frow * a.ld_film : nullptr;
+    const float* fsh = FS ? a.film_shift + (size_t)frow * a.ld_film : nullptr;
+    for (int c = threadIdx.x * 4; c < D; c += 256 * NW) {
+      float4 pa = *reinterpret_cast<const float4*>(a.gamma + c);
+      float4 pc = *reinterpret_cast<const float4*>(a.beta + c);
+      if constexpr (FS) {
+        const float4 s4 = *reinterpret_cast<const float4*>(fsc + c);
+        const float4 h4 = *reinterpret_cast<const float4*>(fsh + c);
+        pa = make_float4(s4.x * pa.x, s4.y * pa.y, s4.z * pa.z, s4.w * pa.w);
+        pc = make_float4(fmaf(s4.x, pc.x, h4.x), fmaf(s4.y, pc.y, h4.y), fmaf(s4.z, pc.z, h4.z), fmaf(s4.w, pc.w, h4.w));
+      }
+      *reinterpret_cast<float4*>(&prm[0][c]) = pa;
+      *reinterpret_cast<float4*>(&prm[1][c]) = pc;
+    }
   }
   __syncthreads();
   const uint32_t l4 = lane * 4;
@@ -200,24 +212,22 @@ __global__ __launch_bounds__(64 * NW) void layernorm_fwd_wide_kernel(LnArgs a, i
     sq = wave_sum(sq);
     const float mean = s * (1.0f / D);
     const float rstd = smd_ln_rstd(sq * (1.0f / D) - mean * mean + LN_EPS);
+    const float nmr = -mean * rstd;
+    if (a.stats_out && lane == 0) *reinterpret_cast<float2*>(a.stats_out + (size_t)row * 2) = make_float2(mean, rstd);
     bf16_t* orow = a.out + (size_t)row * D;
     float yk[F8 ? NV : 1][4];
     float amax = 0.f;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int c = k * 256 + lane * 4;
-      const float4 g4 = *reinterpret_cast<const float4*>(&prm[0][c]);
-      const float4 b4 = *reinterpret_cast<const float4*>(&prm[1][c]);
-      const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
+      const float4 a4 = *reinterpret_cast<const float4*>(&prm[0][c]);
+      const float4 c4 = *reinterpret_cast<const float4*>(&prm[1][c]);
+      const float pa[4] = {a4.x, a4.y, a4.z, a4.w}, pc[4] = {c4.x, c4.y, c4.z, c4.w};
       float y[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) y[e] = (b.x(k, e) - mean) * rstd * gg[e] + bb[e];
-      if constexpr (FS) {
-        const float4 s4 = *reinterpret_cast<const float4*>(&prm[2][c]);
-        const float4 h4 = *reinterpret_cast<const float4*>(&prm[3][c]);
-        const float ss[4] = {s4.x, s4.y, s4.z, s4.w}, hh[4] = {h4.x, h4.y, h4.z, h4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = swishf_(ss[e] * y[e] + hh[e]);
+      for (int e = 0; e < 4; ++e) {
+        y[e] = fmaf(fmaf(b.x(k, e), rstd, nmr), pa[e], pc[e]);
+        if constexpr (FS) y[e] = swishf_(y[e]);
       }
       if (!F8 || a.out) {
         bf16x4_t t;
@@ -251,6 +261,7 @@ struct LnBwdDev {
   const bf16_t* dout;
   const float* dres;      // optional fp32 residual gradient added to dx (may alias dx_f32)
   const bf16_t* dres_bf16; // or the same in bf16 (wide8 kernel only; may alias dx_bf16)
+  const float* stats;     // (mean, rstd) [rows][2] saved by the forward (wide8 kernel only), or null: recomputed
   float* dx_f32;
   bf16_t* dx_bf16;
   float* dscale;
@@ -492,14 +503,21 @@ __global__ __launch_bounds__(256, 2) void layernorm_bwd_wide_kernel(LnBwdDev a) 
 //   * 8 waves share a row group (2 per SIMD), each walks rows w, w+8, ...;
 //   * all of a row's loads (x, dy, residual gradient) are issued up front and stay raw in registers (converted at
 //     use), xhat is recomputed from raw x in the dx pass, the row bases live in SGPRs;
-//   * the residual gradient may be bf16 (RM = 2): the engine keeps the ResBlock residual-gradient chain in bf16.
+//   * the residual gradient may be bf16 (RM = 2): the engine keeps the ResBlock residual-gradient chain in bf16;
+//   * arithmetic the result does not need is left out: with a.stats the row's (mean, rstd) are the two floats the forward
+//     saved (no statistics pass, no wave reductions, no v_rsq, one conversion pass of a bf16 row fewer); a group's rows share
+//     one FiLM row, so the LDS holds A = scale * gamma and C = scale * beta + shift: the pre-activation is xhat * A + C and
+//     dxhat = e * A (gamma, beta and scale are read from global memory once per column for the epilogue); xhat is one FMA,
+//     x * rstd - mean * rstd, with the offset hoisted per row.
 
 template <int D, bool XBF, int RM, bool FS, int OM>   // FS: FiLM + swish (the ResBlock norms) or neither (plain
 __global__ __launch_bounds__(512) void layernorm_bwd_wide8_kernel(LnBwdDev a) {   // LayerNorm); OM: 1 fp32 dx, 2 bf16, 3 both
   typedef RowLayout<D> L;
   constexpr int PL = L::PER_LANE, NV = L::NV, NW = 8;
   constexpr bool film = FS, swish = FS;
-  __shared__ __attribute__((aligned(16))) float prm[4][D];      // gamma, beta, scale, shift; later the combine buffer
+  // A and C in rows 0 / 1 during the row loop (C only with FiLM); all four rows, 32 KiB, only for the 4-wave combine below, whose first
+  // write follows a __syncthreads() that every wave reaches after its last read of A and C
+  __shared__ __attribute__((aligned(16))) float prm[4][D];
   // dh stays in registers: with 32 KiB of LDS a workgroup of this kernel still fits beside a 128-KiB wgrad workgroup
   // of the side stream (an LDS-parked dh row per wave, 96 KiB in all, made every launch queue behind the wgrads)
   const int lane = threadIdx.x & 63;
@@ -508,15 +526,20 @@ __global__ __launch_bounds__(512) void layernorm_bwd_wide8_kernel(LnBwdDev a) { 
   const int r_begin = grp * a.group_rows;
   int r_end = r_begin + a.group_rows;
   r_end = r_end < a.f.rows ? r_end : a.f.rows;
-  {
-    const int frow = film ? (a.f.t_ptr ? smd_clamp_t(*a.f.t_ptr, a.f.film_rows) : r_begin / a.f.rows_per_sample) : 0;
-    const float* src[4] = {a.f.gamma, a.f.beta, film ? a.f.film_scale + (size_t)frow * a.f.ld_film : nullptr,
-                           film ? a.f.film_shift + (size_t)frow * a.f.ld_film : nullptr};
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (src[q])
-        for (int c = threadIdx.x * 4; c < D; c += 2048)
-          *reinterpret_cast<float4*>(&prm[q][c]) = *reinterpret_cast<const float4*>(src[q] + c);
+  const int frow = film ? (a.f.t_ptr ? smd_clamp_t(*a.f.t_ptr, a.f.film_rows) : r_begin / a.f.rows_per_sample) : 0;
+  const float* fsc = film ? a.f.film_scale + (size_t)frow * a.f.ld_film : nullptr;
+  const float* fsh = film ? a.f.film_shift + (size_t)frow * a.f.ld_film : nullptr;
+  for (int c = threadIdx.x * 4; c < D; c += 2048) {
+    float4 pa = *reinterpret_cast<const float4*>(a.f.gamma + c);
+    if constexpr (film) {
+      const float4 b4 = *reinterpret_cast<const float4*>(a.f.beta + c);
+      const float4 s4 = *reinterpret_cast<const float4*>(fsc + c);
+      const float4 h4 = *reinterpret_cast<const float4*>(fsh + c);
+      pa = make_float4(s4.x * pa.x, s4.y * pa.y, s4.z * pa.z, s4.w * pa.w);
+      *reinterpret_cast<float4*>(&prm[1][c]) =
+          make_float4(fmaf(s4.x, b4.x, h4.x), fmaf(s4.y, b4.y, h4.y), fmaf(s4.z, b4.z, h4.z), fmaf(s4.w, b4.w, h4.w));
+    }
+    *reinterpret_cast<float4*>(&prm[0][c]) = pa;
   }
   __syncthreads();
 
@@ -524,6 +547,7 @@ __global__ __launch_bounds__(512) void layernorm_bwd_wide8_kernel(LnBwdDev a) { 
 #pragma unroll
   for (int i = 0; i < PL; ++i) P[i] = Q[i] = 0.f;
   const uint32_t l4 = lane * 4;                     // element offset of this lane inside a 256-column chunk
+  const bool saved = a.stats != nullptr;
 
   auto issue = [&](int row, WideRow<D, XBF>& b) {
     const float* xr = a.f.x + (size_t)row * D;           // uniform row bases
@@ -537,49 +561,52 @@ __global__ __launch_bounds__(512) void layernorm_bwd_wide8_kernel(LnBwdDev a) { 
     }
     __builtin_amdgcn_sched_barrier(0);
   };
-  auto compute = [&](int row, WideRow<D, XBF>& b) {
+  auto compute = [&](int row, WideRow<D, XBF>& b, const float2 mr) {
     auto fence_x = [&]() {             // bf16 rows: re-convert per pass instead of keeping 32 converted registers alive
       if constexpr (XBF) {
 #pragma unroll
         for (int k = 0; k < NV; ++k) asm volatile("" : "+v"(b.xb[k]));
       }
     };
-    // pass 1: row statistics straight from the raw registers
-    float s = 0.f, sq = 0.f;
+    // pass 1: the row statistics, as the forward saved them or straight from the raw registers
+    float mean, rstd;
+    if (saved) {
+      mean = mr.x; rstd = mr.y;
+    } else {
+      float s = 0.f, sq = 0.f;
 #pragma unroll
-    for (int k = 0; k < NV; ++k)
+      for (int k = 0; k < NV; ++k)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { const float v = b.x(k, e); s += v; sq += v * v; }
-    s = wave_sum(s);
-    sq = wave_sum(sq);
-    const float mean = s * (1.0f / D);
-    const float rstd = smd_ln_rstd(sq * (1.0f / D) - mean * mean + LN_EPS);
-    fence_x();
+        for (int e = 0; e < 4; ++e) { const float v = b.x(k, e); s += v; sq += v * v; }
+      s = wave_sum(s);
+      sq = wave_sum(sq);
+      mean = s * (1.0f / D);
+      rstd = smd_ln_rstd(sq * (1.0f / D) - mean * mean + LN_EPS);
+      fence_x();
+    }
+    const float nmr = -mean * rstd;
     // pass 2: column sums P, Q and the row sums
     float s1 = 0.f, s2 = 0.f;
     float dhr[PL];
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int c = k * 256 + lane * 4;
-      const float4 g4 = *reinterpret_cast<const float4*>(&prm[0][c]);
-      const float4 b4 = *reinterpret_cast<const float4*>(&prm[1][c]);
-      const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
-      float ss[4] = {1.f, 1.f, 1.f, 1.f}, hh[4] = {0.f, 0.f, 0.f, 0.f};
+      const float4 a4 = *reinterpret_cast<const float4*>(&prm[0][c]);
+      const float pa[4] = {a4.x, a4.y, a4.z, a4.w};
+      float pc[4] = {0.f, 0.f, 0.f, 0.f};
       if constexpr (film) {
-        const float4 s4 = *reinterpret_cast<const float4*>(&prm[2][c]);
-        const float4 h4 = *reinterpret_cast<const float4*>(&prm[3][c]);
-        ss[0] = s4.x; ss[1] = s4.y; ss[2] = s4.z; ss[3] = s4.w;
-        hh[0] = h4.x; hh[1] = h4.y; hh[2] = h4.z; hh[3] = h4.w;
+        const float4 c4 = *reinterpret_cast<const float4*>(&prm[1][c]);
+        pc[0] = c4.x; pc[1] = c4.y; pc[2] = c4.z; pc[3] = c4.w;
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int i = k * 4 + e;
-        const float xh = (b.x(k, e) - mean) * rstd;
+        const float xh = fmaf(b.x(k, e), rstd, nmr);
         float d = bf2f(b.dy[k][e]);
-        if constexpr (swish) d *= swish_gradf_(ss[e] * (xh * gg[e] + bb[e]) + hh[e]);
+        if constexpr (swish) d *= swish_gradf_(fmaf(xh, pa[e], pc[e]));
         Q[i] += d;
         P[i] += d * xh;
-        const float dhe = d * ss[e] * gg[e];
+        const float dhe = d * pa[e];
         dhr[i] = dhe;
         s1 += dhe;
         s2 += dhe * xh;
@@ -604,7 +631,7 @@ __global__ __launch_bounds__(512) void layernorm_bwd_wide8_kernel(LnBwdDev a) { 
     }
     float* of = (OM & 1) ? a.dx_f32 + (size_t)row * D : nullptr;
     bf16_t* ob = (OM & 2) ? a.dx_bf16 + (size_t)row * D : nullptr;
-    const float m2 = rstd * rstd * s2, c0 = rstd * (s1 - mean * rstd * s2);     // dx = rstd*dh - m2*x - c0
+    const float m2 = rstd * rstd * s2, c0 = rstd * fmaf(nmr, s2, s1);          // dx = rstd*dh - m2*x - c0
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       float rr[4] = {0.f, 0.f, 0.f, 0.f};
@@ -633,18 +660,19 @@ __global__ __launch_bounds__(512) void layernorm_bwd_wide8_kernel(LnBwdDev a) { 
   // loads with the other's arithmetic.)
   for (int row = r_begin + w; row < r_end; row += NW) {
     WideRow<D, XBF> buf;
+    float2 mr = make_float2(0.f, 0.f);
+    if (saved) mr = *reinterpret_cast<const float2*>(a.stats + (size_t)row * 2);      // uniform address, ahead of the row's loads
     issue(row, buf);
-    compute(row, buf);
+    compute(row, buf, mr);
   }
 
   // ---- combine the 8 waves' P and Q through LDS (two rounds of four, fixed order), then expand
   constexpr int CPT = D / 512;                      // columns per thread: c = threadIdx.x + 512*j
   float gc[CPT], bc[CPT], sc[CPT], Pc[CPT], Qc[CPT];
-  __syncthreads();
 #pragma unroll
-  for (int j = 0; j < CPT; ++j) {
+  for (int j = 0; j < CPT; ++j) {                   // gamma, beta, scale of this thread's columns: once, from global memory
     const int c = threadIdx.x + 512 * j;
-    gc[j] = prm[0][c]; bc[j] = prm[1][c]; sc[j] = film ? prm[2][c] : 1.0f;
+    gc[j] = film ? a.f.gamma[c] : 1.0f; bc[j] = film ? a.f.beta[c] : 0.0f; sc[j] = film ? fsc[c] : 1.0f;
     Pc[j] = Qc[j] = 0.f;
   }
 #pragma unroll
@@ -979,6 +1007,7 @@ int launch_layernorm_bwd(const LnBwdArgs& a, hipStream_t st) {
   d.dout = a.dout;
   d.dres = a.dres;
   d.dres_bf16 = a.dres_bf16;
+  d.stats = a.stats;
   d.dx_f32 = a.dx;
   d.dx_bf16 = a.dx_bf16;
   d.dscale = a.dscale;

@@ -110,6 +110,8 @@ struct LnArgs {
   // [rows][D] bytes = e4m3(y * 2^-e), out_scale [rows] dwords = E8M0 byte e + 127; `out` may then be null
   unsigned char* out_f8 = nullptr;
   uint32_t* out_scale = nullptr;
+  // optional: the row statistics (mean, rstd) as fp32 [rows][2], saved for the backward pass (LnBwdArgs::stats)
+  float* stats_out = nullptr;
 };
 int launch_layernorm_fwd(const LnArgs& a, hipStream_t st);
 
@@ -128,6 +130,7 @@ struct LnBwdArgs {
   const bf16_t* dout = nullptr;
   const float* dres = nullptr;
   const bf16_t* dres_bf16 = nullptr;  // bf16 residual gradient instead of dres (D in {1024, 2048})
+  const float* stats = nullptr;       // (mean, rstd) [rows][2] the forward saved (LnArgs::stats_out); null: recomputed from x
   float* dx = nullptr;
   bf16_t* dx_bf16 = nullptr;
   float* dgamma = nullptr;
