@@ -20,6 +20,7 @@
 //     c ^ (r & 15) (source-side swizzle) so that the 16-lane ds_read_b128 groups are conflict-free.
 //   * training: a2, z1 (pre-GELU) and u are written out for the backward pass straight from the C layout.
 #include "smd_kernels.h"
+#include "gemm_tile.h"
 
 namespace {
 
@@ -31,15 +32,10 @@ constexpr int MAX_HIDDEN = 8192;
 constexpr int SMEM_BYTES = OFF_A2 + S_TOK * E_DIM * 2;  // 136 KiB
 constexpr float LN_EPS = 1e-6f;
 
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(3))) bf16x8_t* lds_b128_ptr;
 typedef const __attribute__((address_space(3))) bf16x4_t* lds_b64_ptr;
 typedef const __attribute__((address_space(3))) unsigned char* lds_byte_ptr;
 typedef const __attribute__((address_space(3))) float4* lds_f4_ptr;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)lds_wave_base, 16, voff, soff, 0, 0);
-}
 
 struct MlpArgs {
   const float* h_in;        // [R][128] fp32 residual stream (h_mid)

@@ -288,6 +288,7 @@ class SmdEngine {
   bool w8_dirty_ = true;                       // the e4m3 weight copies are older than the bf16 operand pack
   bool hs_train_ = false;                      // the forward pass of this step used the hidden-split MLP dataflow
   hipEvent_t take_event();
+  int fork_to_side(hipStream_t st, const char* what);   // side_ waits for what `st` has enqueued so far; errors are reported as `what`
   OptTable opt_stem_, opt_head_;               // tile tables of the fused optimiser sweep (parameters < / >= head_off_)
   void build_opt_tables();
   bool opt_fused_ok_ = true;

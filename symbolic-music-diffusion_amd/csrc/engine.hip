@@ -75,42 +75,41 @@ int SmdEngine::wgrad(const DenseP& p, const bf16_t* X, int ldx, const bf16_t* dY
   t.out = G(p.w_off); t.ldo = p.N; t.bias_out = G(p.b_off);
   t.zero_page = W.zero_page; t.slab = W.tn_slab; t.slab_elems = W.tn_slab_elems;
   t.scratch = W.tn_scratch; t.scratch_elems = W.tn_scratch_elems; t.tr_path = tr_path;
-  if (allow_side && group_wgrad && tr_path && t.ldo == t.N) {
-    int per = 0;
-    if (gemm_tn256_plan(t, &per) == 0) {       // a 128-wide-kernel problem: launched with its peers at the end
-      deferred_wgrads_.push_back(t);
-      return 0;
-    }
+  // asked once, and only where the answer is used: does the 256x256 kernel take it (the two slabs are allocated together: same answer)
+  const bool ask = allow_side && tr_path && ((group_wgrad && t.ldo == t.N) || (side_wgrad && side_ && pair_wgrad));
+  int per = 0;
+  const bool is256 = ask && gemm_tn256_plan(t, &per) > 0;
+  if (allow_side && group_wgrad && tr_path && t.ldo == t.N && !is256) {     // a 128-wide-kernel problem: launched with its peers at the end
+    deferred_wgrads_.push_back(t);
+    return 0;
   }
   if (!(allow_side && side_wgrad && side_ && tr_path)) return launch_gemm_tn(t, st);
   t.slab = W.tn_slab_side;
-  if (pair_wgrad) {                      // a 256x256-kernel problem: wait for its partners (the Dense layers of the DenseResBlocks)
-    int per = 0;
-    if (gemm_tn256_plan(t, &per) > 0) {
-      pending256_.push_back(t);
-      if ((int)pending256_.size() < wgrad256_group) return 0;
-      return flush_pending256(st);
-    }
+  if (pair_wgrad && is256) {             // a 256x256-kernel problem: wait for its partners (the Dense layers of the DenseResBlocks)
+    pending256_.push_back(t);
+    if ((int)pending256_.size() < wgrad256_group) return 0;
+    return flush_pending256(st);
   }
+  RC(fork_to_side(st, "wgrad"));
+  return launch_gemm_tn(t, side_);
+}
+
+// The side stream waits for everything `st` has enqueued so far; join_side() brings it back.
+int SmdEngine::fork_to_side(hipStream_t st, const char* what) {
   hipEvent_t ev = take_event();
-  SMD_ARG_CHECK(ev, "wgrad: cannot create an event");
+  SMD_ARG_CHECK(ev, "%s: cannot create an event", what);
   hipError_t e = hipEventRecord(ev, st);
   if (e == hipSuccess) e = hipStreamWaitEvent(side_, ev, 0);
-  if (e != hipSuccess) { smd_set_error("wgrad: event: %s", hipGetErrorString(e)); return (int)e; }
+  if (e != hipSuccess) { smd_set_error("%s: event: %s", what, hipGetErrorString(e)); return (int)e; }
   side_pending_ = true;
-  return launch_gemm_tn(t, side_);
+  return 0;
 }
 
 // The collected 256x256-kernel weight gradients as ONE side-stream launch behind everything the main stream has enqueued so
 // far (four 2048 x 2048 problems = 256 tiles: no split over m, no slabs, no reduce; fewer: two or four m-splits)
 int SmdEngine::flush_pending256(hipStream_t st) {
   if (pending256_.empty()) return 0;
-  hipEvent_t ev = take_event();
-  SMD_ARG_CHECK(ev, "wgrad: cannot create an event");
-  hipError_t e2 = hipEventRecord(ev, st);
-  if (e2 == hipSuccess) e2 = hipStreamWaitEvent(side_, ev, 0);
-  if (e2 != hipSuccess) { smd_set_error("wgrad: event: %s", hipGetErrorString(e2)); return (int)e2; }
-  side_pending_ = true;
+  RC(fork_to_side(st, "wgrad"));
   int rc = 0;
   for (size_t i = 0; i < pending256_.size() && rc == 0; i += SMD_TN256_MULTI_MAX) {
     const int n = (int)std::min<size_t>(SMD_TN256_MULTI_MAX, pending256_.size() - i);
@@ -127,14 +126,9 @@ int SmdEngine::flush_grouped_wgrads(hipStream_t st, bool on_caller_stream) {
   hipStream_t ls = st;
   float* slab = W.tn_slab;
   if (side_wgrad && side_ && !on_caller_stream) {
-    hipEvent_t ev = take_event();
-    SMD_ARG_CHECK(ev, "flush_grouped_wgrads: cannot create an event");
-    hipError_t e = hipEventRecord(ev, st);
-    if (e == hipSuccess) e = hipStreamWaitEvent(side_, ev, 0);
-    if (e != hipSuccess) { smd_set_error("flush_grouped_wgrads: event: %s", hipGetErrorString(e)); return (int)e; }
+    RC(fork_to_side(st, "flush_grouped_wgrads"));
     ls = side_;
     slab = W.tn_slab_side;
-    side_pending_ = true;
   }
   for (TnLaunch& t : deferred_wgrads_) t.slab = slab;
   // a grouped launch shares one contraction length: batch-row problems (FiLM generators) and token-row problems apart
@@ -496,9 +490,9 @@ int SmdEngine::refresh_weights(hipStream_t st) {
 // ------------------------------------------------------------------ dense helpers
 int SmdEngine::dense_fwd(const DenseP& p, const bf16_t* A, int lda, int M, GemmEpilogue ep, hipStream_t st) {
   ep.bias = P(p.b_off);
-  if (nt256_min_tiles > 0 && gemm_nt256_eligible(M, p.N, p.Kp, ep, nt256_min_tiles))
-    return launch_gemm_nt256(A, lda, wpack_ + p.Wt_off, p.Kp, M, p.N, p.Kp, ep, st);
-  return launch_gemm_nt(A, lda, wpack_ + p.Wt_off, p.Kp, M, p.N, p.Kp, ep, st);
+  // option nt256_min_tiles can only lower the grid size from which the 256x256 kernel takes a layer
+  const int min_tiles = nt256_min_tiles > 0 && nt256_min_tiles < smd_plan::NT256_MIN_TILES ? nt256_min_tiles : smd_plan::NT256_MIN_TILES;
+  return launch_gemm_nt(A, lda, wpack_ + p.Wt_off, p.Kp, M, p.N, p.Kp, ep, st, min_tiles);
 }
 
 int SmdEngine::dense_bwd(const DenseP& p, const bf16_t* X, int ldx, const bf16_t* dY, int ldy, int M, bf16_t* dX,
@@ -537,13 +531,9 @@ int SmdEngine::run_network(const int* t_ptr, hipStream_t st, int part, const flo
   hipEvent_t film_ready = nullptr;
   if (tr && !t_ptr && film_side_fwd && side_wgrad && side_ && d_.arch == 0) {
     RC(launch_noise_embed(W.s, B, F, W.emb, F, st));
-    hipEvent_t ev = take_event();
+    RC(fork_to_side(st, "run_network"));
     film_ready = take_event();
-    SMD_ARG_CHECK(ev && film_ready, "run_network: cannot create an event");
-    hipError_t e = hipEventRecord(ev, st);
-    if (e == hipSuccess) e = hipStreamWaitEvent(side_, ev, 0);
-    if (e != hipSuccess) { smd_set_error("run_network: event: %s", hipGetErrorString(e)); return (int)e; }
-    side_pending_ = true;
+    SMD_ARG_CHECK(film_ready, "run_network: cannot create an event");
     for (int k = 0; k < K; ++k) {
       const FilmResP& b = blk_[k];
       { GemmEpilogue ep; ep.act = SMD_ACT_SWISH; ep.out_bf16 = W.f1[k]; ep.ld_outb = 4 * F; ep.pre_bf16 = W.zf1[k]; ep.ld_pre = 4 * F;
@@ -551,7 +541,7 @@ int SmdEngine::run_network(const int* t_ptr, hipStream_t st, int part, const flo
       { GemmEpilogue ep; ep.out_bf16 = W.p[k]; ep.ld_outb = 4 * F; RC(dense_fwd(b.f2, W.f1[k], 4 * F, B, ep, side_)); }
       { GemmEpilogue ep; ep.out_f32 = W.ss[k]; ep.ld_out = 2 * M; RC(dense_fwd(b.ss, W.p[k], 4 * F, B, ep, side_)); }
     }
-    e = hipEventRecord(film_ready, side_);
+    hipError_t e = hipEventRecord(film_ready, side_);
     if (e != hipSuccess) { smd_set_error("run_network: event: %s", hipGetErrorString(e)); return (int)e; }
   }
 
@@ -958,13 +948,8 @@ int SmdEngine::backward_head(hipStream_t st) {
     // main stream behind an event (dscale / dshift of this block are final after the LayerNorm backward above)
     hipStream_t fs = st;
     if (film_side_fwd && film_side && side_wgrad && side_ && tr_path) {     // (the tr_path = 0 fallback shares one scratch)
-      hipEvent_t ev = take_event();
-      SMD_ARG_CHECK(ev, "backward_head: cannot create an event");
-      hipError_t e = hipEventRecord(ev, st);
-      if (e == hipSuccess) e = hipStreamWaitEvent(side_, ev, 0);
-      if (e != hipSuccess) { smd_set_error("backward_head: event: %s", hipGetErrorString(e)); return (int)e; }
+      RC(fork_to_side(st, "backward_head"));
       fs = side_;
-      side_pending_ = true;
     }
     RC(launch_cast_pad_bf16(W.dss[k], B, 2 * M, W.dss_bf16[k], 2 * M, fs));
     RC(dense_bwd(p.ss, W.p[k], 4 * F, W.dss_bf16[k], 2 * M, B, W.dp[k], 4 * F, nullptr, 0, SMD_AUX_NONE, fs, film_side != 0));
@@ -1144,13 +1129,8 @@ int SmdEngine::backward_stem(hipStream_t st) {
       }
       hipStream_t es = st;
       if (side_wgrad && side_) {
-        hipEvent_t em = take_event();
-        SMD_ARG_CHECK(em, "backward_stem: cannot create an event");
-        hipError_t e = hipEventRecord(em, st);
-        if (e == hipSuccess) e = hipStreamWaitEvent(side_, em, 0);
-        if (e != hipSuccess) { smd_set_error("backward_stem: event: %s", hipGetErrorString(e)); return (int)e; }
+        RC(fork_to_side(st, "backward_stem"));
         es = side_;
-        side_pending_ = true;
       }
       hipError_t e = hipEventRecord(bucket_ev_[b], es);
       if (e != hipSuccess) { smd_set_error("backward_stem: event: %s", hipGetErrorString(e)); return (int)e; }
@@ -1182,14 +1162,10 @@ int SmdEngine::loss_backward(const float* x0, const int* labels, const float* ep
       // picks its completion up just before the first gradient is written
       hipStream_t ms = st;
       if (side_wgrad && side_) {
-        hipEvent_t ev0 = take_event();
+        RC(fork_to_side(st, "loss_backward"));
         grads_zeroed = take_event();
-        SMD_ARG_CHECK(ev0 && grads_zeroed, "loss_backward: cannot create an event");
-        hipError_t e0 = hipEventRecord(ev0, st);
-        if (e0 == hipSuccess) e0 = hipStreamWaitEvent(side_, ev0, 0);
-        if (e0 != hipSuccess) { smd_set_error("loss_backward: %s", hipGetErrorString(e0)); return (int)e0; }
+        SMD_ARG_CHECK(grads_zeroed, "loss_backward: cannot create an event");
         ms = side_;
-        side_pending_ = true;
       }
       hipError_t e = hipMemsetAsync(grads_, 0, sizeof(float) * (size_t)n_params_, ms);
       if (e == hipSuccess && grads_zeroed) e = hipEventRecord(grads_zeroed, side_);
@@ -1223,12 +1199,7 @@ int SmdEngine::loss_backward(const float* x0, const int* labels, const float* ep
     if (stage != 3) RC(flush_grouped_wgrads(st));
     if (early_norm) {
       if (!pending256_.empty()) RC(flush_pending256(st));
-      hipEvent_t ev = take_event();
-      SMD_ARG_CHECK(ev, "loss_backward: cannot create an event");
-      hipError_t e = hipEventRecord(ev, st);
-      if (e == hipSuccess) e = hipStreamWaitEvent(side_, ev, 0);
-      if (e != hipSuccess) { smd_set_error("loss_backward: event: %s", hipGetErrorString(e)); return (int)e; }
-      side_pending_ = true;
+      RC(fork_to_side(st, "loss_backward"));
       RC(launch_grad_sumsq_slots(grads_ + head_off_, (size_t)(n_params_ - head_off_), W.norm_partial, SMD_NORM_HEAD_SLOTS, side_));
       head_norm_ready_ = true;
     }

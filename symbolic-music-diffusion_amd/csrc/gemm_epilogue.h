@@ -2,6 +2,7 @@
 // Order of operations: see GemmEpilogue in smd_kernels.h.
 #pragma once
 #include "smd_kernels.h"
+#include "gemm_plan.h"
 
 namespace smd_epi {
 
@@ -169,6 +170,11 @@ inline bool al8h(const void* p, int ld) { return p == nullptr || (((uintptr_t)p 
 inline bool oct_ok(const GemmEpilogue& ep) {
   return ep.alpha == 1.0f && !ep.accumulate && al4(ep.bias, 4) && al4(ep.res_f32, ep.ld_res) && al8h(ep.res_bf16, ep.ld_resb) &&
          al4(ep.out_f32, ep.ld_out) && al8h(ep.pre_bf16, ep.ld_pre) && al8h(ep.aux, ep.ld_aux) && al8h(ep.out_bf16, ep.ld_outb);
+}
+
+inline smd_plan::NtEpiFlags plan_flags(const GemmEpilogue& ep) {      // what smd_plan::nt_plan needs to know about an epilogue
+  return {oct_ok(ep), vec_ok(ep), ep.out_bf16 != nullptr, ep.out_f32 != nullptr, ep.pre_bf16 != nullptr, ep.act != SMD_ACT_NONE,
+          ep.aux_mode != SMD_AUX_NONE, ep.res_f32 || ep.res_bf16};
 }
 
 }  // namespace smd_epi

@@ -20,33 +20,13 @@
 //   * XCD-aware bijective workgroup remap so one XCD's L2 sees a contiguous band of M-tiles.
 #include "smd_kernels.h"
 #include "gemm_epilogue.h"
-#include <string.h>
+#include "gemm_plan.h"
+#include "gemm_tile.h"
 
 namespace {
 
-constexpr int BN = 128, BK = 64;
+constexpr int BN = smd_plan::NT_BN, BK = smd_plan::NT_BK;
 constexpr int STAGE_LD = 132;   // floats per staged row (128 + 4 pad: 528 B, 16-B aligned)
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void glb_void_t;
-
-__device__ __forceinline__ void glds16(const bf16_t* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((glb_void_t*)g, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
-
-template <int N_> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory"); }
-
-template <int... Es> struct IntSeq {};
-typedef IntSeq<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15> Seq16;
-// 32x32 MFMA C layout: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
-template <int... Es>
-__device__ __forceinline__ void stage_tile(const f32x16_t& acc, float* stage, int row0, int col, IntSeq<Es...>) {
-  ((stage[(row0 + (Es & 3) + 8 * (Es >> 2)) * STAGE_LD + col] = acc[Es]), ...);
-}
-template <int... Es>
-__device__ __forceinline__ void stage_tile_add(const f32x16_t& acc, float* stage, int row0, int col, IntSeq<Es...>) {
-  ((stage[(row0 + (Es & 3) + 8 * (Es >> 2)) * STAGE_LD + col] += acc[Es]), ...);
-}
 
 // NS = number of LDS K-tile buffers.  2: one tile prefetched ahead (MFMA-bound shapes, 64 KiB at BM = 128).
 // 4 (BM <= 64, K >= 512): three tiles in flight -- the skinny-output GEMMs of the 128-wide encoder run one
@@ -72,9 +52,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_nt_kernel(const bf16_t* __restr
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_BYTES];
 
   // ---- XCD-aware bijective remap (block b runs on XCD b % 8; give each XCD a contiguous band)
-  const int bid = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int swz = smd_xcd_band(blockIdx.x, nwg);
   const int tm = swz / tiles_n, tn = swz - tm * tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
 
@@ -194,7 +172,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_nt_kernel(const bf16_t* __restr
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
-          stage_tile(acc[i][j], stage, wr * WTM - p * SROWS + i * 32 + 4 * kh, wc * WTN + j * 32 + (lane & 31),
+          stage_tile<STAGE_LD>(acc[i][j], stage, wr * WTM - p * SROWS + i * 32 + 4 * kh, wc * WTN + j * 32 + (lane & 31),
                      Seq16{});
     }
     __syncthreads();
@@ -204,7 +182,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_nt_kernel(const bf16_t* __restr
         for (int i = 0; i < MT; ++i)
 #pragma unroll
           for (int j = 0; j < NT; ++j)
-            stage_tile_add(acc[i][j], stage, wr * WTM - p * SROWS + i * 32 + 4 * kh, wc * WTN + j * 32 + (lane & 31),
+            stage_tile_add<STAGE_LD>(acc[i][j], stage, wr * WTM - p * SROWS + i * 32 + 4 * kh, wc * WTN + j * 32 + (lane & 31),
                            Seq16{});
       }
       __syncthreads();
@@ -223,35 +201,11 @@ __global__ __launch_bounds__(256 * KG) void gemm_nt_kernel(const bf16_t* __restr
   }
 }
 
-template <int BM, int NS, int KG = 1>
-void launch_bm(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, int N, int K, int vec, const GemmEpilogue& ep,
-               hipStream_t st) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int nwg = tiles_m * tiles_n;
-  hipLaunchKernelGGL((gemm_nt_kernel<BM, NS, KG>), dim3(nwg), dim3(256 * KG), 0, st, A, lda, Bt, ldb, M, N, K, tiles_n, nwg, vec, ep);
-}
-
 }  // namespace
 
-// process-wide kernel-selection knobs (smd_set_tuning in the C-ABI)
-namespace {
-struct Knob { const char* key; int value; };
-Knob g_knobs[] = {{"gemm_nt256", 1}, {"gemm_nt256_variant", 0}, {"gemm_nt256_pk", 1}, {"gemm_tn256", 1}, {"ln_bwd_wide", 2}, {"ln_bwd_narrow", 1}, {"gemm_nt_deep", 1}, {"mlp_variant", 0}, {"tn128_target_wgs", 512}, {"gemm_tn_deep", 0}, {"ln_fwd_wide", 3}, {"gemm_nt_kg", 1}, {"mlp_hs_dbg", 0}, {"ln_excl", 0}, {"tn_exclusive_cu", 2}, {"tn_split_model", 1}, {"tn128_loader_waves", 1}, {"tn_mode", 0}, {"gemm_nt_form", 0}, {"gemm_nt_form_wk", 0}};
-}
-int smd_tuning_set(const char* key, int value) {
-  for (Knob& k : g_knobs)
-    if (key && !strcmp(key, k.key)) { k.value = value; return 0; }
-  smd_set_error("smd_set_tuning: unknown key '%s'", key ? key : "(null)");
-  return -1;
-}
-int smd_tuning_get(const char* key) {
-  for (const Knob& k : g_knobs)
-    if (key && !strcmp(key, k.key)) return k.value;
-  return -1;
-}
-
+// Which kernel and tile form a shape gets is decided by smd_plan::nt_plan (gemm_plan.h); this function checks, asks, launches.
 int launch_gemm_nt(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, int N, int K,
-                   const GemmEpilogue& ep, hipStream_t st) {
+                   const GemmEpilogue& ep, hipStream_t st, int min_tiles) {
   SMD_ARG_CHECK(A && Bt, "gemm_nt: null operand");
   SMD_ARG_CHECK(M > 0 && N > 0 && K > 0, "gemm_nt: bad shape M=%d N=%d K=%d", M, N, K);
   SMD_ARG_CHECK(K % BK == 0, "gemm_nt: K=%d must be a multiple of %d (pad the operands)", K, BK);
@@ -259,45 +213,22 @@ int launch_gemm_nt(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, i
                 "gemm_nt: lda=%d ldb=%d must be >=K and multiples of 8", lda, ldb);
   SMD_ARG_CHECK(ep.out_f32 || ep.out_bf16 || ep.pre_bf16, "gemm_nt: no output");
   SMD_ARG_CHECK(ep.aux_mode == SMD_AUX_NONE || ep.aux, "gemm_nt: aux_mode without aux");
-  if (gemm_nt256_eligible(M, N, K, ep)) return launch_gemm_nt256(A, lda, Bt, ldb, M, N, K, ep, st);
-  const int vec = smd_epi::vec_ok(ep);
-  // tile height: keep >= ~256 workgroups on the chip when the output is skinny
-  const int tiles_n = (N + BN - 1) / BN;
-  const long wg128 = (long)((M + 127) / 128) * tiles_n;
-  const long wg64 = (long)((M + 63) / 64) * tiles_n;
-  const bool deep = K >= 8 * BK && smd_tuning_get("gemm_nt_deep");
-  // measurement knob (tools/gemm_nt_forms_ab.py): force one tile form for the shapes that have a choice
-  // ("gemm_nt_form_wk": the same for the wide-K, few-column shapes only -- out_proj: N <= 512, K >= 2048 -- so that an in-step A/B
-  // of that one GEMM leaves every other launch on its default form)
-  const int form_wk = (M > 64 && N <= 512 && K >= 2048) ? smd_tuning_get("gemm_nt_form_wk") : 0;
-  const int form = form_wk ? form_wk : (M > 64 ? smd_tuning_get("gemm_nt_form") : 0);
-  if (form == 1) launch_bm<64, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-  else if (form == 2) launch_bm<128, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-  else if (form == 3 && K % (2 * BK) == 0) launch_bm<128, 2, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-  else if (form == 4 && K % (2 * BK) == 0) launch_bm<64, 2, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-  else if (form == 5) launch_bm<128, 3>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-  else if (form == 6 && K % (2 * BK) == 0) launch_bm<64, 3, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-  else if (N <= 512 && K >= 2048 && K % (2 * BK) == 0 && M >= 2048 && smd_tuning_get("gemm_nt_kg")) {
-    // out_proj (models/ncsn.py:177-178: rows x 2048 -> 512): 128-row tiles with two K-groups of four waves -- half the operand
-    // traffic per flop of the 64-row form and two waves per SIMD on one tile.  In-step A/B (profiles/r6d_schedule_and_out_proj_form_ab.txt):
-    // sample step +2 ... +3 % (1849 / 1855 -> 1914 / 1885 steps/s), train step unchanged
-    launch_bm<128, 2, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-  } else if (M <= 32 || !(wg128 >= 512 || wg64 >= 256 || M <= 64)) {
-    // K >= 1024: two K-groups of four waves per workgroup (A/B: 8-18 % over one group with a 4-deep ring; deeper rings
-    // -- 7 stages, or 2 groups x 4 stages -- gain nothing: the step time follows the LDS-DMA landing cadence)
-    if (deep && K >= 16 * BK && K % (2 * BK) == 0 && smd_tuning_get("gemm_nt_kg")) launch_bm<32, 3, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-    else if (deep) launch_bm<32, 4>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-    else launch_bm<32, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-  } else if (wg128 >= 512) {
-    launch_bm<128, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-  } else if (wg64 <= 256 && K >= 16 * BK && K % (2 * BK) == 0 && smd_tuning_get("gemm_nt_kg")) {
-    // exactly one 64-row workgroup per CU and a long K (out_proj of one sampler chain, 4096 x 2048 -> 512; out_proj of the
-    // C = 146 network): two K-groups of four waves = two waves per SIMD on the same tile, 19.6 -> 16.5 us and 18.9 -> 15.8 us
-    // (profiles/r4w_gemm_nt_forms.txt); with two workgroups per CU (8192 x 2048 -> 512) the one-group form is the faster one
-    launch_bm<64, 2, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);
-  } else {
-    launch_bm<64, 2>(A, lda, Bt, ldb, M, N, K, vec, ep, st);   // 4 stages = 96 KiB: 1 workgroup per CU instead of 3, slower (A/B)
+  const smd_plan::NtKnobs knobs = {smd_tuning_get("gemm_nt256"), smd_tuning_get("gemm_nt256_pk"), smd_tuning_get("gemm_nt_deep"),
+                                   smd_tuning_get("gemm_nt_kg"), smd_tuning_get("gemm_nt_form"), smd_tuning_get("gemm_nt_form_wk")};
+  const smd_plan::NtPlan p = smd_plan::nt_plan(M, N, K, smd_epi::plan_flags(ep), min_tiles, knobs);
+  if (p.kernel == smd_plan::NT256) return launch_gemm_nt256(A, lda, Bt, ldb, M, N, K, ep, p.pk_epilogue, st);
+#define SMD_NT_FORM(BM_, NS_, KG_)                                                                                                   \
+  case BM_ * 100 + NS_ * 10 + KG_:                                                                                                   \
+    hipLaunchKernelGGL((gemm_nt_kernel<BM_, NS_, KG_>), dim3(p.grid), dim3(p.block), 0, st, A, lda, Bt, ldb, M, N, K, (N + BN - 1) / BN, \
+                       p.grid, p.vec_epilogue, ep);                                                                                  \
+    break
+  switch (p.BM * 100 + p.NS * 10 + p.KG) {
+    SMD_NT_FORM(32, 2, 1); SMD_NT_FORM(32, 4, 1); SMD_NT_FORM(32, 3, 2);
+    SMD_NT_FORM(64, 2, 1); SMD_NT_FORM(64, 2, 2); SMD_NT_FORM(64, 3, 2);
+    SMD_NT_FORM(128, 2, 1); SMD_NT_FORM(128, 2, 2); SMD_NT_FORM(128, 3, 1);
+    default: smd_set_error("gemm_nt: no kernel for tile form <%d, %d, %d>", p.BM, p.NS, p.KG); return -1;
   }
+#undef SMD_NT_FORM
   SMD_LAUNCH_CHECK();
   return 0;
 }

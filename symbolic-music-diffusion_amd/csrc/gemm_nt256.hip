@@ -27,33 +27,20 @@
 //   * Bijective XCD-aware workgroup remap (block b runs on XCD b % 8): each XCD's L2 sees a band of M-tiles.
 #include "smd_kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_plan.h"
+#include "gemm_tile.h"
 
 #include <type_traits>
 
 namespace {
 
-constexpr int TM = 256, TN = 256, TK = 64;
+constexpr int TM = smd_plan::NT256_T, TN = smd_plan::NT256_T, TK = smd_plan::NT256_TK;
 constexpr int HALF_BYTES = 128 * TK * 2;          // 16 KiB: 128 rows x 64 bf16
 constexpr int KT_BYTES = 4 * HALF_BYTES;          // B0 A0 B1 A1
 constexpr int SMEM_BYTES = 2 * KT_BYTES;          // 128 KiB
 constexpr int OFF_B0 = 0, OFF_A0 = HALF_BYTES, OFF_B1 = 2 * HALF_BYTES, OFF_A1 = 3 * HALF_BYTES;
 constexpr int SLD = 68;                           // staged epilogue row: 64 floats + 4 pad (272 B)
 constexpr int WAVE_STAGE_BYTES = 32 * SLD * 4;    // 8704 B per wave
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void glb_void_t;
-
-// LDS-DMA of 16 B per lane: source = buffer descriptor base + per-lane voffset + wave-uniform soffset,
-// destination = wave-uniform LDS base + lane*16.
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff,
-                                       unsigned char* lds_wave_base) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-
-#define SMD_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define SMD_LGKMCNT(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
-#define SMD_PIN() __builtin_amdgcn_sched_barrier(0)
-#define SMD_BAR() __builtin_amdgcn_s_barrier()
 
 typedef const __attribute__((address_space(3))) bf16x8_t* lds_frag_ptr;
 typedef const __attribute__((address_space(3))) unsigned char* lds_byte_ptr;
@@ -125,14 +112,6 @@ __device__ __forceinline__ void mma_quadrant(f32x16_t (&acc)[2], const i32x8_t (
   if constexpr (!(V & 2)) __builtin_amdgcn_s_setprio(0);
 }
 
-template <int... Es> struct IntSeq {};
-typedef IntSeq<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15> Seq16;
-// 32x32 MFMA C layout: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
-template <int... Es>
-__device__ __forceinline__ void stage_tile(const f32x16_t& acc, float* stage, int row0, int col, IntSeq<Es...>) {
-  ((stage[(row0 + (Es & 3) + 8 * (Es >> 2)) * SLD + col] = acc[Es]), ...);
-}
-
 // V: schedule variants for A/B runs (bit 0: no explicit lgkmcnt(0) after the phase barrier -- the compiler's own
 // counted waits sit between the MFMAs; bit 1: no s_setprio around the MFMA clusters).
 // F8: the operands are OCP e4m3 bytes with one power-of-two (E8M0) scale per ROW of A and of Bt (sa[M], sb[N], byte 0 of
@@ -153,9 +132,7 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const void* __restrict_
   const unsigned char* Bt = reinterpret_cast<const unsigned char*>(Btv);
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_BYTES];
 
-  const int bid = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int swz = smd_xcd_band(blockIdx.x, nwg);
   const int tm = swz / tiles_n, tn = swz - tm * tiles_n;
   const int m0 = tm * TM, n0 = tn * TN;
 
@@ -339,8 +316,8 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const void* __restrict_
     smd_epi::EpiPre8 pre[4];                                                                      \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                 \
       smd_epi::epi8_prefetch(pre[i], rbase + (mi) * 64 + (mt) * 32 + i * 8, col, ep);             \
-    stage_tile(acc[mi][0][mt], stage, 4 * kh, (lane & 31), Seq16{});                              \
-    stage_tile(acc[mi][1][mt], stage, 4 * kh, 32 + (lane & 31), Seq16{});                         \
+    stage_tile<SLD>(acc[mi][0][mt], stage, 4 * kh, (lane & 31), Seq16{});                              \
+    stage_tile<SLD>(acc[mi][1][mt], stage, 4 * kh, 32 + (lane & 31), Seq16{});                         \
     __builtin_amdgcn_wave_barrier();                                                              \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                               \
       const float* sp = stage + (i * 8 + (lane >> 3)) * SLD + c8;                                 \
@@ -409,32 +386,15 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(const void* __restrict_
 
 }  // namespace
 
-// the packed-bf16 epilogue applies: (bias ->) bf16 output and nothing else (knob "gemm_nt256_pk" 0 switches it off: A/B, tests)
-static int nt256_pk_epilogue(const GemmEpilogue& ep) {
-  return (smd_tuning_get("gemm_nt256_pk") != 0 && ep.out_bf16 && !ep.out_f32 && !ep.pre_bf16 && ep.act == SMD_ACT_NONE &&
-          ep.aux_mode == SMD_AUX_NONE && !ep.res_f32 && !ep.res_bf16) ? 1 : 0;
-}
-
-bool gemm_nt256_eligible(int M, int N, int K, const GemmEpilogue& ep, int min_tiles) {
-  if (!smd_epi::oct_ok(ep)) return false;
-  const int mode = smd_tuning_get("gemm_nt256");
-  if (mode == 0 || M % TM || N % TN || K % (2 * TK) || K < 2 * TK) return false;
-  if (mode == 2) return true;                  // forced (tests)
-  const long tiles = (long)(M / TM) * (N / TN);
-  // at least ~3/4 of the 256 CUs busy (192): smaller grids are better served by 128-wide tiles -- unless the caller runs
-  // two such streams side by side (concurrent sampling chains ask for 128)
-  return tiles >= min_tiles;
-}
-
+// `pk`: the packed-bf16 epilogue (smd_plan::nt256_pk_epilogue); launch_gemm_nt asks smd_plan::nt_plan whether a shape comes here
 int launch_gemm_nt256(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, int N, int K,
-                      const GemmEpilogue& ep, hipStream_t st) {
+                      const GemmEpilogue& ep, int pk, hipStream_t st) {
   SMD_ARG_CHECK(M % TM == 0 && N % TN == 0 && K % (2 * TK) == 0 && K >= 2 * TK,
                 "gemm_nt256: M=%d N=%d must be multiples of 256 and K=%d a multiple of 128", M, N, K);
   SMD_ARG_CHECK((size_t)TM * lda * 2 < (1ull << 32) && (size_t)TN * ldb * 2 < (1ull << 32), "gemm_nt256: row band exceeds 4 GiB");
   const int tiles_m = M / TM, tiles_n = N / TN;
   const int nwg = tiles_m * tiles_n;
   SMD_ARG_CHECK(smd_epi::oct_ok(ep), "gemm_nt256: epilogue not supported (alignment / alpha / res_bf16 / accumulate)");
-  const int pk = nt256_pk_epilogue(ep);
 #define SMD_NT256_LAUNCH(V_) hipLaunchKernelGGL((gemm_nt256_kernel<V_, false>), dim3(nwg), dim3(512), 0, st, A, lda, Bt, ldb, M, N, K, tiles_n, nwg, ep, nullptr, nullptr, pk)
   // schedule variants 1..3 compute the same result (A/B runs); the ABLATION variants (bits 4, 8, 32, 64: parts of the
   // kernel removed, wrong results by construction) exist only in a -DSMD_ABLATIONS build (tools/kbench.py --gemm-ab)
@@ -471,7 +431,7 @@ int launch_gemm_nt256_fp8(const unsigned char* A8, int lda, const uint32_t* scal
   SMD_ARG_CHECK(ep.out_f32 || ep.out_bf16 || ep.pre_bf16, "gemm_nt256_fp8: no output");
   const int tiles_n = N / TN, nwg = (M / TM) * tiles_n;
   hipLaunchKernelGGL((gemm_nt256_kernel<0, true>), dim3(nwg), dim3(512), 0, st, A8, lda, Bt8, ldb, M, N, K, tiles_n, nwg, ep, scale_a,
-                     scale_b, nt256_pk_epilogue(ep));
+                     scale_b, smd_plan::nt256_pk_epilogue(smd_epi::plan_flags(ep), smd_tuning_get("gemm_nt256_pk")));
   SMD_LAUNCH_CHECK();
   return 0;
 }

@@ -23,56 +23,33 @@
 //
 // Fallback (tr_path = 0): explicit bf16 transposes into scratch + the NT kernel + column sums.
 #include "smd_kernels.h"
+#include "gemm_plan.h"
+#include "gemm_tile.h"
 
 namespace {
 
-constexpr int BT = 128;          // output tile edge (both Kd and N)
-constexpr int BKM = 64;          // m rows per K-tile
+constexpr int BT = smd_plan::TN128_T;          // output tile edge (both Kd and N)
+constexpr int BKM = smd_plan::TN128_KM;   // m rows per K-tile
 constexpr int TILE_BYTES = BKM * BT * 2;   // 16 KiB
 constexpr int BUF_BYTES = 2 * TILE_BYTES;
+static_assert(BUF_BYTES == smd_plan::TN128_BUF_BYTES, "gemm_plan.h sizes the LDS pad from this");
 constexpr int STAGE_LD = 132;
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void glb_void_t;
 typedef __attribute__((address_space(3))) unsigned char lds_byte_t;
-
-__device__ __forceinline__ void glds16(const bf16_t* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((glb_void_t*)g, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
 
 union Frag8 {
   bf16x8_t v;
   s16x4_t h[2];
 };
 
-// All 8 transpose reads of one k-step + their wait in ONE asm statement (hipcc does not count
-// asm loads; with the builtin form it drains vmcnt(0) -- and with it the prefetched LDS-DMA --
-// before every read).  a0/a1/b0/b1: LDS byte addresses of the two A / two B fragments at
-// k-step 0, row block 0; KOFF = ks*4096 selects the k-step, +1024 the second 4-row block.
-template <int KOFF>
-__device__ __forceinline__ void tr_read_kstep(unsigned a0, unsigned a1, unsigned b0, unsigned b1,
-                                              Frag8 (&af)[2], Frag8 (&bfr)[2]) {
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %1, %8 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %2, %9 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %3, %9 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %4, %10 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %5, %10 offset:%13\n\t"
-      "ds_read_b64_tr_b16 %6, %11 offset:%12\n\t"
-      "ds_read_b64_tr_b16 %7, %11 offset:%13\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(af[0].h[0]), "=&v"(af[0].h[1]), "=&v"(af[1].h[0]), "=&v"(af[1].h[1]),
-        "=&v"(bfr[0].h[0]), "=&v"(bfr[0].h[1]), "=&v"(bfr[1].h[0]), "=&v"(bfr[1].h[1])
-      : "v"(a0), "v"(a1), "v"(b0), "v"(b1), "i"(KOFF), "i"(KOFF + 1024)
-      : "memory");
-}
-
-// The same eight reads WITHOUT the wait, and the wait as a statement of its own that names the registers it releases
-// ("+v": later uses of the fragments are ordered behind it, and the asm stays where it is written): the reads of k-step
-// k+1 are issued before the MFMAs of k-step k, so a one-wave-per-SIMD workgroup (CU-exclusive wgrads) no longer sits
-// through an LDS round trip in front of every four MFMAs.  LDS reads return in order: with the next k-step's eight
-// reads queued behind them, lgkmcnt(8) means "this k-step's fragments have arrived".
+// All 8 transpose reads of one k-step in ONE asm statement (hipcc does not count asm loads; with the builtin form it drains
+// vmcnt(0) -- and with it the prefetched LDS-DMA -- before every read).  a0/a1/b0/b1: LDS byte addresses of the two A / two B
+// fragments at k-step 0, row block 0; KOFF = ks*4096 selects the k-step, +1024 the second 4-row block.
+// The wait is a statement of its own that names the registers it releases ("+v": later uses of the fragments are ordered
+// behind it, and the asm stays where it is written): the reads of k-step k+1 are issued before the MFMAs of k-step k, so a
+// one-wave-per-SIMD workgroup (CU-exclusive wgrads) does not sit through an LDS round trip in front of every four MFMAs.
+// LDS reads return in order: with the next k-step's eight reads queued behind them, lgkmcnt(8) means "this k-step's
+// fragments have arrived".
 template <int KOFF>
 __device__ __forceinline__ void tr_issue_kstep(unsigned a0, unsigned a1, unsigned b0, unsigned b1,
                                                Frag8 (&af)[2], Frag8 (&bfr)[2]) {
@@ -97,14 +74,6 @@ __device__ __forceinline__ void tr_wait_kstep(Frag8 (&af)[2], Frag8 (&bfr)[2]) {
                  "+v"(bfr[0].h[0]), "+v"(bfr[0].h[1]), "+v"(bfr[1].h[0]), "+v"(bfr[1].h[1])
                : "i"(N)
                : "memory");
-}
-
-template <int... Es> struct IntSeq {};
-typedef IntSeq<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15> Seq16;
-// 32x32 MFMA C layout: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
-template <int... Es>
-__device__ __forceinline__ void stage_tile(const f32x16_t& acc, float* stage, int row0, int col, IntSeq<Es...>) {
-  ((stage[(row0 + (Es & 3) + 8 * (Es >> 2)) * STAGE_LD + col] = acc[Es]), ...);
 }
 
 struct TnArgs {
@@ -297,7 +266,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_128x128_kernel(TnGroupArgs ga
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          stage_tile(acc[i][j], stage, i * 32 + 4 * kh, wc * 64 + j * 32 + (lane & 31), Seq16{});
+          stage_tile<STAGE_LD>(acc[i][j], stage, i * 32 + 4 * kh, wc * 64 + j * 32 + (lane & 31), Seq16{});
     }
     __syncthreads();
     const int c4 = (tid & 31) * 4;
@@ -466,43 +435,15 @@ int smd_tn_pad_bytes(int static_lds_bytes) {
   return pad > 0 ? pad : 0;
 }
 
-// Split-K factor of a 128x128-tile launch.  With CU-exclusive workgroups (tn_exclusive_cu) a launch runs in whole rounds of
-// 256 workgroups, so 36 tiles x 15 splits = 540 workgroups (the old "about 512" rule) took THREE rounds of 9 K-tiles;
-// 7 splits = 252 workgroups take one round of 19.  Cost in K-tile units: rounds x (K-tiles per split + a fixed prologue /
-// slab-epilogue share) + the slab traffic the split adds; the smallest wins, ties go to fewer splits.
-static int smd_tn_pick_split(int tiles, int total_kt, int max_split) {
-  if (!smd_tuning_get("tn_split_model")) {
-    int ns = (512 + tiles - 1) / tiles;
-    return ns < 1 ? 1 : (ns > max_split ? max_split : ns);
-  }
-  const int per_round = smd_tuning_get("tn_exclusive_cu") ? 256 : 512;
-  int best = 1;
-  float best_cost = 1e30f;
-  for (int ns = 1; ns <= max_split && ns <= total_kt; ++ns) {
-    const int per = (total_kt + ns - 1) / ns;
-    const int rounds = (tiles * ns + per_round - 1) / per_round;
-    const float cost = (float)rounds * ((float)per + 5.0f) + (ns > 1 ? 0.35f * (float)ns : 0.0f);
-    if (cost < best_cost - 1e-3f) { best_cost = cost; best = ns; }
-  }
-  return best;
+static smd_plan::TnKnobs tn_knobs() {
+  return {smd_tuning_get("tn128_target_wgs"), smd_tuning_get("tn_split_model"), smd_tuning_get("tn_exclusive_cu"), smd_tuning_get("gemm_tn_deep"),
+          smd_tuning_get("tn128_loader_waves"), smd_tuning_get("tn_mode")};
 }
 
-// CU-exclusive launch: four MFMA waves + four loader waves (tn128_loader_waves = 0: the four MFMA waves load themselves).
-// Knob "tn_mode" (A/B experiments) overrides the choice: NS*100 + NW*10 + pad, pad 0 = none, 1 = fill the
-// CU's 160 KiB, 2 = pad the workgroup to 96 KiB (one wgrad workgroup per CU, small-LDS workgroups may still share it).
-static int smd_tn_launch_128(int tiles, int nsplit, const TnGroupArgs& ga, bool exclusive_default, hipStream_t st) {
-  int mode = smd_tuning_get("tn_mode");
-  if (!mode) {
-    if (exclusive_default) mode = 400 + (smd_tuning_get("tn128_loader_waves") ? 80 : 40) + (smd_tuning_get("tn_exclusive_cu") == 1 ? 1 : 0);
-    else mode = 240;
-  }
-  const int ns = mode / 100, nw = (mode / 10) % 10, padc = mode % 10;
-  const int lds = ns * BUF_BYTES;
-  int pad = 0;
-  if (padc == 1) pad = 160 * 1024 - lds;
-  else if (padc == 2) pad = 96 * 1024 - lds;
-  if (pad < 0) pad = 0;
+// Launches the kernel variant smd_plan::tn128_mode chose (gemm_plan.h).
+static int smd_tn_launch_128(int tiles, int nsplit, const TnGroupArgs& ga, const smd_plan::TnMode& m, hipStream_t st) {
   const dim3 grid(tiles, nsplit);
+  const int ns = m.ns, nw = m.nw, pad = m.pad_bytes;
   // Only <4, 8> ships.  The two-buffer instantiations (and, at a lower rate, <4, 4>) disturb a dependent VALU -> v_rsq_f32 pair
   // of small LayerNorm workgroups that share their CU -- reproduced without the engine by tools/rsq_repro.hip, 53 of 3000
   // victim launches wrong next to <2, 8> even with the guarded instruction -- so they exist only in an
@@ -515,13 +456,64 @@ static int smd_tn_launch_128(int tiles, int nsplit, const TnGroupArgs& ga, bool 
 #endif
   else {
     smd_set_error("gemm_tn: kernel variant %d (tn_mode / tn_exclusive_cu / tn128_loader_waves) is not in this build: only the "
-                  "four-buffer kernel with loader waves ships, the others need -DSMD_TN_EXPERIMENTS", mode);
+                  "four-buffer kernel with loader waves ships, the others need -DSMD_TN_EXPERIMENTS", m.mode);
     return -1;
   }
   return 0;
 }
 
+static size_t tn_slab_stride(const TnLaunch& t) { return ((size_t)t.Kd * t.N + t.N + 3) / 4 * 4; }
+static void fill_tn_args(TnArgs& a, const TnLaunch& t, float* slab, const smd_plan::TnSplit& sp, const bf16_t* zero_page) {
+  a.X = t.X; a.ldx = t.ldx; a.dY = t.dY; a.ldy = t.ldy; a.Mrows = t.Mrows; a.Kd = t.Kd; a.N = t.N;
+  a.out = t.out; a.ldo = t.ldo; a.bias_out = t.bias_out; a.slab = slab; a.slab_stride = tn_slab_stride(t);
+  a.tiles_n = (t.N + BT - 1) / BT; a.ktiles_per_split = sp.ktiles_per_split; a.nsplit = sp.nsplit; a.zero_page = zero_page;
+}
+
 size_t gemm_tn_slab_elems() { return (size_t)4 * 2048 * 2048 + (size_t)1024 * 1024; }
+
+// One launch of the 128-wide kernel for cnt <= 8 problems sharing Mrows (+ one slab reduce when split over m): one split count for all, slabs carved
+// from the first problem's workspace.  TN_SINGLE: launch_gemm_tn's lone problem, which may lack a slab or have ldo > N and then runs unsplit.
+static int launch_tn128(const TnLaunch* probs, int cnt, int index0, smd_plan::TnSite site, hipStream_t st) {
+  const TnLaunch& t0 = probs[0];
+  const int total_kt = (t0.Mrows + BKM - 1) / BKM;
+  TnGroupArgs ga;
+  ga.ngroups = cnt;
+  int tiles = 0;
+  size_t slab_per_split = 0;
+  for (int i = 0; i < cnt; ++i) {
+    const TnLaunch& t = probs[i];
+    SMD_ARG_CHECK(t.X && t.dY && t.out && t.Mrows == t0.Mrows && (site == smd_plan::TN_SINGLE || t.ldo == t.N) && t.ldx % 8 == 0 && t.ldy % 8 == 0,
+                  "%s: problem %d incompatible", site == smd_plan::TN_SINGLE ? "gemm_tn" : "gemm_tn_grouped", index0 + i);
+    ga.tile_start[i] = tiles;
+    tiles += ((t.Kd + BT - 1) / BT) * ((t.N + BT - 1) / BT);
+    slab_per_split += tn_slab_stride(t);
+  }
+  ga.tile_start[cnt] = tiles;
+  const smd_plan::TnKnobs knobs = tn_knobs();
+  // split-K over m needs the slab workspace and an output the slab reduce can write
+  const size_t cap = (t0.slab && (site == smd_plan::TN_GROUPED || t0.ldo == t0.N)) ? t0.slab_elems / slab_per_split : 0;
+  const smd_plan::TnSplit sp = smd_plan::tn128_split(tiles, total_kt, cap, site, knobs);
+  const int nsplit = sp.nsplit;
+  RedGroupArgs ra;
+  ra.n = cnt;
+  size_t slab_off = 0;
+  int blocks = 0;
+  for (int i = 0; i < cnt; ++i) {
+    const TnLaunch& t = probs[i];
+    const size_t stride = tn_slab_stride(t);
+    fill_tn_args(ga.p[i], t, t0.slab + slab_off, sp, t0.zero_page);
+    ra.p[i] = RedProb{ga.p[i].slab, stride, nsplit, (size_t)t.Kd * t.N, t.out, t.N, t.bias_out, blocks};
+    blocks += (int)(((size_t)t.Kd * t.N + (t.bias_out ? t.N : 0) + 255) / 256);
+    slab_off += (size_t)nsplit * stride;
+  }
+  if (int rc = smd_tn_launch_128(tiles, nsplit, ga, smd_plan::tn128_mode(sp.ktiles_per_split, site, knobs), st)) return rc;
+  SMD_LAUNCH_CHECK();
+  if (nsplit > 1) {
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks), dim3(256), 0, st, ra);
+    SMD_LAUNCH_CHECK();
+  }
+  return 0;
+}
 
 int launch_gemm_tn(const TnLaunch& t, hipStream_t st) {
   SMD_ARG_CHECK(t.X && t.dY && t.out, "gemm_tn: null operand");
@@ -532,42 +524,7 @@ int launch_gemm_tn(const TnLaunch& t, hipStream_t st) {
     int per256 = 0;
     if (const int ns256 = gemm_tn256_plan(t, &per256)) return launch_gemm_tn256(t, ns256, per256, st);
     SMD_ARG_CHECK(t.zero_page, "gemm_tn: needs a 128-element zeroed bf16 page");
-    const int tiles_k = (t.Kd + BT - 1) / BT, tiles_n = (t.N + BT - 1) / BT;
-    const int tiles = tiles_k * tiles_n;
-    const int total_kt = (t.Mrows + BKM - 1) / BKM;
-    const size_t stride = ((size_t)t.Kd * t.N + t.N + 3) / 4 * 4;
-    int nsplit = 1;
-    // workgroups wanted on the chip (split-K over m): 512 (two per CU); 256 for the 128-wide weights, where the
-    // slab traffic of 32 splits costs more than the second workgroup per CU gains (kbench --tn128)
-    int target = smd_tuning_get("tn128_target_wgs");
-    if (target == 512 && tiles <= 16) target = 256;
-    if (tiles < target && t.slab && t.ldo == t.N) {
-      nsplit = smd_tuning_get("tn_split_model") ? smd_tn_pick_split(tiles, total_kt, 32) : (target + tiles - 1) / tiles;
-      if (nsplit > 32) nsplit = 32;
-      if (nsplit > total_kt) nsplit = total_kt;
-      const size_t cap = t.slab_elems / stride;
-      if ((size_t)nsplit > cap) nsplit = (int)cap;
-      if (nsplit < 1) nsplit = 1;
-    }
-    const int per = (total_kt + nsplit - 1) / nsplit;
-    nsplit = (total_kt + per - 1) / per;
-    TnGroupArgs ga;
-    ga.ngroups = 1; ga.tile_start[0] = 0; ga.tile_start[1] = tiles;
-    TnArgs& a = ga.p[0];
-    a.X = t.X; a.ldx = t.ldx; a.dY = t.dY; a.ldy = t.ldy; a.Mrows = t.Mrows; a.Kd = t.Kd; a.N = t.N;
-    a.out = t.out; a.ldo = t.ldo; a.bias_out = t.bias_out; a.slab = t.slab; a.slab_stride = stride;
-    a.tiles_n = tiles_n; a.ktiles_per_split = per; a.nsplit = nsplit; a.zero_page = t.zero_page;
-    if (int rc = smd_tn_launch_128(tiles, nsplit, ga, smd_tuning_get("tn_exclusive_cu") || (per >= 6 && smd_tuning_get("gemm_tn_deep")), st)) return rc;
-    SMD_LAUNCH_CHECK();
-    if (nsplit > 1) {
-      RedGroupArgs ra;
-      ra.n = 1;
-      ra.p[0] = RedProb{t.slab, stride, nsplit, (size_t)t.Kd * t.N, t.out, t.N, t.bias_out, 0};
-      const size_t total = ra.p[0].n_w + (t.bias_out ? t.N : 0);
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ra);
-      SMD_LAUNCH_CHECK();
-    }
-    return 0;
+    return launch_tn128(&t, 1, 0, smd_plan::TN_SINGLE, st);
   }
   // ---- fallback: explicit transposed copies, then the NT kernel (contraction = Mrows padded to 64)
   const int Mp = (t.Mrows + 63) / 64 * 64;
@@ -590,58 +547,12 @@ int launch_gemm_tn(const TnLaunch& t, hipStream_t st) {
   return rc;
 }
 
-// Grouped launch of the 128-wide kernel: n problems (<= 8 per launch) sharing Mrows, each with ldo == N; one
-// split count for all, slabs carved from the first problem's workspace, one grouped reduce.
+// Grouped launch of the 128-wide kernel: n problems (<= 8 per launch) sharing Mrows, each with ldo == N.
 int launch_gemm_tn_grouped(const TnLaunch* probs, int n, hipStream_t st) {
-  int i0 = 0;
-  while (i0 < n) {
-    const int cnt = (n - i0) < SMD_TN_GROUP_MAX ? (n - i0) : SMD_TN_GROUP_MAX;
+  for (int i0 = 0; i0 < n; i0 += SMD_TN_GROUP_MAX) {
     const TnLaunch& t0 = probs[i0];
     SMD_ARG_CHECK(t0.zero_page && t0.slab && t0.tr_path, "gemm_tn_grouped: needs zero page, slab workspace and tr_path = 1");
-    const int total_kt = (t0.Mrows + BKM - 1) / BKM;
-    TnGroupArgs ga;
-    ga.ngroups = cnt;
-    int tiles = 0;
-    size_t slab_per_split = 0;
-    for (int i = 0; i < cnt; ++i) {
-      const TnLaunch& t = probs[i0 + i];
-      SMD_ARG_CHECK(t.X && t.dY && t.out && t.Mrows == t0.Mrows && t.ldo == t.N && t.ldx % 8 == 0 && t.ldy % 8 == 0,
-                    "gemm_tn_grouped: problem %d incompatible", i0 + i);
-      ga.tile_start[i] = tiles;
-      tiles += ((t.Kd + BT - 1) / BT) * ((t.N + BT - 1) / BT);
-      slab_per_split += ((size_t)t.Kd * t.N + t.N + 3) / 4 * 4;
-    }
-    ga.tile_start[cnt] = tiles;
-    int nsplit = smd_tn_pick_split(tiles, total_kt, 32);
-    if (nsplit > 32) nsplit = 32;
-    if (nsplit > total_kt) nsplit = total_kt;
-    if ((size_t)nsplit * slab_per_split > t0.slab_elems) nsplit = (int)(t0.slab_elems / slab_per_split);
-    if (nsplit < 1) nsplit = 1;            // one split writes the gradients directly, no slab needed
-    const int per = (total_kt + nsplit - 1) / nsplit;
-    nsplit = (total_kt + per - 1) / per;
-    RedGroupArgs ra;
-    ra.n = cnt;
-    size_t slab_off = 0;
-    int blocks = 0;
-    for (int i = 0; i < cnt; ++i) {
-      const TnLaunch& t = probs[i0 + i];
-      const size_t stride = ((size_t)t.Kd * t.N + t.N + 3) / 4 * 4;
-      TnArgs& a = ga.p[i];
-      a.X = t.X; a.ldx = t.ldx; a.dY = t.dY; a.ldy = t.ldy; a.Mrows = t.Mrows; a.Kd = t.Kd; a.N = t.N;
-      a.out = t.out; a.ldo = t.ldo; a.bias_out = t.bias_out; a.slab = t0.slab + slab_off; a.slab_stride = stride;
-      a.tiles_n = (t.N + BT - 1) / BT; a.ktiles_per_split = per; a.nsplit = nsplit; a.zero_page = t0.zero_page;
-      ra.p[i] = RedProb{a.slab, stride, nsplit, (size_t)t.Kd * t.N, t.out, t.N, t.bias_out, blocks};
-      blocks += (int)(((size_t)t.Kd * t.N + (t.bias_out ? t.N : 0) + 255) / 256);
-      slab_off += (size_t)nsplit * stride;
-    }
-    // tn_exclusive_cu != 0 (default 2): the four-buffer instantiation (1: padded to the CU's whole LDS, see smd_tn_pad_bytes())
-    if (int rc = smd_tn_launch_128(tiles, nsplit, ga, smd_tuning_get("tn_exclusive_cu") != 0, st)) return rc;
-    SMD_LAUNCH_CHECK();
-    if (nsplit > 1) {
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks), dim3(256), 0, st, ra);
-      SMD_LAUNCH_CHECK();
-    }
-    i0 += cnt;
+    if (int rc = launch_tn128(probs + i0, (n - i0) < SMD_TN_GROUP_MAX ? (n - i0) : SMD_TN_GROUP_MAX, i0, smd_plan::TN_GROUPED, st)) return rc;
   }
   return 0;
 }

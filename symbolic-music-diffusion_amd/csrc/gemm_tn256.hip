@@ -20,11 +20,12 @@
 //     on K-tiles with kt % tiles_k == tk (wave row 0 for the B0 columns, wave row 1 for B1), so every block
 //     carries 1/tiles_k of the column-sum work; the partial rows are summed by the same reduce kernel.
 #include "smd_kernels.h"
+#include "gemm_plan.h"
+#include "gemm_tile.h"
 
-// dynamic-LDS pad that makes a weight-gradient workgroup fill a CU's LDS (smd_kernels.h)
 namespace {
 
-constexpr int TM = 256, TN = 256, TKM = 64;
+constexpr int TM = smd_plan::TN256_T, TN = smd_plan::TN256_T, TKM = smd_plan::TN256_KM;
 constexpr int HALF_BYTES = TKM * 128 * 2;         // 16 KiB: 64 rows x 128 bf16
 constexpr int KT_BYTES = 4 * HALF_BYTES;          // B0 A0 B1 A1
 constexpr int SMEM_BYTES = 2 * KT_BYTES;          // 128 KiB
@@ -32,18 +33,7 @@ constexpr int OFF_B0 = 0, OFF_A0 = HALF_BYTES, OFF_B1 = 2 * HALF_BYTES, OFF_A1 =
 constexpr int SLD = 68;
 constexpr int WAVE_STAGE_BYTES = 32 * SLD * 4;
 
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(3))) unsigned char lds_byte_t;
-
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff,
-                                       unsigned char* lds_wave_base) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-
-#define SMD_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define SMD_LGKMCNT(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
-#define SMD_PIN() __builtin_amdgcn_sched_barrier(0)
-#define SMD_BAR() __builtin_amdgcn_s_barrier()
 
 union Frag8 {
   bf16x8_t v;
@@ -81,13 +71,6 @@ __device__ __forceinline__ void mma_ones(f32x16_t& acc, const bf16x8_t ones, con
   for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, b[ks].v, acc, 0, 0, 0);
 }
 
-template <int... Es> struct IntSeq {};
-typedef IntSeq<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15> Seq16;
-template <int... Es>
-__device__ __forceinline__ void stage_tile(const f32x16_t& acc, float* stage, int row0, int col, IntSeq<Es...>) {
-  ((stage[(row0 + (Es & 3) + 8 * (Es >> 2)) * SLD + col] = acc[Es]), ...);
-}
-
 struct Tn256Args {
   const bf16_t* X; int ldx;
   const bf16_t* dY; int ldy;
@@ -109,9 +92,7 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(Tn256Group ga) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_BYTES];
 
   // flattened (problem, split, tile) id, XCD-remapped: one XCD's blocks share an m-range and neighbouring tiles
-  const int bid = blockIdx.x;
-  const int q = ga.nwg_total >> 3, r = ga.nwg_total & 7, xcd = bid & 7;
-  int vid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  int vid = smd_xcd_band(blockIdx.x, ga.nwg_total);
   int gsel = 0;
   while (gsel + 1 < ga.ngroups && vid >= ga.p[gsel].nwg) { vid -= ga.p[gsel].nwg; ++gsel; }
   const Tn256Args a = ga.p[gsel];
@@ -305,8 +286,8 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(Tn256Group ga) {
   float* dst = a.dst + (size_t)split * a.split_stride + (size_t)(kd0 + wr * 128 + (lane >> 3)) * a.ld + n0 + wc * 64 + c8;
 #define EPI_PASS(mi, mt)                                                                          \
   do {                                                                                            \
-    stage_tile(acc[mi][0][mt], stage, 4 * kh, (lane & 31), Seq16{});                              \
-    stage_tile(acc[mi][1][mt], stage, 4 * kh, 32 + (lane & 31), Seq16{});                         \
+    stage_tile<SLD>(acc[mi][0][mt], stage, 4 * kh, (lane & 31), Seq16{});                              \
+    stage_tile<SLD>(acc[mi][1][mt], stage, 4 * kh, 32 + (lane & 31), Seq16{});                         \
     __builtin_amdgcn_wave_barrier();                                                              \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                               \
       const float* sp = stage + (i * 8 + (lane >> 3)) * SLD + c8;                                 \
@@ -351,27 +332,15 @@ __global__ __launch_bounds__(256) void reduce_slabs256_kernel(const float* __res
 
 }  // namespace
 
-// Eligibility + split choice for the 256x256 wgrad kernel.  Returns nsplit (0 = not eligible).
+// Eligibility + split choice for the 256x256 wgrad kernel.  Returns nsplit (0 = not eligible).  The shape rules are
+// smd_plan::tn256_plan (gemm_plan.h); what needs the strides and pointers is checked here.
 int gemm_tn256_plan(const TnLaunch& t, int* ktiles_per_split) {
-  if (smd_tuning_get("gemm_tn256") == 0) return 0;
-  if (t.Kd % TM || t.N % TN || t.ldx % 8 || t.ldy % 8 || t.ldo % 4 || !t.slab) return 0;
+  if (t.ldx % 8 || t.ldy % 8 || t.ldo % 4 || !t.slab) return 0;
   if ((size_t)t.Mrows * t.ldx * 2 >= (1ull << 31) || (size_t)t.Mrows * t.ldy * 2 >= (1ull << 31)) return 0;
   if ((((uintptr_t)t.out) & 15) || (t.bias_out && (((uintptr_t)t.bias_out) & 15))) return 0;
-  const int tiles = (t.Kd / TM) * (t.N / TN);
-  const int total_kt = (t.Mrows + TKM - 1) / TKM;
-  if (total_kt < 8) return 0;
-  int nsplit = (256 + tiles - 1) / tiles;               // one workgroup per CU (128 KiB LDS each)
-  if (nsplit > 4 && smd_tuning_get("gemm_tn256") != 2) return 0;   // slab traffic would dominate: 128-wide kernel
-  if (nsplit * 4 > total_kt) nsplit = total_kt / 4;     // at least 4 K-tiles per block
-  if (nsplit < 1) nsplit = 1;
-  int per = (total_kt + nsplit - 1) / nsplit;
-  per = (per + 1) & ~1;                                 // the pipeline consumes K-tiles in pairs
-  nsplit = (total_kt + per - 1) / per;
-  const size_t need = (size_t)nsplit * t.Kd * t.N + (size_t)nsplit * (t.Kd / TM) * t.N;
-  if (need > t.slab_elems) return 0;
-  if ((long)tiles * nsplit < 96 && smd_tuning_get("gemm_tn256") != 2) return 0;   // tiny grids: 128-wide kernel
-  *ktiles_per_split = per;
-  return nsplit;
+  const smd_plan::TnSplit sp = smd_plan::tn256_plan(t.Mrows, t.Kd, t.N, t.slab_elems, smd_tuning_get("gemm_tn256"));
+  if (sp.nsplit) *ktiles_per_split = sp.ktiles_per_split;
+  return sp.nsplit;
 }
 
 static void fill_tn256(Tn256Args& a, const TnLaunch& t, int nsplit, int per, float* slab) {
@@ -414,12 +383,8 @@ int launch_gemm_tn256_multi(const TnLaunch* ts, int n, hipStream_t st) {
     SMD_ARG_CHECK(ts[i].Mrows == ts[0].Mrows, "gemm_tn256_multi: different contraction lengths");
     tiles_all += (ts[i].Kd / TM) * (ts[i].N / TN);
   }
-  int nsplit = 256 / tiles_all;
-  if (nsplit * 4 > total_kt) nsplit = total_kt / 4;
-  if (nsplit < 1) nsplit = 1;
-  int per = (total_kt + nsplit - 1) / nsplit;
-  per = (per + 1) & ~1;
-  nsplit = (total_kt + per - 1) / per;
+  const smd_plan::TnSplit sp = smd_plan::tn256_multi_split(total_kt, tiles_all);
+  const int nsplit = sp.nsplit, per = sp.ktiles_per_split;
   Tn256Group ga;
   ga.ngroups = n;
   ga.nwg_total = 0;
@@ -452,9 +417,4 @@ int launch_gemm_tn256_multi(const TnLaunch* ts, int n, hipStream_t st) {
     }
   }
   return 0;
-}
-
-int launch_gemm_tn256_pair(const TnLaunch& t0, const TnLaunch& t1, hipStream_t st) {
-  const TnLaunch ts[2] = {t0, t1};
-  return launch_gemm_tn256_multi(ts, 2, st);
 }

@@ -3,6 +3,7 @@
 // library error convention (0 ok, <0 argument error, >0 hipError_t).
 #pragma once
 #include "smd_common.h"
+#include "gemm_plan.h"
 
 // ------------------------------------------------------------------ GEMM (gemm_nt.hip / gemm_tn.hip)
 enum { SMD_ACT_NONE = 0, SMD_ACT_GELU = 1, SMD_ACT_SWISH = 2 };
@@ -32,21 +33,21 @@ struct GemmEpilogue {
   int ld_outb = 0;
 };
 
-// C[M,N] = A[M,K] * Bt[N,K]^T   (both operands K-contiguous bf16; K % 64 == 0; lda,ldb % 8 == 0)
+// C[M,N] = A[M,K] * Bt[N,K]^T   (both operands K-contiguous bf16; K % 64 == 0; lda,ldb % 8 == 0).  Kernel and tile form:
+// smd_plan::nt_plan (gemm_plan.h); min_tiles = grid size from which the 256x256 kernel takes an eligible shape
 int launch_gemm_nt(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, int N, int K,
-                   const GemmEpilogue& ep, hipStream_t st);
+                   const GemmEpilogue& ep, hipStream_t st, int min_tiles = smd_plan::NT256_MIN_TILES);
 
-// 256x256x64 8-phase kernel (gemm_nt256.hip); launch_gemm_nt dispatches to it when eligible and enabled
-bool gemm_nt256_eligible(int M, int N, int K, const GemmEpilogue& ep, int min_tiles = 192);
+// 256x256x64 8-phase kernel (gemm_nt256.hip); launch_gemm_nt dispatches to it when the plan says so
 int launch_gemm_nt256(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, int N, int K,
-                      const GemmEpilogue& ep, hipStream_t st);
+                      const GemmEpilogue& ep, int pk_epilogue, hipStream_t st);
 // the same tile and pipeline on OCP e4m3 operands with one E8M0 (power-of-two) scale per row of A and of Bt (dword
 // arrays, byte 0), v_mfma_scale_f32_32x32x64_f8f6f4: M, N % 256 == 0, K % 256 == 0, lda / ldb in elements (= bytes)
 int launch_gemm_nt256_fp8(const unsigned char* A8, int lda, const uint32_t* scale_a, const unsigned char* Bt8, int ldb,
                           const uint32_t* scale_b, int M, int N, int K, const GemmEpilogue& ep, hipStream_t st);
 // rows of a bf16 matrix -> e4m3 bytes + one E8M0 scale per row (weights of the e4m3 GEMM path): any rows, K % 8 == 0, ld % 8 == 0
 int launch_quantize_rows_e4m3(const bf16_t* in, int ld, int rows, int K, unsigned char* out8, uint32_t* scale, hipStream_t st);
-// process-wide kernel-selection knobs (benchmark A/B; defaults are the fast paths). Keys: "gemm_nt256", "gemm_nt256_variant", "gemm_tn256".
+// process-wide kernel-selection knobs (benchmark A/B; defaults are the fast paths): keys, defaults and meanings in tuning.hip
 int smd_tuning_set(const char* key, int value);
 int smd_tuning_get(const char* key);
 
@@ -69,14 +70,12 @@ struct TnLaunch {
 size_t gemm_tn_slab_elems();
 // Weight-gradient GEMMs normally run on the engine's side stream next to the backward chain.  With the TWO-buffer 128-wide
 // kernel on their CU, the small 128-wide LayerNorm-backward kernels lost bitwise repeatability (round 3, DESIGN.md section 6:
-// a v_rsq_f32 directly behind the VALU that writes its source reads the stale register in lanes 48..63).  Knob
-// "tn_exclusive_cu": 2 (default) = the four-buffer kernels, unpadded (0 of 1499 repeats differ with any LayerNorm build);
-// 1 = the same kernels with a dynamic-LDS pad that fills the CU's 160 KiB (round-2 default); 0 = the two-buffer kernel (A/B only).
+// a v_rsq_f32 directly behind the VALU that writes its source reads the stale register in lanes 48..63).  Knob "tn_exclusive_cu"
+// (tuning.hip): the default 2 = four-buffer kernels, unpadded, shows 0 of 1499 repeats differing with any LayerNorm build.
 int smd_tn_pad_bytes(int static_lds_bytes);
 // 256x256 8-phase wgrad kernel (gemm_tn256.hip): plan returns nsplit (0 = not eligible)
 int gemm_tn256_plan(const TnLaunch& t, int* ktiles_per_split);
 int launch_gemm_tn256(const TnLaunch& t, int nsplit, int ktiles_per_split, hipStream_t st);
-int launch_gemm_tn256_pair(const TnLaunch& t0, const TnLaunch& t1, hipStream_t st);   // two problems, one launch
 #define SMD_TN256_MULTI_MAX 4
 int launch_gemm_tn256_multi(const TnLaunch* ts, int n, hipStream_t st);                 // 1..4 problems, one launch (4 x 64 tiles: no split-K)
 int launch_gemm_tn(const TnLaunch& t, hipStream_t st);

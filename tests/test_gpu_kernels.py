@@ -59,8 +59,13 @@ def test_probe_tr_read(L, dev):
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 384, 128), (300, 42, 192), (1000, 4096, 512),
                                    (8192, 2048, 2048), (64, 512, 2048), (512, 128, 2048), (96, 200, 1024),
-                                   (8192, 128, 2048), (2080, 512, 2048), (4000, 510, 2048)])
-# default forms (gemm_nt.hip): (64, 512, 2048) one 64-row tile per CU with two K-groups; (512, 128, 2048), (96, 200, 1024)
+                                   (8192, 128, 2048), (2080, 512, 2048), (4000, 510, 2048),
+                                   (32, 128, 64), (32, 128, 512), (32, 128, 1024), (32, 128, 1088), (64, 128, 64), (64, 128, 1024),
+                                   (2048, 128, 2048), (65536, 128, 64), (100, 130, 64)])
+# The last nine are the smallest shapes that reach each rule of smd_plan::nt_plan (gemm_plan.h) under the default knobs, as recorded in
+# tests/golden/gemm_dispatch.json: <32,2>, <32,4>, <32,3,2>, <32,4> again (K not a multiple of 128), <64,2>, <64,2,2>, the out_proj
+# rule <128,2,2>, <128,2>, and the 32-row form through the occupancy rule with ragged edges.
+# default forms (gemm_plan.h): (64, 512, 2048) one 64-row tile per CU with two K-groups; (512, 128, 2048), (96, 200, 1024)
 # 32-row tiles with two K-groups per workgroup.  The last three take the out_proj form (N <= 512,
 # K >= 2048, M >= 2048: 128-row tiles with two K-groups per workgroup): a full grid, a ragged M (2080 = 16 x 128 + 32) and an N
 # that is not a multiple of 4 (510: every pointer check of the quad epilogue fails, the scalar epilogue writes the tail columns)
