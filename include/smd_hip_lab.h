@@ -72,6 +72,30 @@ int smd_probe_l2_warm(const void* p, int64_t bytes, uint32_t* sink, void* stream
 /* lane-level probe of ds_read_b64_tr_b16 (debug): out[64][4] = values read from a 2 KiB linear image */
 int smd_probe_tr_read(const smd_bf16* image_1024, smd_bf16* out_256, void* stream);
 
+/* lab entry: the engine's own multi-problem weight-gradient launchers on a caller's problem list (tests/test_gpu_wgrad_groups.py).
+ * Problem i: dW_i[Kd][N] (row stride ldo) = X_i[Mrows][0:Kd]^T dY_i[Mrows][0:N], db_i[N] = column sums of dY_i (bias_out may be NULL);
+ * X / dY bf16 with ldx / ldy multiples of 8, every problem of a call with the same Mrows.
+ * kind 0: SmdEngine::flush_grouped_wgrads' launcher -- the 128x128-tile kernel, at most 8 problems per kernel launch (a longer list
+ *         takes several), one split-K factor per launch, slabs carved from the start of `slab`, one slab reduce; needs ldo == N;
+ * kind 1: SmdEngine::flush_pending256's launcher -- 1..4 problems the 256x256-tile kernel accepts (Kd, N multiples of 256, at least
+ *         8 K-tiles of 64 rows, ldo a multiple of 4, 16-byte aligned outputs; knob "gemm_tn256" 2 admits small grids) in one launch.
+ * zero_page: 128 zeroed bf16; slab / slab_elems: the split-K workspace (smd_gemm_tn_slab_elems() floats in the engine; a smaller
+ * one bounds the split factor of kind 0 and is an error where kind 1 cannot fit its partials).
+ * plan_out (may be NULL): plan_cap int32; for the j-th GEMM kernel launched, plan_out[3 j ..] = tiles (kind 1: of all problems),
+ * nsplit, ktiles_per_split -- the grid and kernel argument of that launch as the launcher passed them.  *launches_out (may be
+ * NULL) = number of GEMM kernel launches, also past plan_cap / 3.
+ * Argument errors (n < 1, n > 64, a null or misaligned operand, differing Mrows, ldo != N for kind 0, an ineligible problem or
+ * n > 4 or too small a slab for kind 1) return < 0 with smd_last_error() set and launch nothing. */
+typedef struct smd_wgrad_problem {
+  const smd_bf16* X;
+  const smd_bf16* dY;
+  float* out;
+  float* bias_out;
+  int32_t ldx, ldy, ldo, Mrows, Kd, N;
+} smd_wgrad_problem;
+int smd_wgrad_lab_launch(const smd_wgrad_problem* probs, int n, int kind, const smd_bf16* zero_page, float* slab, int64_t slab_elems,
+                         int32_t* plan_out, int plan_cap, int32_t* launches_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -513,6 +513,44 @@ int smd_bound_terms(const float* x0, const float* eps, const float* eps_hat, int
 
 int smd_probe_tr_read(const smd_bf16* image, smd_bf16* out, void* stream) { return launch_probe_tr_read(B(image), B(out), S(stream)); }
 
+// ---- lab entry: launch_gemm_tn_grouped / launch_gemm_tn256_multi on a caller's problem list (include/smd_hip_lab.h).  Everything
+// launch_tn128 checks per problem is checked here for the WHOLE list first: a list of more than 8 problems is several launches,
+// and a refusal must come before the first of them.  launch_gemm_tn256_multi makes all of its checks in front of its one launch.
+int smd_wgrad_lab_launch(const smd_wgrad_problem* probs, int n, int kind, const smd_bf16* zero_page, float* slab, int64_t slab_elems,
+                         int32_t* plan_out, int plan_cap, int32_t* launches_out, void* stream) {
+  constexpr int MAXP = 64;
+  if (launches_out) *launches_out = 0;
+  SMD_ARG_CHECK(probs && n >= 1 && n <= MAXP, "smd_wgrad_lab_launch: 1..%d problems", MAXP);
+  SMD_ARG_CHECK(kind == 0 || kind == 1, "smd_wgrad_lab_launch: kind must be 0 (grouped 128-wide) or 1 (256-wide multi)");
+  SMD_ARG_CHECK(zero_page && slab && slab_elems >= 0 && plan_cap >= 0, "smd_wgrad_lab_launch: needs a zero page and a slab workspace");
+  SMD_ARG_CHECK((reinterpret_cast<uintptr_t>(slab) & 15) == 0 && (reinterpret_cast<uintptr_t>(zero_page) & 15) == 0,
+                "smd_wgrad_lab_launch: slab and zero page must be 16-byte aligned");
+  TnLaunch ts[MAXP];
+  for (int i = 0; i < n; ++i) {
+    const smd_wgrad_problem& p = probs[i];
+    SMD_ARG_CHECK(p.X && p.dY && p.out, "smd_wgrad_lab_launch: problem %d: null operand", i);
+    SMD_ARG_CHECK(p.Mrows > 0 && p.Kd > 0 && p.N > 0, "smd_wgrad_lab_launch: problem %d: bad shape", i);
+    SMD_ARG_CHECK(p.Mrows == probs[0].Mrows, "smd_wgrad_lab_launch: problem %d: different contraction length (%d, problem 0 has %d)", i,
+                  p.Mrows, probs[0].Mrows);
+    SMD_ARG_CHECK(p.ldx % 8 == 0 && p.ldy % 8 == 0 && p.ldx >= p.Kd && p.ldy >= p.N && p.ldo >= p.N,
+                  "smd_wgrad_lab_launch: problem %d: ldx / ldy must be multiples of 8 and cover Kd / N, ldo >= N", i);
+    SMD_ARG_CHECK((reinterpret_cast<uintptr_t>(p.X) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.dY) & 15) == 0 &&
+                      (reinterpret_cast<uintptr_t>(p.out) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.bias_out) & 3) == 0,
+                  "smd_wgrad_lab_launch: problem %d: X / dY must be 16-byte aligned", i);
+    SMD_ARG_CHECK(kind != 0 || p.ldo == p.N, "smd_wgrad_lab_launch: problem %d: the grouped launch needs ldo == N", i);
+    TnLaunch& t = ts[i];
+    t.X = B(p.X); t.ldx = p.ldx; t.dY = B(p.dY); t.ldy = p.ldy; t.Mrows = p.Mrows; t.Kd = p.Kd; t.N = p.N;
+    t.out = p.out; t.ldo = p.ldo; t.bias_out = p.bias_out;
+    t.zero_page = B(zero_page); t.slab = slab; t.slab_elems = (size_t)slab_elems; t.tr_path = 1;
+  }
+  TnPlanLog log = {plan_out, plan_out ? plan_cap : 0, 0};
+  smd_tn_plan_log_install(&log);
+  const int rc = kind == 0 ? launch_gemm_tn_grouped(ts, n, S(stream)) : launch_gemm_tn256_multi(ts, n, S(stream));
+  smd_tn_plan_log_install(nullptr);
+  if (launches_out) *launches_out = log.launches;
+  return rc;
+}
+
 // ---- lab probe: a stream restricted by a raw CU mask (hipExtStreamCreateWithCUMask).  What the mask can express on this part is
 // documented in include/smd_hip_lab.h (tools/cumask_probe.hip: bit i belongs to XCC i % 8; an XCC whose share is empty is NOT masked).
 int smd_probe_stream_create_cu_mask(const uint32_t* mask_words, int n_words, void** stream_out) {

@@ -435,6 +435,16 @@ int smd_tn_pad_bytes(int static_lds_bytes) {
   return pad > 0 ? pad : 0;
 }
 
+// ---- lab report of the weight-gradient launches (smd_kernels.h): one log per host thread, off unless installed
+static thread_local TnPlanLog* g_tn_plan_log = nullptr;
+void smd_tn_plan_log_install(TnPlanLog* log) { g_tn_plan_log = log; }
+void smd_tn_plan_log_add(int tiles, int nsplit, int ktiles_per_split) {
+  TnPlanLog* l = g_tn_plan_log;
+  if (!l) return;
+  const int at = 3 * l->launches++;
+  if (l->out && at + 3 <= l->cap) { l->out[at] = tiles; l->out[at + 1] = nsplit; l->out[at + 2] = ktiles_per_split; }
+}
+
 static smd_plan::TnKnobs tn_knobs() {
   return {smd_tuning_get("tn128_target_wgs"), smd_tuning_get("tn_split_model"), smd_tuning_get("tn_exclusive_cu"), smd_tuning_get("gemm_tn_deep"),
           smd_tuning_get("tn128_loader_waves"), smd_tuning_get("tn_mode")};
@@ -459,6 +469,7 @@ static int smd_tn_launch_128(int tiles, int nsplit, const TnGroupArgs& ga, const
                   "four-buffer kernel with loader waves ships, the others need -DSMD_TN_EXPERIMENTS", m.mode);
     return -1;
   }
+  smd_tn_plan_log_add((int)grid.x, (int)grid.y, ga.p[0].ktiles_per_split);      // what was launched: the grid and the kernel's own argument
   return 0;
 }
 

@@ -405,6 +405,7 @@ int launch_gemm_tn256_multi(const TnLaunch* ts, int n, hipStream_t st) {
   }
   hipLaunchKernelGGL(gemm_tn256_kernel, dim3(ga.nwg_total), dim3(512), smd_tn_pad_bytes(SMEM_BYTES), st, ga);
   SMD_LAUNCH_CHECK();
+  smd_tn_plan_log_add(ga.nwg_total / nsplit, nsplit, ga.p[0].ktiles_per_split);     // grid = tiles_all x nsplit; the kernel's own argument
   for (int i = 0; i < n; ++i) {
     const TnLaunch& t = ts[i];
     if (nsplit > 1) {

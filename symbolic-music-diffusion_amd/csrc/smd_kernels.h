@@ -81,6 +81,12 @@ int launch_gemm_tn256_multi(const TnLaunch* ts, int n, hipStream_t st);         
 int launch_gemm_tn(const TnLaunch& t, hipStream_t st);
 // n wgrad problems with the same Mrows (ldo == N each) in grouped launches of the 128-wide kernel + one reduce
 int launch_gemm_tn_grouped(const TnLaunch* probs, int n, hipStream_t st);
+// Lab report (smd_wgrad_lab_launch, capi.hip): while a log is installed on the calling thread, launch_gemm_tn_grouped and
+// launch_gemm_tn256_multi append (tiles, nsplit, ktiles_per_split) of every GEMM kernel they launch -- the grid and kernel
+// arguments themselves, read where hipLaunchKernelGGL is called, not a second evaluation of the planner.
+struct TnPlanLog { int32_t* out; int cap; int launches; };    // `out`: cap int32 (triples; may be null), `launches` counts on past cap
+void smd_tn_plan_log_install(TnPlanLog* log);                // nullptr: off (the default)
+void smd_tn_plan_log_add(int tiles, int nsplit, int ktiles_per_split);
 int launch_transpose_bf16(const bf16_t* in, int ld_in, int rows, int cols, bf16_t* out, int ld_out,
                           hipStream_t st);
 // out[n] = sum_m dY[m][n]  (bias gradient), deterministic two-stage reduction via `partial`

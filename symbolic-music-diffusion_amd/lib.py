@@ -43,6 +43,12 @@ class SampleIO(C.Structure):
                 ("tf_t0", c_i32), ("key_ptr", c_void)]
 
 
+class WgradProblem(C.Structure):
+    """smd_wgrad_problem of include/smd_hip_lab.h"""
+    _fields_ = [("X", c_void), ("dY", c_void), ("out", c_void), ("bias_out", c_void),
+                ("ldx", c_i32), ("ldy", c_i32), ("ldo", c_i32), ("Mrows", c_i32), ("Kd", c_i32), ("N", c_i32)]
+
+
 class StridePlan(C.Structure):
     _fields_ = [("coef", c_void), ("plan", c_void), ("T", c_i32)]
 
@@ -176,6 +182,8 @@ _SIGS = {
     "smd_ddpm_reverse_step": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, c_u32,
                                         c_u32, c_u32, c_void, c_void, c_void, c_void]),
     "smd_probe_tr_read": (C.c_int, [c_void, c_void, c_void]),
+    "smd_wgrad_lab_launch": (C.c_int, [C.POINTER(WgradProblem), C.c_int, C.c_int, c_void, c_void, c_i64, C.POINTER(c_i32), C.c_int,
+                                       C.POINTER(c_i32), c_void]),
     "smd_probe_stream_create_cu_mask": (C.c_int, [C.POINTER(c_u32), C.c_int, C.POINTER(c_void)]),
     "smd_probe_stream_destroy": (C.c_int, [c_void]),
     "smd_pair_kernel_sums_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int]),

@@ -12,6 +12,7 @@ Every byte a kernel is allowed to touch is allocated and owned by the test: a st
 Entry point -> case (every entry of include/smd_hip.h that enqueues a kernel):
   smd_gemm_bf16_nt                               test_gemm_bf16_nt, test_gemm_bf16_nt_256_forced, ..._refuses_a_leading_dimension...
   smd_gemm_bf16_tn, smd_gemm_tn_slab_elems       test_gemm_bf16_tn, test_gemm_bf16_tn_256_forced
+  smd_wgrad_lab_launch (smd_hip_lab.h)           test_wgrad_lab_launch_grouped
   smd_quantize_rows_e4m3, smd_gemm_e4m3_nt       test_quantize_rows_e4m3_ragged, test_gemm_e4m3_nt
   smd_layernorm_fwd_e4m3                         test_layernorm_fwd_e4m3
   smd_gemm_f32, smd_layernorm_f32                test_gemm_f32, test_layernorm_f32
@@ -279,6 +280,43 @@ def test_gemm_bf16_tn_256_forced(L, dev):
         run_tn(L, dev, 1000, 512, 256, 512, 320, 256 + 4, 1)
     finally:
         lib.check(L.smd_set_tuning(b"gemm_tn256", 1))
+
+
+def test_wgrad_lab_launch_grouped(L, dev):
+    """A grouped launch of the 128-wide kernel (include/smd_hip_lab.h) writes its gradients, its bias rows and the first
+    nsplit * sum(stride) floats of the slab, nothing else: in_proj of C = 42 (Kd = 42, ldx = 64), out_proj of C = 42 (N = 42,
+    ldy = 64: the rows of dW are 42 floats, nothing behind the last one) and a 128 x 128 peer without a bias, over 1000 rows,
+    with a slab of exactly three splits' partials (the planner asks for more: the capacity binds)."""
+    import smd_amd.lib as lib
+    import _wgrad_ref as WR
+    Mrows, nsplit = 1000, 3
+    specs = [(42, 128, 64, 128, True), (256, 42, 256, 64, True), (128, 128, 128, 128, False)]
+    data = [tn_case(Mrows, Kd, N) for Kd, N, *_ in specs]
+    slab_elems = nsplit * sum((Kd * N + N + 3) // 4 * 4 for Kd, N, *_ in specs)
+    plans = []
+
+    def body(r):
+        arr = (lib.WgradProblem * len(specs))()
+        for i, (a, (Kd, N, ldx, ldy, wb), (X, Y, _, _)) in enumerate(zip(arr, specs, data)):
+            x, y = r.inp(X, ld=ldx, gemm=True), r.inp(Y, ld=ldy, gemm=True)
+            dw = r.out(f"dW{i}", (Kd, N), gemm=True)
+            db = r.out(f"db{i}", (N,)) if wb else None
+            a.X, a.dY, a.out, a.bias_out = P(x), P(y), P(dw), P(db)
+            a.ldx, a.ldy, a.ldo, a.Mrows, a.Kd, a.N = ldx, ldy, N, Mrows, Kd, N
+        zero = r.inp(torch.zeros(128, dtype=torch.bfloat16))
+        slab = r.out("slab", (slab_elems,), gemm=True)
+        plan, count = (ctypes.c_int32 * 6)(), ctypes.c_int32(0)
+        ck(L.smd_wgrad_lab_launch(arr, len(specs), 0, P(zero), P(slab), slab_elems, plan, 6, ctypes.byref(count), st()))
+        plans.append((count.value, tuple(plan[:3])))
+
+    got, _ = both(dev, body, unwritten=("slab",))        # the slab's rounding gaps and the bias row of problem 2 stay unwritten
+    assert plans == [(1, (1 + 2 + 1, nsplit, 6))] * 2, plans
+    for i, ((Kd, N, ldx, ldy, wb), (X, Y, ref, refb)) in enumerate(zip(specs, data)):
+        e = rel(got[f"dW{i}"], ref)
+        assert e < 3e-5                                  # test_gemm_tn
+        if wb:
+            assert rel(got[f"db{i}"], refb) < 3e-5
+        WR.check(got[f"dW{i}"], got[f"db{i}"] if wb else None, WR.reference(X, Y), Mrows, nsplit, what=f"problem {i}")
 
 
 # ================================================================================================ fp32 kernels

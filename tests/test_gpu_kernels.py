@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _wgrad_ref as WR
 import ddpm_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -227,6 +228,9 @@ def test_gemm_tn(L, dev, tr_path, M, Kd, N, ldx):
     print(f"gemm_tn tr={tr_path} M={M} Kd={Kd} N={N}: rel dW {e:.2e} db {eb:.2e}")
     assert e < 3e-5            # fp32 accumulation
     assert eb < 3e-5
+    if tr_path:                # element by element (tests/_wgrad_ref.py); 32 splits / 4 x 8 bias partial rows: the most either kernel takes
+        rW, rb = WR.check(out, db, WR.reference(Xd[:, :Kd], Yd[:, :N]), M, 32, what=f"gemm_tn M={M} Kd={Kd} N={N}")
+        print(f"   element-wise worst |err| / bound: dW {rW:.2e} db {rb:.2e}")
     if tr_path:                # split-K slabs are reduced in a fixed order: bitwise reproducible
         out2 = torch.empty_like(out)
         ck(L, L.smd_gemm_bf16_tn(P(Xd), ldx, P(Yd), ldy, M, Kd, N, P(out2), N, P(db), P(zero), P(slab), slab.numel(),
@@ -268,6 +272,9 @@ def test_gemm_tn256(L, dev, M, Kd, N, ldx, ldy):
     print(f"gemm_tn256 M={M} Kd={Kd} N={N}: rel dW {e:.2e} db {eb:.2e} vs 128-wide {e128:.2e}")
     assert e < 3e-5 and eb < 3e-5 and e128 < 3e-5
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    # element by element (tests/_wgrad_ref.py): at most 4 splits, bias from 4 x Kd / 256 partial rows
+    rW, rb = WR.check(outs[0][0], outs[0][1], WR.reference(Xd[:, :Kd], Yd[:, :N]), M, 4, Kd // 256, what=f"gemm_tn256 M={M} Kd={Kd} N={N}")
+    print(f"   element-wise worst |err| / bound: dW {rW:.2e} db {rb:.2e}")
 
 
 @pytest.mark.parametrize("rows,M", [(32, 128), (96, 256), (8192, 2048)])
