@@ -96,6 +96,33 @@ typedef struct smd_wgrad_problem {
 int smd_wgrad_lab_launch(const smd_wgrad_problem* probs, int n, int kind, const smd_bf16* zero_page, float* slab, int64_t slab_elems,
                          int32_t* plan_out, int plan_cap, int32_t* launches_out, void* stream);
 
+/* lab entry: launch_gemm_nt, the launcher of every Dense forward and dgrad, with a full epilogue (tests/test_gpu_gemm_nt_epilogue.py).
+ * C[M][N] = A[M][0:K] Bt[N][0:K]^T on bf16 operands (K a multiple of 64, lda / ldb multiples of 8 and >= K, A / Bt 16-byte aligned),
+ * then, per element and in this order (GemmEpilogue, csrc/smd_kernels.h):
+ *   v = alpha * acc + bias[col];  pre_bf16 <- v;  v = act(v) (0 none, 1 tanh-GELU, 2 swish);  v *= act'(aux[row][col]) (aux_mode 0
+ *   none, 1 GELU', 2 swish');  v += res_f32[res_row_mod > 0 ? row % res_row_mod : row][col];  v += res_bf16[row][col];
+ *   out_f32 (accumulate ? += : =) v;  out_bf16 <- v.
+ * Every pointer of the epilogue may be NULL (at least one of pre_bf16 / out_f32 / out_bf16 is needed); out_f32 may be res_f32.
+ * min_tiles: grid size from which an eligible shape goes to the 256 x 256 kernel (<= 0: the library's default).
+ * plan_out (may be NULL): 8 int32 = the smd_plan::NtPlan the launcher ran with, handed out by the launcher itself: kernel (128 /
+ * 256), BM, NS, KG, grid, block, pk_epilogue, vec_epilogue.
+ * Argument errors (act / aux_mode outside 0..2, aux_mode without aux, a non-null epilogue tensor with ld < N, res_row_mod < 0, the
+ * launcher's own lda / ldb / K / no-output rules) return < 0 with smd_last_error() set; nothing is launched, plan_out is untouched. */
+typedef struct smd_gemm_epilogue {
+  float alpha;
+  int32_t act;
+  const float* bias;
+  smd_bf16* pre_bf16;
+  const smd_bf16* aux;
+  const float* res_f32;
+  const smd_bf16* res_bf16;
+  float* out_f32;
+  smd_bf16* out_bf16;
+  int32_t ld_pre, ld_aux, aux_mode, ld_res, res_row_mod, ld_resb, ld_out, accumulate, ld_outb;
+} smd_gemm_epilogue;
+int smd_gemm_nt_lab(const smd_bf16* A, int lda, const smd_bf16* Bt, int ldb, int M, int N, int K, const smd_gemm_epilogue* ep,
+                    int min_tiles, int32_t* plan_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

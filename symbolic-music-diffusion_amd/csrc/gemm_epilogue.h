@@ -64,11 +64,12 @@ __device__ __forceinline__ void epilogue_quad(const float4 a, int row, int col, 
     }
     if (ep.out_f32) {
       float4* o = reinterpret_cast<float4*>(ep.out_f32 + (size_t)row * ep.ld_out + col);
-      if (ep.accumulate) {
+      if (ep.accumulate) {            // out_bf16 below takes v, not the accumulated sum (as epilogue_scalar and GemmEpilogue say)
         const float4 c = *o;
-        v[0] += c.x; v[1] += c.y; v[2] += c.z; v[3] += c.w;
+        *o = make_float4(c.x + v[0], c.y + v[1], c.z + v[2], c.w + v[3]);
+      } else {
+        *o = make_float4(v[0], v[1], v[2], v[3]);
       }
-      *o = make_float4(v[0], v[1], v[2], v[3]);
     }
     if (ep.out_bf16) {
       bf16x4_t p;

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_nt_kernel(const bf16_t* __restr
 
 // Which kernel and tile form a shape gets is decided by smd_plan::nt_plan (gemm_plan.h); this function checks, asks, launches.
 int launch_gemm_nt(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, int N, int K,
-                   const GemmEpilogue& ep, hipStream_t st, int min_tiles) {
+                   const GemmEpilogue& ep, hipStream_t st, int min_tiles, smd_plan::NtPlan* plan_out) {
   SMD_ARG_CHECK(A && Bt, "gemm_nt: null operand");
   SMD_ARG_CHECK(M > 0 && N > 0 && K > 0, "gemm_nt: bad shape M=%d N=%d K=%d", M, N, K);
   SMD_ARG_CHECK(K % BK == 0, "gemm_nt: K=%d must be a multiple of %d (pad the operands)", K, BK);
@@ -216,7 +216,11 @@ int launch_gemm_nt(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, i
   const smd_plan::NtKnobs knobs = {smd_tuning_get("gemm_nt256"), smd_tuning_get("gemm_nt256_pk"), smd_tuning_get("gemm_nt_deep"),
                                    smd_tuning_get("gemm_nt_kg"), smd_tuning_get("gemm_nt_form"), smd_tuning_get("gemm_nt_form_wk")};
   const smd_plan::NtPlan p = smd_plan::nt_plan(M, N, K, smd_epi::plan_flags(ep), min_tiles, knobs);
-  if (p.kernel == smd_plan::NT256) return launch_gemm_nt256(A, lda, Bt, ldb, M, N, K, ep, p.pk_epilogue, st);
+  if (p.kernel == smd_plan::NT256) {
+    const int rc = launch_gemm_nt256(A, lda, Bt, ldb, M, N, K, ep, p.pk_epilogue, st);
+    if (rc == 0 && plan_out) *plan_out = p;
+    return rc;
+  }
 #define SMD_NT_FORM(BM_, NS_, KG_)                                                                                                   \
   case BM_ * 100 + NS_ * 10 + KG_:                                                                                                   \
     hipLaunchKernelGGL((gemm_nt_kernel<BM_, NS_, KG_>), dim3(p.grid), dim3(p.block), 0, st, A, lda, Bt, ldb, M, N, K, (N + BN - 1) / BN, \
@@ -230,5 +234,6 @@ int launch_gemm_nt(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, i
   }
 #undef SMD_NT_FORM
   SMD_LAUNCH_CHECK();
+  if (plan_out) *plan_out = p;
   return 0;
 }

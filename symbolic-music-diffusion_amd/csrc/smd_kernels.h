@@ -34,9 +34,11 @@ struct GemmEpilogue {
 };
 
 // C[M,N] = A[M,K] * Bt[N,K]^T   (both operands K-contiguous bf16; K % 64 == 0; lda,ldb % 8 == 0).  Kernel and tile form:
-// smd_plan::nt_plan (gemm_plan.h); min_tiles = grid size from which the 256x256 kernel takes an eligible shape
+// smd_plan::nt_plan (gemm_plan.h); min_tiles = grid size from which the 256x256 kernel takes an eligible shape;
+// plan_out (nullable) receives the plan this launch ran with (lab entry smd_gemm_nt_lab; untouched when the launch is refused)
 int launch_gemm_nt(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, int N, int K,
-                   const GemmEpilogue& ep, hipStream_t st, int min_tiles = smd_plan::NT256_MIN_TILES);
+                   const GemmEpilogue& ep, hipStream_t st, int min_tiles = smd_plan::NT256_MIN_TILES,
+                   smd_plan::NtPlan* plan_out = nullptr);
 
 // 256x256x64 8-phase kernel (gemm_nt256.hip); launch_gemm_nt dispatches to it when the plan says so
 int launch_gemm_nt256(const bf16_t* A, int lda, const bf16_t* Bt, int ldb, int M, int N, int K,

@@ -49,6 +49,14 @@ class WgradProblem(C.Structure):
                 ("ldx", c_i32), ("ldy", c_i32), ("ldo", c_i32), ("Mrows", c_i32), ("Kd", c_i32), ("N", c_i32)]
 
 
+class GemmEpilogue(C.Structure):
+    """smd_gemm_epilogue of include/smd_hip_lab.h"""
+    _fields_ = [("alpha", C.c_float), ("act", c_i32), ("bias", c_void), ("pre_bf16", c_void), ("aux", c_void), ("res_f32", c_void),
+                ("res_bf16", c_void), ("out_f32", c_void), ("out_bf16", c_void), ("ld_pre", c_i32), ("ld_aux", c_i32),
+                ("aux_mode", c_i32), ("ld_res", c_i32), ("res_row_mod", c_i32), ("ld_resb", c_i32), ("ld_out", c_i32),
+                ("accumulate", c_i32), ("ld_outb", c_i32)]
+
+
 class StridePlan(C.Structure):
     _fields_ = [("coef", c_void), ("plan", c_void), ("T", c_i32)]
 
@@ -184,6 +192,8 @@ _SIGS = {
     "smd_probe_tr_read": (C.c_int, [c_void, c_void, c_void]),
     "smd_wgrad_lab_launch": (C.c_int, [C.POINTER(WgradProblem), C.c_int, C.c_int, c_void, c_void, c_i64, C.POINTER(c_i32), C.c_int,
                                        C.POINTER(c_i32), c_void]),
+    "smd_gemm_nt_lab": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GemmEpilogue), C.c_int,
+                                  C.POINTER(c_i32), c_void]),
     "smd_probe_stream_create_cu_mask": (C.c_int, [C.POINTER(c_u32), C.c_int, C.POINTER(c_void)]),
     "smd_probe_stream_destroy": (C.c_int, [c_void]),
     "smd_pair_kernel_sums_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int]),

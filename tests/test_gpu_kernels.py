@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import _nt_ref as NR
 import _wgrad_ref as WR
 import ddpm_oracle as O
 
@@ -95,6 +96,7 @@ def test_gemm_nt_epilogues(L, dev):
     bias, res = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
     z = A.double() @ Bt.double().t() + bias.double()
     Ad, Bd, bd, rd = A.to(dev), Bt.to(dev), bias.to(dev), res.to(dev)     # keep alive until the sync
+    prob = NR.problem_from(A, Bt, bias, res)
     for act, fn in ((1, lambda v: O.gelu(v)), (2, lambda v: O.swish(v))):
         ref = fn(z) + res.double()
         out = torch.empty(M, N, device=dev)
@@ -104,12 +106,16 @@ def test_gemm_nt_epilogues(L, dev):
         e = rel(out, ref)
         print(f"gemm_nt epilogue act={act}: rel {e:.2e}")
         assert e < 1e-4        # fast-math exp in gelu/swish
+        # and element by element (tests/_nt_ref.py; KG = 2: the bound of whichever form the planner picks)
+        r = NR.check({"f32": out.double().cpu()}, NR.reference(prob, NR.Ep("act+res", bias=True, act=act, res=True, f32=True), KG=2), what=f"act={act}")
+        print(f"gemm_nt epilogue act={act}: worst |err| / bound {r['f32']:.3f}")
     # in-place residual stream: out == residual buffer
     buf = res.clone().to(dev)
     ck(L, L.smd_gemm_bf16_nt(P(Ad), K, P(Bd), K, M, N, K, P(bd), 0, P(buf), N, P(buf), N,
                              None, 0, st()))
     torch.cuda.synchronize()
     assert rel(buf, z + res.double()) < 2e-5
+    NR.check({"f32": buf.double().cpu()}, NR.reference(prob, NR.Ep("in-place", bias=True, res=True, f32=True), KG=2), what="in place")
 
 
 @pytest.mark.parametrize("variant", [0, 1])
@@ -138,6 +144,11 @@ def test_gemm_nt256_forced(L, dev, M, N, K, variant):
     e, eb, e2 = rel(out, z), rel(outb.float(), z), rel(out2, O.gelu(z) + res.double())
     print(f"gemm_nt256 v{variant} {M}x{N}x{K}: rel fp32 {e:.2e} bf16 {eb:.2e} gelu+res {e2:.2e}")
     assert e < 2e-5 and eb < 4e-3 and e2 < 1e-4
+    # and element by element (tests/_nt_ref.py)
+    prob = NR.problem_from(A, Bt, bias, res)
+    r = NR.check({"f32": out.double().cpu(), "b16": outb.double().cpu()}, NR.reference(prob, NR.Ep("bias", bias=True, f32=True, b16=True)), what="bias")
+    r2 = NR.check({"f32": out2.double().cpu()}, NR.reference(prob, NR.Ep("gelu+res", bias=True, act=1, res=True, f32=True)), what="gelu + residual")
+    print(f"gemm_nt256 v{variant} {M}x{N}x{K}: worst |err| / bound fp32 {r['f32']:.3f} bf16 {r['b16']:.3f} gelu+res {r2['f32']:.3f}")
 
 
 def test_gemm_nt256_matches_128_tiles_and_is_deterministic(L, dev):
