@@ -232,6 +232,28 @@ typedef struct smd_stride_plan {
 } smd_stride_plan;
 int smd_engine_strided_step(smd_engine* e, const smd_sample_io* io, const smd_stride_plan* plan, int part, void* stream);
 
+/* One iteration of a MULTISTEP walk down a sub-sequence of the timesteps: DPM-Solver++(2M) of Lu et al. 2022 (Algorithm 2, data
+ * prediction; no counterpart in the reference), the deterministic strided step with one more term from the chain's history:
+ *   coef[t] = (sqrt(1/ap_t), sqrt(1-ap_t)/sqrt(ap_t), a0, b, unused, clip, sqrt(ap_s), sqrt(1-ap_s), a1, 0, 0, 0)
+ *   plan[t] = (next_t, iteration, slot, 0)                                       as for smd_engine_strided_step
+ *   x0 = clamp(coef0 x - coef1 eps_hat, -clip, clip) (rounded once, as there);  x' = a0 x0 + a1 x0_prev + b x;  infill as there;
+ *   x0_prev = x0 (the clamped value just used, before the infill blend).
+ * x0_prev is one fp32 array of the state's shape per chain, owned by the caller.  It is read only where a1 != 0 and always
+ * written, so the first iteration of a walk (a1 = 0: no history yet) does not depend on what the array holds; a1 = 0 everywhere is
+ * smd_engine_strided_step at sigma = 0, bit for bit.  There is no noise term: io->z_in and io->tf_noise_keys are not used and
+ * the noise-norm partial is that of zeros.  Everything else -- the infill draws (infill_z_in, else tf_infill_keys row
+ * `iteration`, else Philox keyed by t), the bf16 network input, the collection row, metrics_partial[t], the last workgroup's
+ * store of next_t, the no-op for t outside [0, T) or off the walk, `part` and its refusal under option "fp32" -- is as for
+ * smd_engine_strided_step.  plan->T must be the engine's num_timesteps; the plan rows, and for data_channels % 4 == 0 every
+ * fp32 array, x0_prev included, 16-byte aligned. */
+typedef struct smd_multistep_plan {
+  const float* coef;               /* [T][12] */
+  const int32_t* plan;             /* [T][4] */
+  int32_t T;
+} smd_multistep_plan;
+int smd_engine_multistep_step(smd_engine* e, const smd_sample_io* io, const smd_multistep_plan* plan, float* x0_prev, int part,
+                              void* stream);
+
 /* One iteration of a walk that evaluates the variational bound of Ho et al. 2020 (eq. 5) term by term on held-out examples (no
  * counterpart in the reference).  At t = *t_ptr:
  *   smd_bound_noise   x_t = sqrt(ap_t) x0 + sqrt(1-ap_t) eps  -> x_t (fp32) and the engine's bf16 network input

@@ -2,7 +2,8 @@
 --sampling_dir`` on the MI355X HIP engine: unconditional generation, infilling (--infill) and
 interpolation (--interpolate) for DDPM checkpoints, writing {sampling_dir}/ncsn/{generated,
 collection,real}.pkl in the reference's layout (sample_ncsn.py:368-471).  --ddim_steps=K walks K of the
-schedule's timesteps with the strided (DDIM) sampler instead of all of them, in all three modes.  --compute_bound
+schedule's timesteps with the strided (DDIM) sampler instead of all of them, in all three modes.  --ddim_order=2
+--ddim_spacing=logsnr makes that walk the second-order multistep solver DPM-Solver++(2M) on a lambda-uniform grid.  --compute_bound
 evaluates the per-timestep variational bound on the eval examples first (--bound_only: and stops there).
 
 Multi-GPU sampling is embarrassingly parallel: under torch.distributed.run each rank generates a
@@ -58,7 +59,8 @@ def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sampl
     generated, collection, ld_metrics = ncsn.sample(
         model, sigmas, sample_rng, sample_shape, num_samples=num_samples, sampling=FLAGS.sampling,
         epsilon=FLAGS.ld_epsilon, steps=FLAGS.ld_steps, denoise=FLAGS.denoise, sample_offset=sample_offset,
-        use_graph=FLAGS.graph, global_num_samples=global_num_samples, ddim_steps=FLAGS.ddim_steps, ddim_eta=FLAGS.ddim_eta)
+        use_graph=FLAGS.graph, global_num_samples=global_num_samples, ddim_steps=FLAGS.ddim_steps, ddim_eta=FLAGS.ddim_eta,
+        ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing)
     torch.cuda.synchronize()
     log.info("Generated samples in %f seconds", time.time() - t0)
     return generated, collection, ld_metrics
@@ -86,7 +88,8 @@ def infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=0, g
     if FLAGS.ddim_steps:
         generated, collection, ld_metrics = ncsn.strided_dynamics(
             ld_rng, model, sigmas, init, FLAGS.ddim_steps, FLAGS.ddim_eta, True, infill_samples=samples, infill_masks=masks,
-            use_graph=FLAGS.graph, sample_offset=sample_offset, global_num_samples=global_num_samples)
+            use_graph=FLAGS.graph, sample_offset=sample_offset, global_num_samples=global_num_samples, order=FLAGS.ddim_order,
+            spacing=FLAGS.ddim_spacing)
         return generated, collection, ncsn.collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = ncsn.diffusion_dynamics(
         ld_rng, model, sigmas, init, FLAGS.ld_epsilon, FLAGS.ld_steps, FLAGS.denoise, True,
@@ -113,12 +116,13 @@ def diffusion_stochastic_encoder(samples, sigmas, rng, device="cuda:0", sample_o
 
 
 def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl, dev, use_graph=True, points=9, ddim_steps=0,
-                        ddim_eta=0.0, ddim_encode=False):
+                        ddim_eta=0.0, ddim_encode=False, ddim_order=1, ddim_spacing="uniform"):
     """sample_ncsn.py:425-435 + diffusion_decoder (:269-310) for this rank's rows [lo, hi): goals = roll(starts, 1); both are
     encoded with the same key (the same noise); every one of the 9 interpolated latents is decoded with the SAME
     ld_rng = split(PRNGKey(sample_seed), 3)[1].  Returns (generated (9, n, ...), collection (9, 41, n, ...), collated metrics).
     ``ddim_steps`` > 0: the points are decoded with the strided sampler; with ``ddim_encode`` starts and goals are encoded by its
-    deterministic inversion (ncsn.ddim_encode) instead of the single re-noising."""
+    deterministic inversion (ncsn.ddim_encode) instead of the single re-noising.  ``ddim_order`` / ``ddim_spacing``: the solver
+    and the grid of the decoding walks (ncsn.strided_dynamics)."""
     from smd_amd import ncsn
     num = len(real)
     starts = real[lo:hi]
@@ -134,7 +138,7 @@ def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl,
         z = ((1 - alpha) * zs + alpha * zg).astype(np.float32)
         if ddim_steps:
             g, c, ld = ncsn.strided_dynamics(ld_rng, model, sigmas, z, ddim_steps, ddim_eta, use_graph=use_graph, sample_offset=lo,
-                                             global_num_samples=num)
+                                             global_num_samples=num, order=ddim_order, spacing=ddim_spacing)
         else:
             g, c, ld = ncsn.diffusion_dynamics(ld_rng, model, sigmas, z, use_graph=use_graph, sample_offset=lo, global_num_samples=num)
         gens.append(g.cpu().numpy())
@@ -231,8 +235,9 @@ def check_cluster_flags(FLAGS):
 
 
 def check_ddim_flags(FLAGS):
-    """the refusals of --ddim_steps / --ddim_eta / --ddim_encode, before the GPU is touched"""
+    """the refusals of --ddim_steps / --ddim_eta / --ddim_encode / --ddim_order / --ddim_spacing, before the GPU is touched"""
     used = [f"--{n}" for n in ("ddim_steps", "ddim_eta", "ddim_encode") if FLAGS.is_present(n) and getattr(FLAGS, n)]
+    used += [f"--{n}" for n, off in (("ddim_order", 1), ("ddim_spacing", "uniform")) if FLAGS.is_present(n) and getattr(FLAGS, n) != off]
     if used and FLAGS.sampling != "ddpm":
         raise SystemExit(f"{', '.join(used)}: the strided sampler walks a DDPM schedule, it needs --sampling=ddpm (got --sampling={FLAGS.sampling})")
     steps = FLAGS.ddim_steps
@@ -244,6 +249,20 @@ def check_ddim_flags(FLAGS):
         raise SystemExit("--ddim_eta / --ddim_encode belong to the strided sampler: give --ddim_steps")
     if FLAGS.ddim_encode and not FLAGS.interpolate:
         raise SystemExit("--ddim_encode replaces the encoder of --interpolate: it needs --interpolate")
+    order, spacing = FLAGS.ddim_order, FLAGS.ddim_spacing
+    if order not in (1, 2):
+        raise SystemExit(f"--ddim_order={order}: 1 (the strided update, DDIM) or 2 (DPM-Solver++(2M))")
+    if (order != 1 or spacing != "uniform") and not steps:
+        raise SystemExit("--ddim_order / --ddim_spacing belong to the strided sampler: give --ddim_steps")
+    if order == 2 and FLAGS.ddim_eta != 0:
+        raise SystemExit(f"--ddim_order=2 is a deterministic solver: it needs --ddim_eta=0 (got --ddim_eta={FLAGS.ddim_eta})")
+    if order == 2 and FLAGS.ddim_encode:
+        raise SystemExit("--ddim_order=2 with --ddim_encode: the inversion is first order, so encoding and decoding would not be the "
+                         "same solver; use --ddim_order=1 or the stochastic encoder")
+    if order == 2 and spacing == "uniform":
+        log.warning("--ddim_order=2 --ddim_spacing=uniform: on a grid that is uniform in t the second-order update is LESS accurate "
+                    "than --ddim_order=1 at the same --ddim_steps (history weight up to 3.7; DESIGN.md section 18, the table): "
+                    "use --ddim_spacing=logsnr")
 
 
 def check_bound_flags(FLAGS):
@@ -382,7 +401,8 @@ def main(argv):
     elif FLAGS.interpolate:                                                 # :425-435
         generated, collection, ld_metrics = interpolate_samples(model, sigmas, real, lo, hi, rng, FLAGS.sample_seed, FLAGS.rng_impl,
                                                                 dev, FLAGS.graph, ddim_steps=FLAGS.ddim_steps,
-                                                                ddim_eta=FLAGS.ddim_eta, ddim_encode=FLAGS.ddim_encode)
+                                                                ddim_eta=FLAGS.ddim_eta, ddim_encode=FLAGS.ddim_encode,
+                                                                ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing)
     else:                                                                   # :437-439
         generated, collection, ld_metrics = generate_samples(FLAGS, model, rng, shape, hi - lo, sigmas, sample_offset=lo,
                                                              global_num_samples=num)

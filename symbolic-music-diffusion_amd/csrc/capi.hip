@@ -225,6 +225,14 @@ int smd_engine_strided_step(smd_engine* e, const smd_sample_io* io, const smd_st
   p.coef = plan->coef; p.plan = plan->plan; p.T = plan->T;
   return e->impl.strided_step(sample_io(io), p, S(stream), part);
 }
+int smd_engine_multistep_step(smd_engine* e, const smd_sample_io* io, const smd_multistep_plan* plan, float* x0_prev, int part,
+                              void* stream) {
+  NEED(e);
+  SMD_ARG_CHECK(io && plan, "multistep_step: null io / plan");
+  MultistepPlan p;
+  p.coef = plan->coef; p.plan = plan->plan; p.T = plan->T;
+  return e->impl.multistep_step(sample_io(io), p, x0_prev, S(stream), part);
+}
 int smd_engine_bound_step(smd_engine* e, const smd_bound_io* io, void* stream) {
   NEED(e);
   SMD_ARG_CHECK(io, "bound_step: null io");

@@ -5,6 +5,7 @@
 //   mse_loss_grad    mean((eps-pred)^2) and d/dpred            utils/losses.py:304-308
 //   reverse_step     one sample_with_beta iteration            utils/ebm_utils.py:327-394
 //   strided_step     one DDIM iteration / inversion step on a sub-sequence of the timesteps (no reference counterpart)
+//   multistep_step   one DPM-Solver++(2M) iteration on such a sub-sequence: the strided step with one array of history
 //
 // All per-step scalars (timestep t, optimiser step) are read from device memory so the whole
 // step is hipGraph-replayable with frozen kernel arguments.
@@ -565,6 +566,166 @@ __global__ __launch_bounds__(128 * RG) void strided_step_kernel(StridedStepArgs 
   }
 }
 
+// ------------------------------------------------------------------ multistep (DPM-Solver++(2M)) step
+// The second-order multistep update of Lu et al. 2022 (Algorithm 2, data prediction) on the layout of strided_step_kernel: one
+// more state array, the clamped x0 of the chain's previous iteration.  coef[t] = (sqrt_recip, sqrt_m1, a0, b, -, clip, sqrt_as,
+// sqrt_1m_as, a1, -, -, -), plan[t] as for the strided step:
+//   x0 = clamp(sqrt_recip x - sqrt_m1 eps_hat, -clip, clip);  x' = a0 x0 + a1 x0_prev + b x;  infill at the level of next_t;
+//   x0_prev = x0 (the value just used, before the infill blend).
+// Deterministic: there is no noise term, and the z-norm metric is the norm of zeros, as the strided step's at sigma = 0.
+// a1 == 0 (the first and the last iteration, every iteration at order 1): x0_prev is not read, so whatever an earlier walk
+// left there cannot reach the state.  The shared lines are repeated as in strided_step_kernel (follow-up).
+template <int VEC, int RG>
+__global__ __launch_bounds__(128 * RG) void multistep_step_kernel(MultistepStepArgs a) {
+  __shared__ float red[2][3];
+  __shared__ float part[RG > 1 ? RG : 1][2][128 * VEC];
+  const int b = blockIdx.x;
+  const int ct = threadIdx.x & 127, rg = threadIdx.x >> 7;
+  const int t = *a.t_ptr;
+  if (t < 0 || t >= a.T) return;          // the walk's terminator (or a bad timestep): a no-op, t is not advanced either
+  const int4 pl = *reinterpret_cast<const int4*>(a.plan + (size_t)t * 4);
+  const int next_t = pl.x, iter = pl.y;
+  if (iter < 0) return;
+  const float* cf = a.coef + (size_t)t * SMD_MULTISTEP_COLUMNS;
+  const float sqrt_recip = cf[0], sqrt_m1 = cf[1], ca0 = cf[2], cb = cf[3], clip = cf[5];
+  const float sqrt_as = cf[6], sqrt_1m_as = cf[7], ca1 = cf[8];
+  const bool history = ca1 != 0.0f;
+  const bool next_live = next_t >= 0 && next_t < a.T;       // the state being produced is still a noisy level
+  int slot = a.collection ? pl.z : -1;
+  if (slot > 40) slot = -1;               // the collection has 41 rows; out-of-range scatters are dropped
+  const uint32_t bglob = (uint32_t)b + a.sample_offset;
+  const size_t sample_base = (size_t)b * a.S * a.C;
+  const uint64_t tf_base = (uint64_t)bglob * a.S * a.C;       // this sample's first element in the global jax array
+  const uint32_t key_lo = a.key_ptr ? a.key_ptr[0] : a.key.seed_lo, key_hi = a.key_ptr ? a.key_ptr[1] : a.key.seed_hi;
+  TfKey tf_ik{0, 0};
+  if (a.tf_infill_keys) { tf_ik.k0 = a.tf_infill_keys[2 * iter]; tf_ik.k1 = a.tf_infill_keys[2 * iter + 1]; }
+  float m_eps = 0.f, m_step = 0.f, m_z = 0.f;
+  for (int cb0 = 0; cb0 < a.C; cb0 += 128 * VEC) {          // uniform trip count: the LDS combine below has barriers
+    const int col0 = cb0 + ct * VEC;
+    const bool live = col0 < a.C;
+    float acc_e[VEC], acc_s[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc_e[v] = acc_s[v] = 0.f;
+    for (int s = rg; live && s < a.S; s += RG) {
+      const int e = s * a.C + col0;
+      const size_t idx = sample_base + e;
+      float x[VEC], eh[VEC], hp[VEC], x0[VEC], nx[VEC];
+      ldv<VEC>(a.x + idx, x);
+      ldv<VEC>(a.eps_hat + idx, eh);
+      if (history) {
+        ldv<VEC>(a.x0_prev + idx, hp);
+      } else {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) hp[v] = 0.f;
+      }
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        // x0 rounded once, as in strided_step_kernel: p + perr is sqrt_m1 * eps_hat exactly
+        const float p = sqrt_m1 * eh[v];
+        const float perr = __builtin_fmaf(sqrt_m1, eh[v], -p);
+        float recon = __builtin_fmaf(sqrt_recip, x[v], -p) - perr;
+        recon = fminf(fmaxf(recon, -clip), clip);                 // clip = inf: no clamp
+        x0[v] = recon;
+        nx[v] = __builtin_fmaf(ca0, recon, __builtin_fmaf(ca1, hp[v], cb * x[v]));
+      }
+      if (a.infill_masks) {
+        float im[VEC], is[VEC], iz[VEC];
+        ldv<VEC>(a.infill_masks + idx, im);
+        ldv<VEC>(a.infill_samples + idx, is);
+        if (next_live) {
+          if (a.infill_z_in) {
+            ldv<VEC>(a.infill_z_in + idx, iz);
+          } else if (a.tf_infill_keys) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) iz[v] = jax_normal_from_bits(jax_bits_at(tf_ik, tf_base + e + v, (uint64_t)a.tf_n_total));
+          } else {
+            const float4 n4 = philox_normal4((uint32_t)(e >> 2), bglob, SMD_STREAM_INFILL, (uint32_t)t, key_lo, key_hi);
+            if constexpr (VEC == 4) { iz[0] = n4.x; iz[1] = n4.y; iz[2] = n4.z; iz[3] = n4.w; }
+            else iz[0] = pick4(n4, e & 3);
+          }
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          // the known region at the noise level of the state being PRODUCED (next_t), the clean samples at the end
+          const float y = next_live ? __builtin_fmaf(sqrt_as, is[v], sqrt_1m_as * iz[v]) : is[v];
+          nx[v] = nx[v] * (1.0f - im[v]) + y * im[v];
+        }
+      }
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        const float st = x[v] - nx[v];
+        acc_e[v] += eh[v] * eh[v];
+        acc_s[v] += st * st;
+      }
+      stv<VEC>(a.x + idx, nx);
+      stv<VEC>(a.x0_prev + idx, x0);                              // the next iteration's history: this thread's own elements
+      if (slot >= 0) stv<VEC>(a.collection + ((size_t)slot * a.B) * a.S * a.C + idx, nx);
+      if (a.x_bf16) {
+        bf16_t* xb = a.x_bf16 + ((size_t)b * a.S + s) * a.Cp + col0;
+        if constexpr (VEC == 4) {
+          bf16x4_t pk;
+#pragma unroll
+          for (int v = 0; v < 4; ++v) pk[v] = f2bf(nx[v]);
+          *reinterpret_cast<bf16x4_t*>(xb) = pk;
+        } else {
+          xb[0] = f2bf(nx[0]);
+        }
+      }
+    }
+    if constexpr (RG > 1) {
+      __syncthreads();
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        part[rg][0][ct * VEC + v] = acc_e[v]; part[rg][1][ct * VEC + v] = acc_s[v];
+      }
+      __syncthreads();
+      if (rg == 0) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          float se = 0.f, ss = 0.f;
+#pragma unroll
+          for (int g2 = 0; g2 < RG; ++g2) {
+            se += part[g2][0][ct * VEC + v]; ss += part[g2][1][ct * VEC + v];
+          }
+          acc_e[v] = se; acc_s[v] = ss;
+        }
+      }
+    }
+    // sqrt(sum(v^2, axis=1) + 1e-10) as in reverse_step_kernel: axis 1 is the sequence axis, the channel axis for S == 1;
+    // the noise is identically zero, so its sum of squares is
+    if (rg == 0 && live)
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      if (a.S > 1) {
+        m_eps += sqrtf(acc_e[v] + 1e-10f);
+        m_step += sqrtf(acc_s[v] + 1e-10f);
+        m_z += sqrtf(1e-10f);
+      } else {
+        m_eps += acc_e[v]; m_step += acc_s[v];
+      }
+    }
+  }
+  if (a.metrics_partial) {
+    m_eps = wave_sum(m_eps); m_step = wave_sum(m_step); m_z = wave_sum(m_z);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0 && w < 2) { red[w][0] = m_eps; red[w][1] = m_step; red[w][2] = m_z; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+      float v = red[0][threadIdx.x] + red[1][threadIdx.x];
+      if (a.S == 1) v = sqrtf(v + 1e-10f);
+      a.metrics_partial[((size_t)t * a.B + b) * 3 + threadIdx.x] = v;
+    }
+  }
+  // *t_advance = plan[t].next_t by the LAST workgroup to get here, as in strided_step_kernel
+  if (a.t_advance && threadIdx.x == 0) {
+    const unsigned prev = __hip_atomic_fetch_add(a.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (prev == gridDim.x - 1) {
+      __hip_atomic_exchange(a.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(a.t_advance, next_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 __global__ void advance_t_kernel(int* t_ptr) { *t_ptr -= 1; }
 __global__ void set_t_kernel(int* t_ptr, int v) { *t_ptr = v; }
 
@@ -773,6 +934,34 @@ int launch_strided_step(const StridedStepArgs& a, hipStream_t st) {
   } else {
     if (vec) hipLaunchKernelGGL((strided_step_kernel<4, 1>), dim3(a.B), dim3(128), 0, st, a);
     else hipLaunchKernelGGL((strided_step_kernel<1, 1>), dim3(a.B), dim3(128), 0, st, a);
+  }
+  SMD_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_multistep_step(const MultistepStepArgs& a, hipStream_t st) {
+  SMD_ARG_CHECK(a.x && a.eps_hat && a.coef && a.plan && a.t_ptr, "multistep_step: null pointer");
+  SMD_ARG_CHECK(a.x0_prev, "multistep_step: null history (x0_prev: one float32 array of the state's shape per chain)");
+  SMD_ARG_CHECK(a.B > 0 && a.S > 0 && a.C > 0 && (!a.x_bf16 || a.Cp >= a.C), "multistep_step: bad shape");
+  SMD_ARG_CHECK((a.infill_masks != nullptr) == (a.infill_samples != nullptr), "multistep_step: infill needs samples and masks");
+  SMD_ARG_CHECK(a.T > 0, "multistep_step: T=%d (number of timesteps: bounds the coefficient table and the plan)", a.T);
+  SMD_ARG_CHECK(!a.t_advance || a.arrive, "multistep_step: t_advance needs the arrival counter");
+  SMD_ARG_CHECK(((uintptr_t)a.plan & 15) == 0, "multistep_step: the plan rows are read as 16-byte vectors");
+  SMD_ARG_CHECK(!a.tf_infill_keys || (a.tf_n_total >= (int64_t)(a.sample_offset + a.B) * a.S * a.C && a.tf_n_total <= (1ll << 32)),
+                "multistep_step: tf_n_total=%lld must cover this rank's window and be <= 2^32", (long long)a.tf_n_total);
+  const bool vec = a.C % 4 == 0 && (!a.x_bf16 || a.Cp % 4 == 0);
+  if (vec) {
+    const uintptr_t f32 = (uintptr_t)a.x | (uintptr_t)a.eps_hat | (uintptr_t)a.x0_prev | (uintptr_t)a.infill_samples |
+                          (uintptr_t)a.infill_masks | (uintptr_t)a.infill_z_in | (uintptr_t)a.collection;
+    SMD_ARG_CHECK((f32 & 15) == 0 && ((uintptr_t)a.x_bf16 & 7) == 0,
+                  "multistep_step: C=%d takes 16-byte loads: state, history, eps_hat, infill arrays and collection must be 16-byte aligned", a.C);
+  }
+  if (a.S >= 4) {
+    if (vec) hipLaunchKernelGGL((multistep_step_kernel<4, 4>), dim3(a.B), dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((multistep_step_kernel<1, 4>), dim3(a.B), dim3(512), 0, st, a);
+  } else {
+    if (vec) hipLaunchKernelGGL((multistep_step_kernel<4, 1>), dim3(a.B), dim3(128), 0, st, a);
+    else hipLaunchKernelGGL((multistep_step_kernel<1, 1>), dim3(a.B), dim3(128), 0, st, a);
   }
   SMD_LAUNCH_CHECK();
   return 0;

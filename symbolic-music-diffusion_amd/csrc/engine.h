@@ -87,6 +87,12 @@ struct BoundStepIO {                   // include/smd_hip.h smd_bound_io
   float* partial = nullptr;           // [T][B][3]
 };
 
+struct MultistepPlan {
+  const float* coef = nullptr;        // [T][12], see MultistepStepArgs
+  const int32_t* plan = nullptr;      // [T][4]
+  int T = 0;
+};
+
 class SmdEngine {
  public:
   explicit SmdEngine(const SmdModelDesc& d);
@@ -151,6 +157,8 @@ class SmdEngine {
   int sample_step(const SampleStepIO& io, hipStream_t st, int part = 0);   // eps-net forward + fused reverse step
   // eps-net forward + fused strided (DDIM) step: the walk and its coefficients come from the plan (io.slot_table / tf_t0 unused)
   int strided_step(const SampleStepIO& io, const StridePlan& plan, hipStream_t st, int part = 0);
+  // eps-net forward + fused multistep (DPM-Solver++(2M)) step; x0_prev: the chain's history array (io.z_in and the noise keys unused)
+  int multistep_step(const SampleStepIO& io, const MultistepPlan& plan, float* x0_prev, hipStream_t st, int part = 0);
   // one iteration of the variational-bound walk: noise an example to level t, eps-net forward at table row t, the three sums
   int bound_step(const BoundStepIO& io, hipStream_t st);
   int init_state(float* x, uint32_t seed_lo, uint32_t seed_hi, uint32_t sample_offset, hipStream_t st);

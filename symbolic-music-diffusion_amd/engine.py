@@ -469,6 +469,21 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.L.smd_engine_strided_step(self.h, C.byref(io), C.byref(plan), int(part), _stream()), "strided_step")
 
+    def multistep_step(self, io: "_lib.SampleIO", plan: "_lib.MultistepPlan", x0_prev: torch.Tensor, part: int = 0) -> None:
+        """One iteration of a multistep (DPM-Solver++(2M)) walk: the strided step with the chain's history array ``x0_prev``
+        (fp32, the state's shape; include/smd_hip.h smd_engine_multistep_step); ``part`` as in sample_step."""
+        want = (self.batch, *self.cfg.sample_shape)
+        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        if (x0_prev.dtype != torch.float32 or not x0_prev.is_contiguous() or not x0_prev.is_cuda or x0_prev.device.index != index
+                or tuple(x0_prev.shape) != want):
+            raise ValueError(f"multistep_step: x0_prev must be a contiguous float32 tensor of shape {want} on {self.device}, got "
+                             f"{x0_prev.dtype} {tuple(x0_prev.shape)} on {x0_prev.device}")
+        self._sync_fp8_weights()
+        self._join_pending()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.smd_engine_multistep_step(self.h, C.byref(io), C.byref(plan), x0_prev.data_ptr(), int(part), _stream()),
+                       "multistep_step")
+
     def bound_step(self, io: "_lib.BoundIO") -> None:
         """One iteration of the variational-bound walk: noise the examples to the level of the device timestep, eps-net
         forward at that table row, the three per-example sums (include/smd_hip.h smd_engine_bound_step)."""

@@ -268,6 +268,10 @@ ENGINE_FLAGS: List[FlagDef] = [
     _D("bound_steps", "int", 0, "--compute_bound: 0 = every timestep (the bound itself, in bits/dim), else the per-timestep terms at "
        "2..num_sigmas evenly spaced timesteps only (the curve; no total)."),
     _D("bound_only", "bool", False, "--compute_bound: stop after writing the bound (no sampling run)."),
+    _D("ddim_order", "int", 1, "--ddim_steps: order of the solver, 1 = the strided (DDIM) update, 2 = the second-order multistep "
+       "update DPM-Solver++(2M) of Lu et al. 2022 (deterministic: --ddim_eta=0; DESIGN.md section 18)."),
+    _D("ddim_spacing", "enum", "uniform", "--ddim_steps: the timesteps are evenly spaced in t (uniform) or in "
+       "lambda = log(sqrt(ap) / sqrt(1 - ap)) snapped to timesteps (logsnr: at most --ddim_steps of them).", ("uniform", "logsnr")),
     _D("ckpt_format", "enum", "safetensors", "Checkpoint file format written by train_ncsn: safetensors, or the "
        "reference's flax-0.3.0 msgpack state dict (both are recognised when restoring).", ("safetensors", "flax")),
     _D("rng_impl", "enum", "philox", "Random streams: the engine's fused Philox draws, or jax.random-compatible "

@@ -67,6 +67,10 @@ class BoundIO(C.Structure):
                 ("sample_offset", c_u32), ("key_ptr", c_void), ("tf_keys", c_void), ("tf_n_total", c_i64), ("partial", c_void)]
 
 
+class MultistepPlan(C.Structure):
+    _fields_ = [("coef", c_void), ("plan", c_void), ("T", c_i32)]
+
+
 class LangevinIO(C.Structure):
     _fields_ = [("x", c_void), ("grad", c_void), ("alpha", C.c_float), ("noise_coef", C.c_float), ("z_in", c_void),
                 ("seed_lo", c_u32), ("seed_hi", c_u32), ("step", c_u32), ("sample_offset", c_u32), ("use_threefry", c_i32),
@@ -126,6 +130,7 @@ _SIGS = {
     "smd_engine_sample_step": (C.c_int, [c_void, C.POINTER(SampleIO), c_void]),
     "smd_engine_sample_step_part": (C.c_int, [c_void, C.POINTER(SampleIO), C.c_int, c_void]),
     "smd_engine_strided_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(StridePlan), C.c_int, c_void]),
+    "smd_engine_multistep_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(MultistepPlan), c_void, C.c_int, c_void]),
     "smd_engine_bound_step": (C.c_int, [c_void, C.POINTER(BoundIO), c_void]),
     "smd_bound_noise": (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, C.c_int, c_u32, c_u32,
                                   c_void, c_u32, c_void, c_void, c_void]),

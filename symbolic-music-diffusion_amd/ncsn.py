@@ -5,7 +5,8 @@ Same names, argument meaning and error behaviour as the reference seam (SURVEY s
   create_model          train_ncsn.py:193-203        Model.__call__   models/ncsn.py:141-148
   diffusion_loss        utils/losses.py:250-308      reduce_fn        utils/losses.py:22-30
   diffusion_dynamics    utils/ebm_utils.py:280-405   collate_sampling_metrics  :408-428
-  strided_dynamics / ddim_encode: the strided (DDIM) sampler and its inversion, no reference counterpart
+  strided_dynamics / ddim_encode: the strided (DDIM) sampler and its inversion, no reference counterpart (DESIGN.md section 16);
+                        order=2 / spacing="logsnr": DPM-Solver++(2M) on a lambda-uniform grid
   variational_bound: the per-timestep variational bound on held-out examples, no reference counterpart
   sample                train_ncsn.py:499-551
 
@@ -883,11 +884,13 @@ def diffusion_dynamics(rng: PRNGKey, model: Model, betas, init, epsilon=None, T=
 def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], coef: np.ndarray, plan: np.ndarray, walk_key: tuple, *,
                   collect: bool, infill: bool = False, infill_samples=None, infill_masks=None, noises: Optional[Callable] = None,
                   infill_noises: Optional[Callable] = None, use_graph: bool = True, one_chain: bool = False, sample_offset: int = 0,
-                  global_num_samples: Optional[int] = None):
+                  global_num_samples: Optional[int] = None, multistep: bool = False):
     """A table-driven walk over the timesteps ``order`` (smd_engine_strided_step) in the arrangement of diffusion_dynamics:
     eager launches with explicit draws, else one graph-replayed chain, else (B >= 128, bf16 / fp8) the pipelined pair.  Its
     cached graphs and persistent buffers live in their own ``slot`` of the model's sampler cache, beside diffusion_dynamics'
-    entry, keyed additionally by ``walk_key``.  Returns (state, collection or None, metrics_partial (T, B, 3) indexed by t)."""
+    entry, keyed additionally by ``walk_key``.  ``multistep``: ``coef`` is a multistep table ([T][12]), every chain carries one
+    history tensor of its state's shape and steps with smd_engine_multistep_step; the first iteration does not read the
+    history, so a reused buffer needs no reset.  Returns (state, collection or None, metrics_partial (T, B, 3) indexed by t)."""
     eng = model.engine
     dev = eng.device
     init = torch.as_tensor(init).to(dev, torch.float32).contiguous()
@@ -950,7 +953,7 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
             entry["inf_m"].copy_(inf_m)
     else:
         coef_d, plan_d = torch.from_numpy(coef).to(dev), torch.from_numpy(plan).to(dev)
-        sp = _lib.StridePlan()
+        sp = _lib.MultistepPlan() if multistep else _lib.StridePlan()
         sp.coef, sp.plan, sp.T = coef_d.data_ptr(), plan_d.data_ptr(), nT
         if graphed:
             cache.pop(slot, None)
@@ -972,6 +975,7 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
             ch["t_ptr"].fill_(order[0])
         else:
             ch = dict(eng=e, x=x[lo:hi], metrics=torch.zeros((nT, h, 3), dtype=torch.float32, device=dev),
+                      hist=torch.zeros((h, *init.shape[1:]), dtype=torch.float32, device=dev) if multistep else None,
                       coll=torch.zeros((COLLECTION_STEPS + 1, h, *init.shape[1:]), dtype=torch.float32, device=dev) if collect else None,
                       t_ptr=torch.tensor([order[0]], dtype=torch.int32, device=dev),
                       key=torch.zeros(2, dtype=torch.int32, device=dev))
@@ -995,7 +999,10 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
             ch["coll"][0] = start[lo:hi]
         e.load_state(ch["x"])
 
-    step = lambda ch, part=0: ch["eng"].strided_step(ch["io"], sp, part)
+    if multistep:
+        step = lambda ch, part=0: ch["eng"].multistep_step(ch["io"], sp, ch["hist"], part)
+    else:
+        step = lambda ch, part=0: ch["eng"].strided_step(ch["io"], sp, part)
     if explicit:
         ch = chains[0]
         zbuf = torch.zeros_like(x)
@@ -1027,9 +1034,23 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
     return x, collection, metrics_partial
 
 
+def _walk_ld_metrics(model: Model, betas, taus, mp):
+    """ld_metrics (4, iterations, 1) of a table-driven walk from its metric partials (T, B, 3): row j = iteration j"""
+    eng = model.engine
+    B = mp.shape[1]
+    denom = float(B) if eng.S == 1 else float(B * eng.C)
+    idx = torch.tensor([int(t) for t in taus], device=eng.device, dtype=torch.long)
+    per_t = mp.sum(dim=1)[idx] / denom                                              # (K, 3), row j = iteration j
+    ld = torch.zeros((4, len(idx), 1), dtype=torch.float32, device=eng.device)
+    ld[0, :, 0], ld[1, :, 0], ld[3, :, 0] = per_t[:, 0], per_t[:, 1], per_t[:, 2]
+    ld[2, :, 0] = torch.from_numpy(_sched.alphas_cumprod(betas)[taus]).to(eng.device)
+    return ld
+
+
 def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, infill=False, infill_samples=None,
                      infill_masks=None, *, noises: Optional[Callable] = None, infill_noises: Optional[Callable] = None,
-                     use_graph: bool = True, sample_offset: int = 0, global_num_samples: Optional[int] = None):
+                     use_graph: bool = True, sample_offset: int = 0, global_num_samples: Optional[int] = None, order: int = 1,
+                     spacing: str = "uniform"):
     """The generalised non-Markovian sampler of Song et al. 2021 (DDIM) on ``steps`` evenly spaced timesteps of the schedule
     (schedule.stride_timesteps) instead of all of them: ``steps`` network evaluations from the same checkpoint.  ``eta`` scales
     the noise of every iteration (0: deterministic, 1: the DDPM posterior's variance).  Returns (state, collection (41, ...),
@@ -1037,24 +1058,35 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
     of that iteration's timestep; the collection follows the reference's bookkeeping for a walk of ``steps`` iterations.
     ``noises(t)`` / ``infill_noises(t)`` supply the draws of the iteration at timestep t explicitly.  With infill the known
     region is re-noised to the level of the state being PRODUCED (the next timestep of the walk), not to the level of t as
-    utils/ebm_utils.py:346 does: one timestep apart there, a whole stride here."""
+    utils/ebm_utils.py:346 does: one timestep apart there, a whole stride here.
+    ``order`` = 2: the second-order multistep update DPM-Solver++(2M) of Lu et al. 2022 on the same clamped x0 (eta must be 0);
+    ``spacing`` = "logsnr": timesteps uniform in lambda = log(sqrt(ap) / sqrt(1 - ap)) (schedule.logsnr_timesteps), possibly
+    fewer than ``steps`` of them.  Order 2 walks with smd_engine_multistep_step and keeps its graphs in the cache slot
+    "multistep", keyed by (iterations, order, spacing) AND the timesteps themselves: on the lambda grid two values of ``steps``
+    can snap to the same number of iterations on different timesteps.  Order 1 on the lambda grid keys its "strided" entry the
+    same way; the defaults are the strided walk, and its key, as they were."""
     nT = len(betas)
-    taus = _sched.stride_timesteps(nT, steps)
-    coef, plan = _sched.strided_coefficient_table(betas, taus, eta)
-    order = [int(t) for t in taus]
-    x, collection, mp = _strided_walk("strided", rng, model, betas, init, order, coef, plan, ("strided", len(order), float(eta)),
-                                      collect=True, infill=infill, infill_samples=infill_samples, infill_masks=infill_masks,
-                                      noises=noises, infill_noises=infill_noises, use_graph=use_graph, sample_offset=sample_offset,
-                                      global_num_samples=global_num_samples)
-    eng = model.engine
-    B = x.shape[0]
-    denom = float(B) if eng.S == 1 else float(B * eng.C)
-    idx = torch.tensor(order, device=eng.device, dtype=torch.long)
-    per_t = mp.sum(dim=1)[idx] / denom                                              # (K, 3), row j = iteration j
-    ld = torch.zeros((4, len(order), 1), dtype=torch.float32, device=eng.device)
-    ld[0, :, 0], ld[1, :, 0], ld[3, :, 0] = per_t[:, 0], per_t[:, 1], per_t[:, 2]
-    ld[2, :, 0] = torch.from_numpy(_sched.alphas_cumprod(betas)[taus]).to(eng.device)
-    return x, collection, ld
+    if order not in (1, 2):
+        raise ValueError(f"order={order}: 1 (DDIM) or 2 (DPM-Solver++(2M))")
+    if spacing not in ("uniform", "logsnr"):
+        raise ValueError(f"spacing={spacing!r}: 'uniform' (in t) or 'logsnr' (in lambda)")
+    if order == 2 and float(eta) != 0.0:
+        raise ValueError(f"order=2 is a deterministic solver: eta must be 0, got {eta}")
+    taus = _sched.stride_timesteps(nT, steps) if spacing == "uniform" else _sched.logsnr_timesteps(nT, steps, betas)
+    walk = [int(t) for t in taus]
+    kw = dict(collect=True, infill=infill, infill_samples=infill_samples, infill_masks=infill_masks, noises=noises,
+              infill_noises=infill_noises, use_graph=use_graph, sample_offset=sample_offset, global_num_samples=global_num_samples)
+    if order == 1:                                       # the strided update on either grid; the default key is the one it had
+        coef, plan = _sched.strided_coefficient_table(betas, taus, eta)
+        # on the lambda grid the number of iterations does not name the timesteps (K = 19 and K = 20 both snap to 18): the key
+        # carries the walk itself, because a reused entry keeps its device tables
+        key = ("strided", len(walk), float(eta)) + ((spacing, tuple(walk)) if spacing != "uniform" else ())
+        x, collection, mp = _strided_walk("strided", rng, model, betas, init, walk, coef, plan, key, **kw)
+    else:
+        coef, plan = _sched.multistep_coefficient_table(betas, taus, order)
+        x, collection, mp = _strided_walk("multistep", rng, model, betas, init, walk, coef, plan,
+                                          ("multistep", len(walk), int(order), spacing, tuple(walk)), multistep=True, **kw)
+    return x, collection, _walk_ld_metrics(model, betas, taus, mp)
 
 
 def ddim_encode(model: Model, betas, x0, steps, *, use_graph: bool = True):
@@ -1160,12 +1192,13 @@ def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip
 
 def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400, sampling="ald", epsilon=1e-3,
            steps=100, denoise=True, *, sample_offset: int = 0, use_graph: bool = True,
-           global_num_samples: Optional[int] = None, ddim_steps: int = 0, ddim_eta: float = 0.0):
+           global_num_samples: Optional[int] = None, ddim_steps: int = 0, ddim_eta: float = 0.0, ddim_order: int = 1,
+           ddim_spacing: str = "uniform"):
     """train_ncsn.py:499-551.  'ddpm': N(0,1) init + diffusion_dynamics.  'ald' / 'cas': uniform(-sqrt(12)/2, sqrt(12)/2)
     init (:542-547) + annealed / consistent Langevin dynamics with the score network ``scorenet``.  The reference unpacks
     three values from every sampler although consistent_langevin_dynamics returns two (a ValueError upstream); here 'cas'
     returns a two-entry collection [init, final state].  ``ddim_steps`` > 0 ('ddpm' only): the same initialisation, then the
-    strided walk ``strided_dynamics(..., ddim_steps, ddim_eta)`` instead of every timestep."""
+    strided walk ``strided_dynamics(..., ddim_steps, ddim_eta, order=ddim_order, spacing=ddim_spacing)`` instead of every timestep."""
     if sampling not in ("ddpm", "ald", "cas"):
         raise ValueError(f"Unknown sampling algorithm: {sampling}")
     if ddim_steps and sampling != "ddpm":
@@ -1206,7 +1239,8 @@ def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400
     if ddim_steps:
         generated, collection, ld_metrics = strided_dynamics(ld_rng, scorenet, sigmas, init, ddim_steps, ddim_eta,
                                                              sample_offset=sample_offset, use_graph=use_graph,
-                                                             global_num_samples=global_num_samples)
+                                                             global_num_samples=global_num_samples, order=ddim_order,
+                                                             spacing=ddim_spacing)
         return generated, collection, collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = diffusion_dynamics(ld_rng, scorenet, sigmas, init, epsilon, steps, denoise,
                                                            False, sample_offset=sample_offset, use_graph=use_graph,

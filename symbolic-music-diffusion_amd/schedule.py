@@ -136,6 +136,68 @@ def inversion_coefficient_table(betas: np.ndarray, taus):
     return _walk_tables(betas, asc[:-1], co, asc[1:-1] + [len(betas)], [-1] * n, np.inf)
 
 
+# ------------------------------------------------------------------ second-order multistep walks
+def half_logsnr(betas: np.ndarray) -> np.ndarray:
+    """lambda_t = log(sqrt(ap_t) / sqrt(1 - ap_t)), float64 from the float32 ``alphas_cumprod``: the time variable of
+    DPM-Solver (Lu et al. 2022), strictly decreasing in t."""
+    ap = alphas_cumprod(betas).astype(np.float64)
+    return 0.5 * (np.log(ap) - np.log1p(-ap))
+
+
+def logsnr_timesteps(T: int, K: int, betas: np.ndarray) -> np.ndarray:
+    """Timesteps of a walk that is uniform in lambda instead of in t, descending: K values of lambda evenly spaced from
+    lambda[T-1] to lambda[0], each snapped to the timestep of nearest lambda, duplicates dropped.  Always with T - 1 and 0; near
+    t = 0 the snapping merges points, so len(result) <= K (as ``stride_timesteps`` may)."""
+    T, K = int(T), int(K)
+    if len(betas) != T:
+        raise ValueError(f"logsnr_timesteps: {len(betas)} betas for T={T}")
+    if not 2 <= K <= T:
+        raise ValueError(f"a strided walk takes 2 <= steps <= {T} timesteps, got {K}")
+    lam = half_logsnr(betas)
+    want = np.linspace(lam[T - 1], lam[0], K)
+    taus = np.argmin(np.abs(lam[None, :] - want[:, None]), axis=1)       # linspace's end points are lam[T-1] and lam[0] exactly
+    return np.unique(taus)[::-1].astype(int).copy()
+
+
+def multistep_coefficients(betas: np.ndarray, taus, order: int) -> dict:
+    """float64 (a0, a1, b, w, h, sqrt_as, sqrt_1m_as), one entry per iteration of the descending walk ``taus``, of the
+    data-prediction multistep update of DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2) in the notation of
+    ``strided_coefficients`` at eta = 0:  x_s = b x_t + a0 x0 + a1 x0_prev,  a0 = a (1 + w),  a1 = -a w,
+    w_j = h_j / (2 h_{j-1}),  h_j = lambda_s - lambda_t.  w = 0 on the first iteration (no history) and on the last (ap_s := 1,
+    h = inf: a first-order step that returns x0); ``order`` 1 is w = 0 everywhere, the strided update itself."""
+    if order not in (1, 2):
+        raise ValueError(f"multistep_coefficients: order={order} (1: DDIM, 2: DPM-Solver++(2M))")
+    taus = np.asarray(taus, dtype=np.int64)
+    co = strided_coefficients(betas, taus, 0.0)
+    lam = half_logsnr(betas)
+    n = len(taus)
+    h = np.full(n, np.inf)
+    h[:-1] = lam[taus[1:]] - lam[taus[:-1]]
+    w = np.zeros(n)
+    if order == 2 and n > 2:
+        w[1:-1] = h[1:-1] / (2 * h[:-2])
+    a1 = np.where(w == 0, 0.0, -co["a"] * w)               # an exact +0 where there is no history term: the kernel tests it
+    return dict(a0=co["a"] * (1 + w), a1=a1, b=co["b"], w=w, h=h, sqrt_as=co["sqrt_as"], sqrt_1m_as=co["sqrt_1m_as"])
+
+
+MULTISTEP_COLUMNS = 12    # floats per row of the multistep coefficient table: rows stay 16-byte aligned
+
+
+def multistep_coefficient_table(betas: np.ndarray, taus, order: int, clip: float = 1.0):
+    """Tables of the multistep sampler for the descending timesteps ``taus``: float32 [T][12] -- the eight columns of
+    ``strided_coefficient_table`` at eta = 0 with a0 in place of a (sqrt_recip, sqrt_m1, a0, b, 0, clip, sqrt_as, sqrt_1m_as),
+    then a1 and three zeros -- and that function's int32 [T][4] plan unchanged.  At order 1 the first eight columns ARE the
+    strided table, bit for bit."""
+    taus = [int(t) for t in taus]
+    co = multistep_coefficients(betas, taus, order)
+    base, plan = strided_coefficient_table(betas, taus, 0.0, clip)
+    coef = np.zeros((len(betas), MULTISTEP_COLUMNS), dtype=np.float32)
+    coef[:, :8] = base
+    coef[taus, 2] = co["a0"]
+    coef[taus, 8] = co["a1"]
+    return coef, plan
+
+
 # ------------------------------------------------------------------ variational bound (DESIGN.md section 17)
 def bound_tables(betas: np.ndarray, timesteps, clip: float = 1.0) -> dict:
     """Everything the per-timestep variational bound (Ho et al. 2020, eq. 5) needs from the schedule, for the timesteps
