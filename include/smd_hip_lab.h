@@ -123,6 +123,17 @@ typedef struct smd_gemm_epilogue {
 int smd_gemm_nt_lab(const smd_bf16* A, int lda, const smd_bf16* Bt, int ldb, int M, int N, int K, const smd_gemm_epilogue* ep,
                     int min_tiles, int32_t* plan_out, void* stream);
 
+/* lab entry: launch_layernorm_fwd with the sampler's table-driven FiLM row (tests/test_gpu_ln_regimes.py).  It is
+ * smd_layernorm_fwd_stats (smd_hip.h) plus the two LnArgs fields that only the engine's sampler steps set: with t_ptr != NULL every
+ * row of the launch reads FiLM row clamp(*t_ptr, 0, film_rows - 1) of the [film_rows][ld_film] tables film_scale / film_shift (*t_ptr
+ * is read on the device when the kernel runs), rows_per_sample is ignored by the forward and rows need not be a multiple of it.
+ * With t_ptr == NULL it is smd_layernorm_fwd_stats.  No arithmetic of its own; the argument checks are the launcher's (t_ptr needs
+ * a FiLM table and film_rows > 0), errors return < 0 with smd_last_error() set and launch nothing. */
+int smd_layernorm_fwd_lab(const float* x, const smd_bf16* x_bf16, int rows, int D, const float* gamma, const float* beta,
+                          const float* film_scale, const float* film_shift, int ld_film, int rows_per_sample, int swish,
+                          smd_bf16* out, uint8_t* out8, uint32_t* out_scale, float* stats_out, const int32_t* t_ptr, int film_rows,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

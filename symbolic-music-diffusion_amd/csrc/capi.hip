@@ -406,6 +406,16 @@ int smd_layernorm_fwd_stats(const float* x, const smd_bf16* x_bf16, int rows, in
   a.out = B(out); a.out_f8 = out8; a.out_scale = out_scale; a.stats_out = stats_out;
   return launch_layernorm_fwd(a, S(stream));
 }
+int smd_layernorm_fwd_lab(const float* x, const smd_bf16* x_bf16, int rows, int D, const float* gamma, const float* beta,
+                          const float* film_scale, const float* film_shift, int ld_film, int rows_per_sample, int swish,
+                          smd_bf16* out, uint8_t* out8, uint32_t* out_scale, float* stats_out, const int32_t* t_ptr, int film_rows,
+                          void* stream) {
+  LnArgs a;
+  a.x = x; a.x_bf16 = B(x_bf16); a.rows = rows; a.D = D; a.gamma = gamma; a.beta = beta; a.film_scale = film_scale;
+  a.film_shift = film_shift; a.ld_film = ld_film; a.rows_per_sample = rows_per_sample; a.swish = swish;
+  a.out = B(out); a.out_f8 = out8; a.out_scale = out_scale; a.stats_out = stats_out; a.t_ptr = t_ptr; a.film_rows = film_rows;
+  return launch_layernorm_fwd(a, S(stream));
+}
 int smd_layernorm_bwd_stats(const float* x, const smd_bf16* x_bf16, int rows, int D, const float* gamma, const float* beta,
                             const float* film_scale, const float* film_shift, int ld_film, int rows_per_sample, int swish,
                             const smd_bf16* dout, const float* dres, const smd_bf16* dres_bf16, float* dx,

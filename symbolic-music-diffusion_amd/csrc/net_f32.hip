@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(LnF32Args a) {
   const float inv_d = 1.0f / (float)a.D;
   const float mean = s * inv_d;
   const float var = s2 * inv_d - mean * mean;
-  const float rstd = 1.0f / sqrtf(var + 1e-6f);
+  const float rstd = 1.0f / sqrtf(fmaxf(var + 1e-6f, 1e-6f));      // the one-pass variance can round below 0 (smd_ln_rstd, smd_common.h)
   const float* fs = nullptr;
   const float* fh = nullptr;
   if (a.film_scale) {

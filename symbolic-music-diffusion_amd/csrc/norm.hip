@@ -912,8 +912,10 @@ static int check_ln(const LnArgs& a, bool need_out) {
                 "layernorm: e4m3 output needs out_scale, D in {1024, 2048} and FiLM+swish or neither");
   SMD_ARG_CHECK(a.rows > 0, "layernorm: rows=%d", a.rows);
   SMD_ARG_CHECK((a.film_scale != nullptr) == (a.film_shift != nullptr), "layernorm: scale/shift must come together");
+  SMD_ARG_CHECK(!a.t_ptr || (a.film_scale && a.film_rows > 0), "layernorm: t_ptr needs a FiLM table with film_rows > 0");
   if (a.film_scale) {
-    SMD_ARG_CHECK(a.rows_per_sample > 0 && a.rows % a.rows_per_sample == 0 && a.ld_film >= a.D,
+    // with t_ptr every row reads the one table row *t_ptr: the forward then ignores rows_per_sample (groups of 32 rows)
+    SMD_ARG_CHECK(a.rows_per_sample > 0 && (a.rows % a.rows_per_sample == 0 || (a.t_ptr && need_out)) && a.ld_film >= a.D,
                   "layernorm: bad FiLM geometry rows=%d rows_per_sample=%d ld_film=%d", a.rows,
                   a.rows_per_sample, a.ld_film);
   }

@@ -47,16 +47,22 @@ __device__ __forceinline__ int smd_clamp_t(int t, int T) { return t < 0 ? 0 : (t
 __device__ __forceinline__ float bf2f(bf16_t v) { return (float)v; }
 __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)v; }
 
-// LayerNorm 1/sqrt(var + eps): v_rsq_f32 (the argument is >= 1e-6, never a denormal: same bits as rsqrtf) behind eight idle
-// issue cycles.  History: round 3 attributed the intermittently wrong row statistics of the 128-wide
-// LayerNorm backward next to a two-buffer weight-gradient workgroup to this instruction and put the idle cycles in front of
-// it, which lowered the rate without closing it.  The stand-alone reproducer of round 4 (tools/rsq_repro.hip) shows the value
+// LayerNorm 1/sqrt(var + eps): v_rsq_f32 behind eight idle issue cycles.  The argument is raised to eps first: every caller forms
+// var = E[x^2] - mean^2 in ONE pass in fp32, which is >= 0 in exact arithmetic only -- on a (nearly) constant row whose value is
+// no power of two the two terms agree to fp32 rounding and their difference comes out as small negative numbers (a constant 3.3
+// over 2048 columns: -2.9e-6, 10.1: -5.3e-5), and v_rsq_f32 of a negative argument is NaN.  The true argument is >= eps, so the
+// clamp only moves the computed one towards it; wherever the computed variance is >= 0 the bits are unchanged (DESIGN.md
+// section 21, "One-pass variance").  The clamped argument is never a denormal: same bits as rsqrtf.
+// History: round 3 attributed the intermittently wrong row statistics of the 128-wide LayerNorm
+// backward next to a two-buffer weight-gradient workgroup to this instruction and put the idle cycles in front of it, which
+// lowered the rate without closing it.  The stand-alone reproducer of round 4 (tools/rsq_repro.hip) shows the value
 // this instruction WRITES is always right; what reads a stale register in lanes 48..63 is the v_pk_mul_f32 that hipcc's SLP
 // vectoriser forms for the first use of the result -- with a plain FMA as the producer alike.  The cure is in the build
 // (no packed-fp32 arithmetic in the small-LDS kernels, build.py) and in the library (only the four-buffer weight-gradient
 // kernel ships); the idle cycles stay as they are part of the code every determinism soak has run on.
 // -DSMD_LN_RSTD_BARE (tools/build_rsq_repro.sh): the bare instruction, for the reproducer's victim build.
 __device__ __forceinline__ float smd_ln_rstd(float v) {
+  v = fmaxf(v, 1e-6f);
 #ifdef SMD_LN_RSTD_BARE
   return __builtin_amdgcn_rsqf(v);
 #else

@@ -174,6 +174,8 @@ _SIGS = {
                                          C.c_int, c_void, c_i64, c_void]),
     "smd_layernorm_fwd_stats": (C.c_int, [c_void, c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void, C.c_int, C.c_int,
                                           C.c_int, c_void, c_void, c_void, c_void, c_void]),
+    "smd_layernorm_fwd_lab": (C.c_int, [c_void, c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void, C.c_int, C.c_int,
+                                        C.c_int, c_void, c_void, c_void, c_void, c_void, C.c_int, c_void]),
     "smd_layernorm_bwd_stats": (C.c_int, [c_void, c_void, C.c_int, C.c_int, c_void, c_void, c_void, c_void, C.c_int, C.c_int,
                                           C.c_int, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void,
                                           C.c_int, c_void, c_i64, c_void, c_void]),

@@ -15,6 +15,7 @@ Entry point -> case (every entry of include/smd_hip.h that enqueues a kernel):
   smd_wgrad_lab_launch (smd_hip_lab.h)           test_wgrad_lab_launch_grouped
   smd_quantize_rows_e4m3, smd_gemm_e4m3_nt       test_quantize_rows_e4m3_ragged, test_gemm_e4m3_nt
   smd_layernorm_fwd_e4m3                         test_layernorm_fwd_e4m3
+  smd_layernorm_fwd_lab (smd_hip_lab.h)          test_layernorm_fwd_lab_table_row
   smd_gemm_f32, smd_layernorm_f32                test_gemm_f32, test_layernorm_f32
   smd_attention_f32, smd_noise_embed_f32         test_attention_f32, test_noise_embed_f32_and_bf16
   smd_noise_embed                                test_noise_embed_f32_and_bf16
@@ -1135,6 +1136,36 @@ def test_layernorm_fwd_e4m3(L, dev, rows):
     assert rel(dequant(got["q"], got["scale"]), y) < 4e-2 and rel(got["bf16"].float(), y) < 4e-3          # test_layernorm_fwd_e4m3
     e_ref = torch.ceil(torch.log2(y.abs().amax(1) / 448.0)).to(torch.int64)
     assert bool(((((got["scale"].to(torch.int64) & 0xFF) - 127) - e_ref).abs() <= 1).all())
+
+
+@pytest.mark.parametrize("D,t", [(1024, 2), (512, 9)])
+def test_layernorm_fwd_lab_table_row(L, dev, D, t):
+    """The sampler's FiLM path (include/smd_hip_lab.h): 33 rows (a second row group with one row; no multiple of rows_per_sample,
+    which this path ignores), the FiLM row read through a device timestep, in range and clamped to the last table row; bf16 output,
+    e4m3 copy with one scale per row (D = 1024, the wide kernel) and the saved statistics; D = 512 is the row kernel."""
+    rows, T = 33, 4
+    g = torch.Generator().manual_seed(17 + D)
+    x = torch.randn(rows, D, generator=g) * 2 + 0.5
+    gamma, beta = 1 + 0.1 * torch.randn(D, generator=g), 0.1 * torch.randn(D, generator=g)
+    table = torch.cat([1 + 0.3 * torch.randn(T, D, generator=g), 0.2 * torch.randn(T, D, generator=g)], 1)
+    row = min(max(t, 0), T - 1)
+    y = O.swish(table[row, :D].double() * ln64(x.double(), gamma, beta) + table[row, D:].double())
+    f8 = D == 1024
+
+    def body(r):
+        xD, gD, bD, tab = r.inp(x), r.inp(gamma), r.inp(beta), r.inp(table)
+        tD = r.inp(torch.tensor([t], dtype=torch.int32))
+        ob, stt = r.out("bf16", (rows, D), torch.bfloat16), r.out("stats", (rows, 2))
+        q = r.out("q", (rows, D), torch.uint8) if f8 else None
+        s = r.out("scale", (rows,), torch.int32) if f8 else None
+        ck(L.smd_layernorm_fwd_lab(P(xD), None, rows, D, P(gD), P(bD), P(tab), P(tab[:, D:]), 2 * D, 32, 1, P(ob), P(q), P(s), P(stt),
+                                   P(tD), T, st()))
+
+    got, _ = both(dev, body)
+    assert rel(got["bf16"].float(), y) < 4e-3                                      # test_layernorm_fwd_bwd
+    assert bool(torch.isfinite(got["stats"]).all())
+    if f8:
+        assert rel(dequant(got["q"], got["scale"]), y) < 4e-2                      # test_layernorm_fwd_e4m3
 
 
 # ================================================================================================ Langevin update
