@@ -471,7 +471,9 @@ int smd_noise_embed(const float* noise_level, int n, int channels, smd_bf16* out
  *   inv_global_count (the columns >= C are not written, as in smd_q_sample: the caller zeroes them once).
  * smd_adam_clip_ema: train_ncsn.py:284-287,340-342,364-365 on flat fp32 buffers of n elements: gradient norm -> clip ->
  *   Adam with the stepped LR evaluated from *step_ptr (incremented by the kernel) -> EMA (ema may be NULL).
- *   norm_partial: >= 1024 floats of scratch; metrics_out [4] = norm before clip, after clip, lr, step. */
+ *   norm_partial: >= 1024 floats of scratch; metrics_out [4] = norm before clip, after clip, lr, step.
+ * Alignment: where S*C % 4 == 0 (smd_q_sample) or C % 4 == 0 and Cp % 4 == 0 (smd_mse_fwd_bwd, smd_ddpm_reverse_step with Cp = C) the
+ *   fp32 arrays must be 16-byte aligned and the bf16 array 8-byte aligned (16-byte loads); anything else is refused before the launch. */
 int smd_q_sample(const float* x0, int B, int S, int C, int Cp, int T, const float* alphas_prod_ext, const int32_t* labels,
                  int label_min, const float* used_alphas, const float* eps_in, uint32_t seed_lo, uint32_t seed_hi,
                  const uint32_t* step_ptr, uint32_t sample_offset, smd_bf16* xt_bf16, float* eps_out,

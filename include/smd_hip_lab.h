@@ -134,6 +134,69 @@ int smd_layernorm_fwd_lab(const float* x, const smd_bf16* x_bf16, int rows, int 
                           smd_bf16* out, uint8_t* out8, uint32_t* out_scale, float* stats_out, const int32_t* t_ptr, int film_rows,
                           void* stream);
 
+/* lab entries: the launchers of csrc/diffusion.hip with EVERY field of their argument structs (tests/test_gpu_diffusion_regimes.py).
+ * The stable entries smd_ddpm_reverse_step / smd_q_sample / smd_mse_fwd_bwd fix some of them (no infill arrays, no bf16 re-cast, no
+ * t_advance hand-off, no score-matching form); the engine sets all of them.  The structs mirror ReverseStepArgs / QSampleArgs
+ * (csrc/smd_kernels.h) field for field; a field left 0 / NULL means what it means there.  No arithmetic of their own.
+ * form_out (may be NULL) receives the instantiation the LAUNCHER chose, handed out by the launcher itself, written only behind a launch:
+ *   smd_reverse_step_lab  form_out[0..1] = (VEC, RG) of reverse_step_kernel<VEC, RG>: VEC 4 iff C % 4 == 0 (and Cp % 4 == 0 with x_bf16),
+ *                         RG 4 iff S >= 4;
+ *   smd_q_sample_lab      form_out[0] = 0 q_sample_quads_kernel<4>, 1 q_sample_quads_kernel<1>, 2 q_sample_kernel<true> (S*C % 4 == 0),
+ *                         3 q_sample_kernel<false> (the scalar tail);
+ *   smd_loss_grad_lab     form_out[0] = VEC of mse_loss_grad_kernel<VEC> (4 iff C % 4 == 0 and Cp % 4 == 0).
+ * The vector forms move 16 bytes per lane: the launchers refuse fp32 arrays that are not 16-byte aligned and a bf16 array that is
+ * not 8-byte aligned.  On top of the launchers' own checks the lab entries refuse what the launchers trust the engine for: a
+ * pointer that is not aligned to its element, infill draws without masks, threefry key tables with tf_t0 outside [0, T), Cp < C.
+ * Errors return < 0 with smd_last_error() set; nothing is launched and form_out is untouched. */
+typedef struct smd_reverse_step_args {
+  float* x;
+  const float* eps_hat;
+  int32_t B, S, C, Cp, T;
+  const float* coef;
+  const int32_t* t_ptr;
+  int32_t* t_advance;
+  uint32_t* arrive;
+  const float* z_in;
+  uint32_t seed_lo, seed_hi;
+  const uint32_t* key_ptr;
+  uint32_t sample_offset;
+  const float* infill_samples;
+  const float* infill_masks;
+  const float* infill_z_in;
+  const uint32_t* tf_noise_keys;
+  const uint32_t* tf_infill_keys;
+  int64_t tf_n_total;
+  int32_t tf_t0;
+  smd_bf16* x_bf16;
+  float* metrics_partial;
+  float* collection;
+  const int32_t* slot_table;
+} smd_reverse_step_args;
+int smd_reverse_step_lab(const smd_reverse_step_args* a, int32_t* form_out, void* stream);
+
+typedef struct smd_q_sample_args {
+  const float* x0;
+  int32_t B, S, C, Cp, T;
+  const float* alphas_prod_ext;
+  const int32_t* labels;
+  int32_t label_min;
+  const float* alpha_in;
+  int32_t dsm;
+  const float* eps_in;
+  uint32_t seed_lo, seed_hi;
+  const uint32_t* step_ptr;
+  uint32_t sample_offset;
+  smd_bf16* xt_bf16;
+  float* eps_out;
+  float* s_out;
+} smd_q_sample_args;
+int smd_q_sample_lab(const smd_q_sample_args* a, int32_t* form_out, void* stream);
+
+/* launch_mse_loss_grad; dsm_sigma [B] (may be NULL) selects the score-matching form: d = sigma pred + eps, loss = 0.5 sum d^2,
+ * dpred = d sigma inv_global_count S C */
+int smd_loss_grad_lab(const float* pred, const float* eps, int B, int S, int C, int Cp, float inv_global_count, float* loss_per_sample,
+                      smd_bf16* dpred_bf16, const float* dsm_sigma, int32_t* form_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -598,6 +598,64 @@ int smd_gemm_nt_lab(const smd_bf16* A, int lda, const smd_bf16* Bt, int ldb, int
   return rc;
 }
 
+// ---- lab entries: the launchers of diffusion.hip with every field of their argument structs (include/smd_hip_lab.h).  What the
+// launchers trust the engine for is checked here; the alignment of the vector forms is the launchers' own check.  The reported
+// form is the launcher's, written only behind a launch.
+static inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+static inline bool al2(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1) == 0; }
+
+int smd_reverse_step_lab(const smd_reverse_step_args* p, int32_t* form_out, void* stream) {
+  SMD_ARG_CHECK(p, "smd_reverse_step_lab: null arguments");
+  SMD_ARG_CHECK(al4(p->x) && al4(p->eps_hat) && al4(p->coef) && al4(p->t_ptr) && al4(p->t_advance) && al4(p->arrive) && al4(p->z_in) &&
+                    al4(p->key_ptr) && al4(p->infill_samples) && al4(p->infill_masks) && al4(p->infill_z_in) && al4(p->tf_noise_keys) &&
+                    al4(p->tf_infill_keys) && al4(p->metrics_partial) && al4(p->collection) && al4(p->slot_table) && al2(p->x_bf16),
+                "smd_reverse_step_lab: a pointer is not aligned to its element");
+  SMD_ARG_CHECK(p->Cp >= p->C, "smd_reverse_step_lab: Cp=%d is below C=%d", p->Cp, p->C);
+  SMD_ARG_CHECK(p->infill_masks || !(p->infill_z_in || p->tf_infill_keys), "smd_reverse_step_lab: infill draws without infill masks");
+  SMD_ARG_CHECK(!(p->tf_noise_keys || p->tf_infill_keys) || (p->tf_t0 >= 0 && p->tf_t0 < p->T),
+                "smd_reverse_step_lab: tf_t0=%d must be in [0, T): the key tables are indexed by tf_t0 - t", p->tf_t0);
+  ReverseStepArgs a;
+  a.x = p->x; a.eps_hat = p->eps_hat; a.B = p->B; a.S = p->S; a.C = p->C; a.Cp = p->Cp; a.T = p->T; a.coef = p->coef;
+  a.t_ptr = p->t_ptr; a.t_advance = p->t_advance; a.arrive = p->arrive; a.z_in = p->z_in; a.key = RngKey{p->seed_lo, p->seed_hi};
+  a.key_ptr = p->key_ptr; a.sample_offset = p->sample_offset; a.infill_samples = p->infill_samples; a.infill_masks = p->infill_masks;
+  a.infill_z_in = p->infill_z_in; a.tf_noise_keys = p->tf_noise_keys; a.tf_infill_keys = p->tf_infill_keys;
+  a.tf_n_total = p->tf_n_total; a.tf_t0 = p->tf_t0; a.x_bf16 = B(p->x_bf16); a.metrics_partial = p->metrics_partial;
+  a.collection = p->collection; a.slot_table = p->slot_table;
+  int form[2] = {0, 0};
+  const int rc = launch_reverse_step(a, S(stream), form);
+  if (rc == 0 && form_out) { form_out[0] = form[0]; form_out[1] = form[1]; }
+  return rc;
+}
+
+int smd_q_sample_lab(const smd_q_sample_args* p, int32_t* form_out, void* stream) {
+  SMD_ARG_CHECK(p, "smd_q_sample_lab: null arguments");
+  SMD_ARG_CHECK(al4(p->x0) && al4(p->alphas_prod_ext) && al4(p->labels) && al4(p->alpha_in) && al4(p->eps_in) && al4(p->step_ptr) &&
+                    al4(p->eps_out) && al4(p->s_out) && al2(p->xt_bf16),
+                "smd_q_sample_lab: a pointer is not aligned to its element");
+  SMD_ARG_CHECK(p->dsm == 0 || p->dsm == 1, "smd_q_sample_lab: dsm=%d must be 0 or 1", p->dsm);
+  SMD_ARG_CHECK((int64_t)p->S * p->C < (1ll << 31), "smd_q_sample_lab: S*C must fit an int");
+  QSampleArgs q;
+  q.x0 = p->x0; q.B = p->B; q.S = p->S; q.C = p->C; q.Cp = p->Cp; q.T = p->T; q.alphas_prod_ext = p->alphas_prod_ext;
+  q.labels = p->labels; q.label_min = p->label_min; q.alpha_in = p->alpha_in; q.dsm = p->dsm; q.eps_in = p->eps_in;
+  q.key = RngKey{p->seed_lo, p->seed_hi}; q.step_ptr = p->step_ptr; q.sample_offset = p->sample_offset;
+  q.xt_bf16 = B(p->xt_bf16); q.eps_out = p->eps_out; q.s_out = p->s_out;
+  int form = -1;
+  const int rc = launch_q_sample(q, S(stream), &form);
+  if (rc == 0 && form_out) *form_out = form;
+  return rc;
+}
+
+int smd_loss_grad_lab(const float* pred, const float* eps, int Bn, int Sn, int C, int Cp, float inv_global_count, float* loss_per_sample,
+                      smd_bf16* dpred_bf16, const float* dsm_sigma, int32_t* form_out, void* stream) {
+  SMD_ARG_CHECK(al4(pred) && al4(eps) && al4(loss_per_sample) && al4(dsm_sigma) && al2(dpred_bf16),
+                "smd_loss_grad_lab: a pointer is not aligned to its element");
+  SMD_ARG_CHECK(Sn > 0 && C > 0 && (int64_t)Sn * C < (1ll << 31), "smd_loss_grad_lab: S*C must fit an int");
+  int vec = 0;
+  const int rc = launch_mse_loss_grad(pred, eps, Bn, Sn, C, Cp, inv_global_count, loss_per_sample, B(dpred_bf16), S(stream), dsm_sigma, &vec);
+  if (rc == 0 && form_out) *form_out = vec;
+  return rc;
+}
+
 // ---- lab probe: a stream restricted by a raw CU mask (hipExtStreamCreateWithCUMask).  What the mask can express on this part is
 // documented in include/smd_hip_lab.h (tools/cumask_probe.hip: bit i belongs to XCC i % 8; an XCC whose share is empty is NOT masked).
 int smd_probe_stream_create_cu_mask(const uint32_t* mask_words, int n_words, void** stream_out) {

@@ -855,41 +855,55 @@ int launch_noise_embed(const float* s, int n, int channels, bf16_t* out, int ld_
   return 0;
 }
 
-int launch_q_sample(const QSampleArgs& a, hipStream_t st) {
+int launch_q_sample(const QSampleArgs& a, hipStream_t st, int* form_out) {
   SMD_ARG_CHECK(a.x0 && a.alphas_prod_ext && a.xt_bf16 && a.eps_out && a.s_out, "q_sample: null pointer");
   SMD_ARG_CHECK(a.B > 0 && a.S > 0 && a.C > 0 && a.Cp >= a.C && a.T > 0, "q_sample: bad shape");
   SMD_ARG_CHECK(a.label_min == 0 || a.label_min == 1, "q_sample: label_min=%d", a.label_min);
   SMD_ARG_CHECK(!a.dsm || a.alpha_in, "q_sample: the score-matching form needs the per-sample used_sigmas");
   const int groups = (a.S * a.C + 3) / 4;
-  if (a.C % 4 == 0 && a.Cp % 4 == 0 && a.S * a.C < (1 << 22)) {
+  const bool quads = a.C % 4 == 0 && a.Cp % 4 == 0 && a.S * a.C < (1 << 22);
+  if (quads || (a.S * a.C) % 4 == 0) {
+    const uintptr_t f32 = (uintptr_t)a.x0 | (uintptr_t)a.eps_in | (uintptr_t)a.eps_out;
+    SMD_ARG_CHECK((f32 & 15) == 0 && (!quads || ((uintptr_t)a.xt_bf16 & 7) == 0),
+                  "q_sample: S*C=%d takes 16-byte loads: x0, eps and eps_out must be 16-byte aligned (xt_bf16 8-byte where C and Cp are multiples of 4)", a.S * a.C);
+  }
+  if (quads) {
     // four groups per thread when that still leaves >= 4 workgroups per CU, else one
-    if ((long)a.B * ((groups + 1023) / 1024) >= 1024) hipLaunchKernelGGL(q_sample_quads_kernel<4>, dim3((groups + 1023) / 1024, a.B), dim3(256), 0, st, a);
+    const bool four = (long)a.B * ((groups + 1023) / 1024) >= 1024;
+    if (four) hipLaunchKernelGGL(q_sample_quads_kernel<4>, dim3((groups + 1023) / 1024, a.B), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(q_sample_quads_kernel<1>, dim3((groups + 255) / 256, a.B), dim3(256), 0, st, a);
     SMD_LAUNCH_CHECK();
+    if (form_out) *form_out = four ? SMD_QS_QUADS4 : SMD_QS_QUADS1;
     return 0;
   }
   const dim3 grid((groups + 255) / 256, a.B);
-  if ((a.S * a.C) % 4 == 0) hipLaunchKernelGGL(q_sample_kernel<true>, grid, dim3(256), 0, st, a);
+  const bool vec4 = (a.S * a.C) % 4 == 0;
+  if (vec4) hipLaunchKernelGGL(q_sample_kernel<true>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(q_sample_kernel<false>, grid, dim3(256), 0, st, a);
   SMD_LAUNCH_CHECK();
+  if (form_out) *form_out = vec4 ? SMD_QS_SCALAR_VEC4 : SMD_QS_SCALAR_TAIL;
   return 0;
 }
 
 int launch_mse_loss_grad(const float* pred, const float* eps, int B, int S, int C, int Cp, float inv_global_count,
-                         float* loss_per_sample, bf16_t* dpred_bf16, hipStream_t st, const float* dsm_sigma) {
+                         float* loss_per_sample, bf16_t* dpred_bf16, hipStream_t st, const float* dsm_sigma, int* vec_out) {
   SMD_ARG_CHECK(pred && eps && loss_per_sample && dpred_bf16 && B > 0 && S > 0 && C > 0 && Cp >= C,
                 "mse_loss_grad: bad arguments");
-  if (C % 4 == 0 && Cp % 4 == 0)
+  const bool vec = C % 4 == 0 && Cp % 4 == 0;
+  SMD_ARG_CHECK(!vec || ((((uintptr_t)pred | (uintptr_t)eps) & 15) == 0 && ((uintptr_t)dpred_bf16 & 7) == 0),
+                "mse_loss_grad: C=%d takes 16-byte loads: pred and eps must be 16-byte aligned (dpred 8-byte)", C);
+  if (vec)
     hipLaunchKernelGGL(mse_loss_grad_kernel<4>, dim3(B), dim3(1024), 0, st, pred, eps, S, C, Cp, inv_global_count,
                        loss_per_sample, dpred_bf16, dsm_sigma);
   else
     hipLaunchKernelGGL(mse_loss_grad_kernel<1>, dim3(B), dim3(1024), 0, st, pred, eps, S, C, Cp, inv_global_count,
                        loss_per_sample, dpred_bf16, dsm_sigma);
   SMD_LAUNCH_CHECK();
+  if (vec_out) *vec_out = vec ? 4 : 1;
   return 0;
 }
 
-int launch_reverse_step(const ReverseStepArgs& a, hipStream_t st) {
+int launch_reverse_step(const ReverseStepArgs& a, hipStream_t st, int* form_out) {
   SMD_ARG_CHECK(a.x && a.eps_hat && a.coef && a.t_ptr, "reverse_step: null pointer");
   SMD_ARG_CHECK(a.B > 0 && a.S > 0 && a.C > 0 && (!a.x_bf16 || a.Cp >= a.C), "reverse_step: bad shape");
   SMD_ARG_CHECK((a.infill_masks != nullptr) == (a.infill_samples != nullptr), "reverse_step: infill needs samples and masks");
@@ -900,6 +914,12 @@ int launch_reverse_step(const ReverseStepArgs& a, hipStream_t st) {
                                                             a.tf_n_total <= (1ll << 32)),
                 "reverse_step: tf_n_total=%lld must cover this rank's window and be <= 2^32", (long long)a.tf_n_total);
   const bool vec = a.C % 4 == 0 && (!a.x_bf16 || a.Cp % 4 == 0);
+  if (vec) {
+    const uintptr_t f32 = (uintptr_t)a.x | (uintptr_t)a.eps_hat | (uintptr_t)a.z_in | (uintptr_t)a.infill_samples |
+                          (uintptr_t)a.infill_masks | (uintptr_t)a.infill_z_in | (uintptr_t)a.collection;
+    SMD_ARG_CHECK((f32 & 15) == 0 && ((uintptr_t)a.x_bf16 & 7) == 0,
+                  "reverse_step: C=%d takes 16-byte loads: state, eps_hat, draws, infill arrays and collection must be 16-byte aligned", a.C);
+  }
   if (a.S >= 4) {
     if (vec) hipLaunchKernelGGL((reverse_step_kernel<4, 4>), dim3(a.B), dim3(512), 0, st, a);
     else hipLaunchKernelGGL((reverse_step_kernel<1, 4>), dim3(a.B), dim3(512), 0, st, a);
@@ -908,6 +928,7 @@ int launch_reverse_step(const ReverseStepArgs& a, hipStream_t st) {
     else hipLaunchKernelGGL((reverse_step_kernel<1, 1>), dim3(a.B), dim3(128), 0, st, a);
   }
   SMD_LAUNCH_CHECK();
+  if (form_out) { form_out[0] = vec ? 4 : 1; form_out[1] = a.S >= 4 ? 4 : 1; }
   return 0;
 }
 

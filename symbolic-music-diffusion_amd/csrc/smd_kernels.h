@@ -261,12 +261,16 @@ struct QSampleArgs {
   float* eps_out = nullptr;               // [B*S][C]
   float* s_out = nullptr;                 // [B] sqrt(alpha) noise level
 };
-int launch_q_sample(const QSampleArgs& a, hipStream_t st);
+// form_out (nullable) receives the kernel this launch ran (lab entry smd_q_sample_lab; untouched when the launch is refused):
+// SMD_QS_QUADS4 / SMD_QS_QUADS1 = q_sample_quads_kernel<4> / <1>, SMD_QS_SCALAR_VEC4 / SMD_QS_SCALAR_TAIL = q_sample_kernel<true> / <false>
+enum { SMD_QS_QUADS4 = 0, SMD_QS_QUADS1 = 1, SMD_QS_SCALAR_VEC4 = 2, SMD_QS_SCALAR_TAIL = 3 };
+int launch_q_sample(const QSampleArgs& a, hipStream_t st, int* form_out = nullptr);
 
 // loss + dpred: loss_b = mean_{s,c} (eps-pred)^2 ; dpred = 2 (pred-eps) / (Bglobal*S*C) -> bf16 [B*S][Cp]
 int launch_mse_loss_grad(const float* pred, const float* eps, int B, int S, int C, int Cp,
                          float inv_global_count, float* loss_per_sample, bf16_t* dpred_bf16,
-                         hipStream_t st, const float* dsm_sigma = nullptr);   // dsm_sigma [B]: the score-matching form
+                         hipStream_t st, const float* dsm_sigma = nullptr,    // dsm_sigma [B]: the score-matching form
+                         int* vec_out = nullptr);                             // nullable: VEC of the kernel this launch ran (4 / 1)
 
 // fused reverse step (reference utils/ebm_utils.py:327-394)
 struct ReverseStepArgs {
@@ -295,7 +299,8 @@ struct ReverseStepArgs {
   float* collection = nullptr;        // [41][B][S][C] or null
   const int* slot_table = nullptr;    // [T] slot for timestep t or -1
 };
-int launch_reverse_step(const ReverseStepArgs& a, hipStream_t st);
+// form_out (nullable) receives (VEC, RG) of the kernel this launch ran (lab entry smd_reverse_step_lab; untouched when refused)
+int launch_reverse_step(const ReverseStepArgs& a, hipStream_t st, int* form_out = nullptr);
 
 // fused strided (DDIM) step: the walk (next timestep, iteration, collection slot) and its coefficients from tables
 struct StridedStepArgs {

@@ -57,6 +57,27 @@ class GemmEpilogue(C.Structure):
                 ("accumulate", c_i32), ("ld_outb", c_i32)]
 
 
+class ReverseStepLabArgs(C.Structure):
+    """smd_reverse_step_args of include/smd_hip_lab.h"""
+    _fields_ = [("x", c_void), ("eps_hat", c_void), ("B", c_i32), ("S", c_i32), ("C", c_i32), ("Cp", c_i32), ("T", c_i32),
+                ("coef", c_void), ("t_ptr", c_void), ("t_advance", c_void), ("arrive", c_void), ("z_in", c_void),
+                ("seed_lo", c_u32), ("seed_hi", c_u32), ("key_ptr", c_void), ("sample_offset", c_u32),
+                ("infill_samples", c_void), ("infill_masks", c_void), ("infill_z_in", c_void), ("tf_noise_keys", c_void),
+                ("tf_infill_keys", c_void), ("tf_n_total", c_i64), ("tf_t0", c_i32), ("x_bf16", c_void),
+                ("metrics_partial", c_void), ("collection", c_void), ("slot_table", c_void)]
+
+
+class QSampleLabArgs(C.Structure):
+    """smd_q_sample_args of include/smd_hip_lab.h"""
+    _fields_ = [("x0", c_void), ("B", c_i32), ("S", c_i32), ("C", c_i32), ("Cp", c_i32), ("T", c_i32),
+                ("alphas_prod_ext", c_void), ("labels", c_void), ("label_min", c_i32), ("alpha_in", c_void), ("dsm", c_i32),
+                ("eps_in", c_void), ("seed_lo", c_u32), ("seed_hi", c_u32), ("step_ptr", c_void), ("sample_offset", c_u32),
+                ("xt_bf16", c_void), ("eps_out", c_void), ("s_out", c_void)]
+
+
+Q_SAMPLE_FORMS = ("quads QPT 4", "quads QPT 1", "scalar VEC4", "scalar tail")      # form_out of smd_q_sample_lab
+
+
 class StridePlan(C.Structure):
     _fields_ = [("coef", c_void), ("plan", c_void), ("T", c_i32)]
 
@@ -201,6 +222,10 @@ _SIGS = {
                                        C.POINTER(c_i32), c_void]),
     "smd_gemm_nt_lab": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GemmEpilogue), C.c_int,
                                   C.POINTER(c_i32), c_void]),
+    "smd_reverse_step_lab": (C.c_int, [C.POINTER(ReverseStepLabArgs), C.POINTER(c_i32), c_void]),
+    "smd_q_sample_lab": (C.c_int, [C.POINTER(QSampleLabArgs), C.POINTER(c_i32), c_void]),
+    "smd_loss_grad_lab": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void,
+                                    C.POINTER(c_i32), c_void]),
     "smd_probe_stream_create_cu_mask": (C.c_int, [C.POINTER(c_u32), C.c_int, C.POINTER(c_void)]),
     "smd_probe_stream_destroy": (C.c_int, [c_void]),
     "smd_pair_kernel_sums_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int]),
