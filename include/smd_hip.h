@@ -585,6 +585,21 @@ int64_t smd_ball_cover_workspace_bytes(int nq, int nx);
 int smd_ball_cover(const float* q, int64_t ldq, int nq, const float* x, int64_t ldx, int nx, int d, const float* r2,
                    const uint8_t* keep, int exclude_diagonal, void* workspace, int64_t workspace_bytes, uint8_t* covered,
                    float* realism2, void* stream);
+/* smd_nn_search: for every row q_j of Q (nq x d, row stride ldq) the k candidates of X (nx x d, row
+ *   stride ldx) with the smallest (d2, global index) in lexicographic order, the global index of candidate i being x_base + i:
+ *   d2_out[j][0..k) ascending (fp32) and idx_out[j][0..k) (int64), both [nq][k] contiguous.  d2 = (-2 <q,x> + |q|^2) + |x|^2
+ *   clamped at 0, the query owning the expression (smd_knn_radii's bits when Q is X).  Equal d2 bits are ordered by the lower
+ *   global index, in every comparison the kernels make.  exclude_self != 0: the pair with q_base + j == x_base + i takes part
+ *   in nothing (by index: a duplicate of the query still counts, with its own d2).  accumulate == 0: the lists start as
+ *   (+inf, -1), which stays as the tail where fewer than k candidates exist (no error).  accumulate != 0: d2_out / idx_out hold
+ *   the valid result of earlier calls (possibly padded with (+inf, -1)) and the new candidates are merged into it under the same
+ *   order -- one call on all of X and calls on any partition of X into slabs, in any order, give the same bits in both outputs.
+ *   1 <= k <= SMD_KNN_MAX_K, any nq, nx, d >= 1, q_base, x_base >= 0.  No atomics: two calls give the same bits.  workspace: >=
+ *   smd_nn_search_workspace_bytes(nq, nx, k) bytes, 8-byte aligned; q, x, d2_out 4-byte and idx_out 8-byte aligned. */
+int64_t smd_nn_search_workspace_bytes(int nq, int nx, int k);
+int smd_nn_search(const float* q, int64_t ldq, int nq, int64_t q_base, const float* x, int64_t ldx, int nx, int64_t x_base, int d, int k,
+                  int exclude_self, int accumulate, void* workspace, int64_t workspace_bytes, float* d2_out, int64_t* idx_out,
+                  void* stream);
 
 /* ---- k-means over latent frames (the primitive of the PRD precision / recall histogram, Sajjadi et al. 2018, and of the NDB
  * score, Richardson & Weiss 2018; the reference's sample_ncsn.py:141-146,160 logs them, DESIGN.md section 15 defines them) ----

@@ -281,6 +281,59 @@ def check_bound_flags(FLAGS):
         raise SystemExit(f"--bound_steps={steps}: 0 (every timestep) or from 2 to --num_sigmas={FLAGS.num_sigmas} timesteps")
 
 
+def check_copy_flags(FLAGS):
+    """the refusals of --copy_metrics / --copy_k / --copy_train_examples, before the GPU is touched"""
+    if not FLAGS.copy_metrics:
+        return
+    if FLAGS.interpolate:
+        raise SystemExit("--copy_metrics does not apply to --interpolate: its output holds 9 interpolation points per sample, not a "
+                         "set of the sample shape to search the training set for")
+    if FLAGS.copy_k is None or not 1 <= FLAGS.copy_k <= 8:
+        raise SystemExit(f"--copy_k={FLAGS.copy_k}: --copy_metrics keeps from 1 to 8 training neighbours per row")
+    if FLAGS.copy_train_examples is None or FLAGS.copy_train_examples < 0:
+        raise SystemExit(f"--copy_train_examples={FLAGS.copy_train_examples}: 0 (every training example) or the number of examples to search")
+
+
+COPY_SYNTHETIC_SEED = 4322         # --synthetic --copy_metrics: the training set's seed; the eval examples ("real") take 4321
+COPY_SLAB_EXAMPLES = 1024         # training examples per slab of the search: 64 MiB of fp32 at the base shape (32, 512)
+
+
+def copy_metrics_report(FLAGS, train, real, generated, dev):
+    """--copy_metrics: the nearest training neighbours of the ``generated`` examples next to those of the eval examples ``real``,
+    at frame and at sequence level (smd_amd.metrics.copy_metrics).  ``train``: the training examples in
+    the normalised space the model sees, on the host; they are searched in slabs of COPY_SLAB_EXAMPLES.  Writes
+    {sampling_dir}/ncsn/copy_report.json (the scalars, k, the set sizes, the definitions' version) and nearest_train.pkl (per
+    generated example the k nearest training sequences and per frame the nearest training frame), logs the scalars under copy/..."""
+    import json
+
+    from smd_amd import data, train_utils
+    from smd_amd import metrics as M
+    t0 = time.time()
+    k = FLAGS.copy_k
+    n = len(generated)
+    frames = int(np.prod(generated.shape[1:-1])) if generated.ndim > 2 else 1
+    as3 = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(len(a), frames, -1)
+    train, real, generated = as3(train), as3(real), as3(generated)
+    slabs = [train[i:i + COPY_SLAB_EXAMPLES] for i in range(0, len(train), COPY_SLAB_EXAMPLES)]
+    rep = M.copy_metrics(slabs, real, generated, k, device=dev)
+    scalars = {name + s: rep[name + s] for s in ("", "_seq") for name in M.COPY_SCALARS}
+    summary = dict(scalars, k=k, version=rep["version"], num_train_examples=int(len(train)), num_generated=int(n),
+                   num_held_out=int(len(real)), frames_per_example=frames,
+                   **{name + s: int(rep[name + s]) for s in ("", "_seq") for name in ("n_train", "n_fake", "n_held_out")})
+    out_dir = os.path.join(FLAGS.sampling_dir, "ncsn")
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "copy_report.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    fi = rep["nn_idx"][:, 0].reshape(n, frames)
+    data.save(dict(k=k, sequence_example=rep["nn_idx_seq"], sequence_distance=np.sqrt(rep["nn_d2_seq"].astype(np.float64)),
+                   frame_example=fi // frames, frame_index=fi % frames,
+                   frame_distance=np.sqrt(rep["nn_d2"][:, 0].astype(np.float64)).reshape(n, frames)),
+              os.path.join(out_dir, "nearest_train.pkl"))
+    train_utils.log_metrics({f"copy/{name}": v for name, v in scalars.items()}, 1, 1)
+    log.info("copy metrics: %d generated and %d eval examples against %d training examples (k = %d) in %.1f s", n, len(real),
+             len(train), k, time.time() - t0)
+
+
 def compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world):
     """The variational bound over this rank's rows [lo, hi) of the eval set; rank 0 gathers and writes
     {sampling_dir}/ncsn/bound.json (scalars, per-timestep means) and bound_terms.pkl (the per-example arrays)."""
@@ -349,6 +402,7 @@ def main(argv):
         check_cluster_flags(FLAGS)
     check_ddim_flags(FLAGS)
     check_bound_flags(FLAGS)
+    check_copy_flags(FLAGS)
     torch.cuda.set_device(local_rank)
     dev = f"cuda:{local_rank}"
     if world > 1:
@@ -369,10 +423,15 @@ def main(argv):
         n = FLAGS.sample_size
         real = data.SyntheticLatents(shape, max(n, 1), max(n, 1), 4321).take_examples(n)
         tmin, tmax, emin, emax = -1.0, 1.0, -1.0, 1.0
+        if FLAGS.copy_metrics and rank == 0:                                # no dataset here: a training set of the same law
+            n_train = max(FLAGS.copy_train_examples or n, 2)
+            copy_train = data.SyntheticLatents(shape, n_train, n_train, COPY_SYNTHETIC_SEED).take_examples(n_train)
     else:
         train_ds, eval_ds, _, _ = build_datasets(FLAGS, shape, None, 0, 1)
         real = eval_ds.take_examples(FLAGS.sample_size)
         tmin, tmax, emin, emax = train_ds.min, train_ds.max, eval_ds.min, eval_ds.max
+        if FLAGS.copy_metrics and rank == 0:
+            copy_train = train_ds.take_examples(FLAGS.copy_train_examples or len(train_ds.array))
     num = len(real)
     lo, hi = shard_bounds(num, world, rank)
     model, rng = load_model(FLAGS, shape, dev)
@@ -454,6 +513,8 @@ def main(argv):
                          prd_runs=FLAGS.prd_runs, ndb_bins=FLAGS.ndb_bins)
         writer.close()
         train_utils.log_metrics(stats, 1, 1)
+    if rank == 0 and FLAGS.copy_metrics:                                    # on the final samples only, with or without --compute_metrics
+        copy_metrics_report(FLAGS, copy_train, real, generated, dev)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -256,6 +256,12 @@ ENGINE_FLAGS: List[FlagDef] = [
     _D("prd_clusters", "int", 20, "--cluster_metrics: clusters of the PRD histogram (2..128)."),
     _D("prd_runs", "int", 10, "--cluster_metrics: k-means runs the PRD curve is averaged over (1..100)."),
     _D("ndb_bins", "int", 50, "--cluster_metrics: bins of the NDB score (2..128)."),
+    _D("copy_metrics", "bool", False, "sample_ncsn: search the training set for the nearest neighbours of every generated example "
+       "and write {sampling_dir}/ncsn/copy_report.json (authenticity of Alaa et al. 2022, nearest-training distances against "
+       "those of the eval examples, exact copies; frames and whole sequences) and nearest_train.pkl (DESIGN.md section 24)."),
+    _D("copy_k", "int", 1, "--copy_metrics: training neighbours kept per generated row (1..8)."),
+    _D("copy_train_examples", "int", 0, "--copy_metrics: search the first N training examples; 0 = all of them (--synthetic: as "
+       "many as --sample_size)."),
     _D("graph", "bool", True, "Capture the sampling step in a hipGraph."),
     _D("ddim_steps", "int", 0, "sample_ncsn --sampling=ddpm: walk this many evenly spaced timesteps of the schedule with the strided "
        "(DDIM, Song et al. 2021) sampler instead of all --num_sigmas of them: 0 (off) or 2..num_sigmas network evaluations per "

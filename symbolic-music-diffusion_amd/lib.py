@@ -238,6 +238,9 @@ _SIGS = {
     "smd_ball_cover_workspace_bytes": (c_i64, [C.c_int, C.c_int]),
     "smd_ball_cover": (C.c_int, [c_void, c_i64, C.c_int, c_void, c_i64, C.c_int, C.c_int, c_void, c_void, C.c_int, c_void, c_i64,
                                  c_void, c_void, c_void]),
+    "smd_nn_search_workspace_bytes": (c_i64, [C.c_int, C.c_int, C.c_int]),
+    "smd_nn_search": (C.c_int, [c_void, c_i64, C.c_int, c_i64, c_void, c_i64, C.c_int, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, c_void,
+                                c_i64, c_void, c_void, c_void]),
     "smd_kmeans_assign_workspace_bytes": (c_i64, [C.c_int, C.c_int]),
     "smd_kmeans_assign": (C.c_int, [c_void, c_i64, C.c_int, C.c_int, c_void, C.c_int, C.c_int, c_void, c_i64, c_void, c_void, c_void,
                                     c_void, c_void]),

@@ -19,6 +19,11 @@ define: Kynkaanniemi et al. 2019 as fixed in DESIGN.md section 14, on csrc/nn_me
 (precision / recall / f1 from the PRD histogram of Sajjadi et al. 2018, sample_ncsn.py:141-146; ndb of Richardson & Weiss 2018,
 :160) as fixed in DESIGN.md section 15, on the full-batch Lloyd ``kmeans`` of csrc/kmeans.hip (``kmeans_assign``,
 ``kmeans_update``); the histograms, the PRD curve and the two-proportion test are host float64.
+
+``nn_search``, ``TrainIndex``, ``authenticity`` and ``copy_report`` (``copy_metrics`` for frames and sequences together) ask what
+none of the scores above can: which TRAINING row a sample is closest to and whether it is closer than unseen data is -- the
+authenticity score of Alaa et al. 2022 and the nearest-training-neighbour distances, as fixed in DESIGN.md section 24, on
+csrc/nn_search.hip.  The training set is streamed slab by slab and may stay on the host.
 """
 from __future__ import annotations
 
@@ -580,3 +585,179 @@ def cluster_metrics(real, samples, prd_clusters: int = 20, prd_runs: int = 10, n
     recall, precision = prd_f_beta_score(prd, beta=8)
     return {"precision": precision, "recall": recall, "f1": f1_score(precision, recall),
             "ndb": ndb_score(ref, samples, k=ndb_bins, seed=seed)}
+
+
+# ---------------------------------------------------------------------------------------------------- copying
+KNN_MAX_K = 8             # SMD_KNN_MAX_K of include/smd_hip.h
+COPY_METRICS_VERSION = "copy-metrics-1 (DESIGN.md section 24: authenticity d2 >= r1_sq[i*], ties to the lower index, medians of distances)"
+
+
+def nn_search(q: torch.Tensor, x: torch.Tensor, k: int = 1, *, q_base: int = 0, x_base: int = 0, exclude_self: bool = False,
+              out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d2 fp32 (nq, k), idx int64 (nq, k)) on the device: for every row of the fp32 (nq, d) cuda tensor ``q`` the k rows of ``x``
+    (nx, d) with the smallest (squared distance, global index) in lexicographic order, the global index of row i of ``x`` being
+    ``x_base + i``; ascending, equal distances by the lower index.  Where fewer than k candidates exist the tail is (+inf, -1).
+    ``exclude_self``: the pair with q_base + j == x_base + i takes no part (by index: a duplicate of the query still counts).
+    ``out=(d2, idx)``, a previous result for the same queries and k: the rows of ``x`` are merged into it, in place, and it is
+    returned -- one call on all candidates and calls on any partition of them into slabs, in any order, give the same bits.
+    1 <= k <= 8.  Enqueued on the current stream, nothing waits; two calls give the same bits."""
+    L = _lib.get_lib()
+    _check_rows("nn_search", q, x)
+    if int(k) != k:
+        raise ValueError(f"k={k!r}: nn_search takes an integer k")
+    k = int(k)
+    q, x = _rows(q), _rows(x)
+    nq, d = q.shape
+    nx, dx = x.shape
+    if dx != d:
+        raise ValueError(f"nn_search: d mismatch ({d} vs {dx})")
+    if out is None:
+        d2 = torch.empty((nq, max(k, 1)), dtype=torch.float32, device=q.device)
+        idx = torch.empty((nq, max(k, 1)), dtype=torch.int64, device=q.device)
+    else:
+        d2, idx = out
+        for t, dt in ((d2, torch.float32), (idx, torch.int64)):
+            if tuple(t.shape) != (nq, k) or t.dtype != dt or t.device != q.device or not t.is_contiguous():
+                raise ValueError(f"nn_search: out must be contiguous (d2 fp32, idx int64) tensors of shape ({nq}, {k}) on the queries' device")
+    ws_bytes = L.smd_nn_search_workspace_bytes(nq, nx, k)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=q.device)
+    _lib.check(L.smd_nn_search(q.data_ptr(), q.stride(0), nq, int(q_base), x.data_ptr(), x.stride(0), nx, int(x_base), d, k,
+                               int(bool(exclude_self)), int(out is not None), ws.data_ptr(), ws_bytes, d2.data_ptr(), idx.data_ptr(),
+                               _stream(q.device)), "smd_nn_search")
+    return d2, idx
+
+
+class TrainIndex:
+    """The training set of the copy metrics as an iterable of slabs (numpy arrays or tensors, on the host or the device; one
+    array is one slab), searched exhaustively slab by slab: a host slab is uploaded when its turn comes and dropped after it, so
+    device memory holds at most two slabs and the outputs.  A slab of more than two dimensions is read as frames of its last
+    axis, or with ``sequences`` as one row per leading index (an (N, S, C) slab: N*S rows of C, or N rows of S*C).  Global row
+    indices count through the slabs in order.  Kept on the device: ``r1_sq[n]``, every training row's squared distance to its
+    nearest OTHER training row (``nn_search`` of every slab against every slab, self excluded by index), ``nn1_idx[n]``, that
+    row, and ``norm[n]`` (float64), the rows' Euclidean norms."""
+
+    def __init__(self, slabs, device=None, sequences: bool = False):
+        self.source = slabs
+        self.sequences = bool(sequences)
+        if torch.is_tensor(slabs) or isinstance(slabs, np.ndarray):
+            slabs = [slabs]
+        slabs = list(slabs)
+        self.device = _device(*slabs) if device is None else torch.device(device)
+        self._slabs = [s if torch.is_tensor(s) else torch.from_numpy(np.asarray(s)) for s in slabs]
+        sizes = [int(self._view(s).shape[0]) for s in self._slabs]
+        self.offsets = [0] + [int(v) for v in np.cumsum(sizes)]
+        self.n = self.offsets[-1]
+        dims = {int(self._view(s).shape[1]) for s in self._slabs}
+        if len(dims) != 1:
+            raise ValueError(f"TrainIndex: the slabs must agree in their row length (got {sorted(dims)})")
+        self.d = dims.pop()
+        if self.n < 2:
+            raise ValueError(f"TrainIndex: {self.n} training rows: a nearest OTHER row needs two")
+        self.r1_sq = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        self.nn1_idx = torch.empty(self.n, dtype=torch.int64, device=self.device)
+        self.norm = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        for a in range(len(self._slabs)):
+            xa = self.slab(a)
+            lo, hi = self.offsets[a], self.offsets[a + 1]
+            d2, idx = self.query(xa, 1, exclude_self=True, q_base=lo, resident=(a, xa))
+            self.r1_sq[lo:hi] = d2[:, 0]
+            self.nn1_idx[lo:hi] = idx[:, 0]
+            self.norm[lo:hi] = xa.double().pow(2).sum(1).sqrt()
+
+    def _view(self, t: torch.Tensor) -> torch.Tensor:
+        if t.dim() <= 1:
+            return t.reshape(-1, 1)
+        return t.reshape(t.shape[0], -1) if self.sequences else t.reshape(-1, t.shape[-1])
+
+    def rows(self, a) -> torch.Tensor:
+        """``a`` (numpy or tensor) as this index reads it: contiguous fp32 (n, d) rows on its device"""
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
+        return self._view(t).to(device=self.device, dtype=torch.float32).contiguous()
+
+    def slab(self, a: int) -> torch.Tensor:
+        return self.rows(self._slabs[a])
+
+    def query(self, rows, k: int = 1, exclude_self: bool = False, q_base: int = 0, resident=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(d2, idx) of ``nn_search`` for ``rows`` against ALL slabs, accumulated slab by slab.  ``exclude_self``: ``rows`` are
+        the training rows q_base, q_base + 1, ...: each leaves itself out.  ``resident=(a, tensor)``: slab a is on the device
+        already."""
+        q = rows if torch.is_tensor(rows) and rows.is_cuda and rows.dim() == 2 and rows.dtype == torch.float32 else self.rows(rows)
+        if q.shape[1] != self.d:
+            raise ValueError(f"TrainIndex.query: d mismatch ({self.d} vs {q.shape[1]})")
+        out = None
+        for b in range(len(self._slabs)):
+            xb = resident[1] if resident is not None and resident[0] == b else self.slab(b)
+            out = nn_search(q, xb, k, q_base=q_base, x_base=self.offsets[b], exclude_self=exclude_self, out=out)
+        return out
+
+    def is_same(self, other) -> bool:
+        return other is self or other is self.source
+
+
+def _nearest_train(index: TrainIndex, rows, k: int):
+    """(d2, idx, norms float64) of ``rows`` against the training set; the training set itself (the index or the object it was
+    built from, as ``kernel_mmds`` detects identity) is searched leave-one-out"""
+    if index.is_same(rows):
+        parts = [index.query(index.slab(a), k, exclude_self=True, q_base=index.offsets[a]) for a in range(len(index._slabs))]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), index.norm, True
+    q = index.rows(rows)
+    d2, idx = index.query(q, k)
+    return d2, idx, q.double().pow(2).sum(1).sqrt(), False
+
+
+def _authentic(index: TrainIndex, d2: torch.Tensor, idx: torch.Tensor, same: bool) -> torch.Tensor:
+    """d2(q, x_i*) >= r1_sq[i*].  Leave-one-out (``same``): when row i is in turn the nearest other row of its i*, both sides are
+    the distance of ONE pair and the row sits on the boundary, which counts -- decided by index, since the fp32 d2 of a pair is
+    formed around the query's norm and its last bit can differ between the two directions."""
+    nearest = idx[:, 0]
+    a = d2[:, 0] >= index.r1_sq[nearest]
+    if same:
+        a |= index.nn1_idx[nearest] == torch.arange(index.n, device=a.device)
+    return a
+
+
+def authenticity(index: TrainIndex, fake) -> Dict[str, object]:
+    """The authenticity score of Alaa et al. 2022: with i* the nearest training row of a fake row q (``nn_search`` order), q is
+    authentic when d2(q, x_i*) >= r1_sq[i*] -- it is no closer to x_i* than x_i*'s nearest other training row is; the boundary
+    counts as authentic.  {"authenticity": the mean over the fake rows, "authentic": the per-row flags (numpy bool)}.  When
+    ``fake`` is the training set itself (the index, or the object it was built from) pair (i, i) is excluded: leave-one-out."""
+    d2, idx, _, same = _nearest_train(index, fake, 1)
+    a = _authentic(index, d2, idx, same).cpu().numpy()
+    return {"authenticity": float(a.mean()), "authentic": a}
+
+
+def _median_distance(d2: torch.Tensor) -> float:
+    return float(np.median(np.sqrt(d2[:, 0].cpu().numpy().astype(np.float64))))
+
+
+def copy_report(index: TrainIndex, held_out, fake, k: int = 1) -> Dict[str, object]:
+    """How close the ``fake`` rows sit to the training set, next to how close unseen (``held_out``) rows do:
+    authenticity (see ``authenticity``); median_nn_fake / median_nn_held_out, the median distance (not squared) to the nearest
+    training row; copy_gap, their ratio (below 1: the samples are closer to the training data than unseen data is);
+    exact_copies, the fake rows whose nearest d2 is at most the fp32 error bound (d + 4) 2^-24 (|q| + |x_i*|)^2 of that pair
+     -- indistinguishable from distance 0; nn_d2, nn_idx (numpy (n, k)): the k nearest training rows of
+    every fake row; k, n_train, n_fake, n_held_out, version."""
+    d2, idx, qn, same = _nearest_train(index, fake, k)
+    dh = _nearest_train(index, held_out, 1)[0]
+    m = (index.d + 4) * 2.0 ** -24 * (qn + index.norm[idx[:, 0]]) ** 2
+    mf, mh = _median_distance(d2), _median_distance(dh)
+    gap = mf / mh if mh > 0 else (float("inf") if mf > 0 else float("nan"))
+    return {"authenticity": float(_authentic(index, d2, idx, same).double().mean()), "median_nn_fake": mf, "median_nn_held_out": mh,
+            "copy_gap": gap, "exact_copies": int((d2[:, 0].double() <= m).sum()), "nn_d2": d2.cpu().numpy(), "nn_idx": idx.cpu().numpy(),
+            "k": int(k), "n_train": index.n, "n_fake": int(d2.shape[0]), "n_held_out": int(dh.shape[0]), "version": COPY_METRICS_VERSION}
+
+
+COPY_SCALARS = ("authenticity", "median_nn_fake", "median_nn_held_out", "copy_gap", "exact_copies")
+
+
+def copy_metrics(train_slabs, held_out, fake, k: int = 1, device=None) -> Dict[str, object]:
+    """``copy_report`` at both levels of (N, S, C) sets: frames (N*S rows of C) under the plain keys and sequences (N rows of
+    S*C) under the same keys with the suffix ``_seq`` -- a lifted two-bar phrase and a lifted piece are different findings.
+    ``train_slabs``: a list of (n_i, S, C) arrays (walked once per level) or one array."""
+    out: Dict[str, object] = {}
+    for sequences, suffix in ((False, ""), (True, "_seq")):
+        index = TrainIndex(train_slabs, device, sequences=sequences)
+        rep = copy_report(index, held_out, fake, k)
+        out.update({name + suffix: v for name, v in rep.items() if name not in ("k", "version")})
+    out.update(k=int(k), version=COPY_METRICS_VERSION)
+    return out
