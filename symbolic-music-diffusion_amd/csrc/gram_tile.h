@@ -1,5 +1,6 @@
 // The 128 x 128 Gram tile on exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) that the evaluation kernels share: metrics.hip (pair
-// sums, moments) and nn_metrics.hip (k-NN radii, ball cover).  Every product is an fp32 fma in k order.
+// sums, moments), kmeans.hip (assignment) and, through the query-column walk of gram_walk.h, nn_metrics.hip and nn_search.hip.
+// Every product is an fp32 fma in k order.  The row norms and the host-side helpers of those files' entry points live here too.
 #pragma once
 #include "smd_common.h"
 
@@ -85,8 +86,30 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const float* __restrict_
   out[i] = s;
 }
 
+// |row|^2 of the n rows of x into nrm, and of the ny rows of y into nrm_y unless y is null
+inline int launch_row_norms(const float* x, int n, int64_t ld, float* nrm, const float* y, int ny, int64_t ldy, float* nrm_y, int d,
+                            hipStream_t st) {
+  row_norms_kernel<<<(n + 255) / 256, 256, 0, st>>>(x, n, d, ld, nrm);
+  SMD_LAUNCH_CHECK();
+  if (y) {
+    row_norms_kernel<<<(ny + 255) / 256, 256, 0, st>>>(y, ny, d, ldy, nrm_y);
+    SMD_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- host side
+inline int64_t tiles_of(int n) { return ((int64_t)n + MT - 1) / MT; }
+
+// HIP bounds a launch by gridDim.x * blockDim.x < 2^32 work-items: 2^24 - 1 workgroups of NT = 256
+constexpr int64_t MAX_WORKGROUPS = (((int64_t)1 << 32) - 1) / NT;
+inline bool fits_one_launch(int64_t workgroups) { return workgroups * NT < ((int64_t)1 << 32); }
+
 inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 inline int64_t up8(int64_t b) { return (b + 7) & ~(int64_t)7; }
+// the part of a workspace that starts `bytes` into it
+template <typename T>
+inline T* ws_at(void* workspace, int64_t bytes) { return reinterpret_cast<T*>(reinterpret_cast<char*>(workspace) + bytes); }
 
 }  // namespace

@@ -31,7 +31,6 @@ static_assert(KMAX == MT && KMAX <= 2 * 64, "the centres are one tile of the Gra
 constexpr int UPD_ROWS = 256;      // rows per slab of the update
 constexpr int UPD_COLS = 64;       // columns per strip: one per lane
 
-inline int64_t tiles_of(int n) { return ((int64_t)n + MT - 1) / MT; }
 inline int64_t slabs_of(int n) { return ((int64_t)n + UPD_ROWS - 1) / UPD_ROWS; }
 inline int64_t strips_of(int d) { return ((int64_t)d + UPD_COLS - 1) / UPD_COLS; }
 
@@ -219,22 +218,17 @@ int smd_kmeans_assign(const float* x, int64_t ld, int n, int d, const float* cen
   SMD_ARG_CHECK(al4(x) && al4(centres) && al4(labels) && al4(min_d2) && al8(inertia) && al8(changed) && al8(workspace),
                 "smd_kmeans_assign: x, centres, labels, min_d2 must be 4-byte and inertia, changed, workspace 8-byte aligned");
   const int64_t tiles = tiles_of(n);
-  // HIP bounds a launch by gridDim.x * blockDim.x < 2^32 work-items: 2^24 - 1 workgroups of NT = 256; any int n stays below it,
-  // the check keeps that true should the tile shrink
-  SMD_ARG_CHECK(tiles * NT < ((int64_t)1 << 32), "smd_kmeans_assign: %lld row slabs exceed one launch (at most %lld workgroups)",
-                (long long)tiles, (long long)((((int64_t)1 << 32) - 1) / NT));
+  // any int n stays below the bound; the check keeps that true should the tile shrink
+  SMD_ARG_CHECK(fits_one_launch(tiles), "smd_kmeans_assign: %lld row slabs exceed one launch (at most %lld workgroups)",
+                (long long)tiles, (long long)MAX_WORKGROUPS);
   const int64_t need = smd_kmeans_assign_workspace_bytes(n, k);
   SMD_ARG_CHECK(workspace_bytes >= need, "smd_kmeans_assign: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  char* ws = reinterpret_cast<char*>(workspace);
-  float* nx = reinterpret_cast<float*>(ws);
-  float* nc = reinterpret_cast<float*>(ws + up8((int64_t)n * 4));
-  double* part_inertia = reinterpret_cast<double*>(ws + up8((int64_t)n * 4) + up8((int64_t)KMAX * 4));
+  float* nx = ws_at<float>(workspace, 0);
+  float* nc = ws_at<float>(workspace, up8((int64_t)n * 4));
+  double* part_inertia = ws_at<double>(workspace, up8((int64_t)n * 4) + up8((int64_t)KMAX * 4));
   int64_t* part_changed = reinterpret_cast<int64_t*>(part_inertia + tiles);
-  row_norms_kernel<<<(n + 255) / 256, 256, 0, st>>>(x, n, d, ld, nx);
-  SMD_LAUNCH_CHECK();
-  row_norms_kernel<<<1, 256, 0, st>>>(centres, k, d, (int64_t)d, nc);
-  SMD_LAUNCH_CHECK();
+  if (const int e = launch_row_norms(x, n, ld, nx, centres, k, (int64_t)d, nc, d, st)) return e;
   AssignArgs a;
   a.x = x; a.ld = ld; a.c = centres; a.n = n; a.d = d; a.k = k; a.has_prev = prev ? 1 : 0; a.nx = nx; a.nc = nc;
   a.labels = labels; a.min_d2 = min_d2; a.part_inertia = part_inertia; a.part_changed = part_changed;

@@ -2,7 +2,7 @@
 // MFMA (v_mfma_f32_32x32x2_f32): no bf16 anywhere, every product is an fp32 fma in k order.
 //
 //   pair_sums    sum_ij exp(-g_rbf max(d2_ij, 0)) and sum_ij (g_poly <x_i,y_j> + c0)^degree in ONE pass over X Y^T: the
-//                Gram tile stays in registers and both epilogues read it; the N x N kernel matrix is never written.
+//                Gram tile (gram_tile.h) stays in registers and both epilogues read it; the N x N kernel matrix is never written.
 //                d2 = (-2 <x,y> + |x|^2) + |y|^2 in the order of sklearn 0.19's euclidean_distances (the pinned reference).
 //   moments      fp64 column mean and ddof = 1 covariance: fp64 column sums, then the Gram of the centred fp32 rows on
 //                the same MFMA, split over row slabs and reduced in fixed order in fp64 (frechet_distance's np.mean / np.cov).
@@ -51,42 +51,9 @@ __global__ __launch_bounds__(NT) void pair_sums_kernel(PairArgs a) {
   if (t < MT) na[t] = (i0 + t < a.nx) ? a.nrm_x[i0 + t] : 0.0f;
   else nb[t - MT] = (j0 + t - MT < a.ny) ? a.nrm_y[j0 + t - MT] : 0.0f;
 
-  // loader: element q of this thread is (row idx / BK, k idx % BK), idx = t + NT q: 16 consecutive k of a row per 16 lanes.
-  // Rows past n and k past d load zeros (masked again in the epilogue: a zero row would still add exp(0) = 1).
-  float ra[LOADS], rb[LOADS];
-  auto load = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < LOADS; ++q) {
-      const int idx = t + NT * q, r = idx / BK, k = k0 + idx % BK;
-      ra[q] = (i0 + r < a.nx && k < a.d) ? a.x[(int64_t)(i0 + r) * a.ldx + k] : 0.0f;
-      rb[q] = (j0 + r < a.ny && k < a.d) ? a.y[(int64_t)(j0 + r) * a.ldy + k] : 0.0f;
-    }
-  };
-  auto store = [&]() {
-#pragma unroll
-    for (int q = 0; q < LOADS; ++q) {
-      const int idx = t + NT * q, r = idx / BK, kk = idx % BK;
-      As[kk * LDP + r] = ra[q];
-      Bs[kk * LDP + r] = rb[q];
-    }
-  };
+  // Padded rows load zeros and are masked again in the epilogue: a zero row would still add exp(0) = 1.
   f32x16_t acc[2][2];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
-
-  const int stages = (a.d + BK - 1) / BK;
-  load(0);
-  for (int s = 0; s < stages; ++s) {
-    __syncthreads();                       // the previous stage's reads are done
-    store();
-    __syncthreads();
-    if (s + 1 < stages) load((s + 1) * BK);   // next stage's global reads in flight under this stage's MFMAs
-    mfma_stage(As, Bs, wr, wc, lane, acc);
-  }
+  gram_tile(a.x, a.ldx, a.nx, i0, a.y, a.ldy, a.ny, j0, a.d, As, Bs, acc);   // its barriers publish na, nb
 
   // epilogue: both kernels from the same Gram values; fp32 for the 16 values of one MFMA tile, then fp64
   const bool diag = a.symmetric && bi == bj;
@@ -252,7 +219,7 @@ __global__ __launch_bounds__(256) void cov_reduce_kernel(const double* __restric
 }
 
 int64_t pair_tiles(int nx, int ny, int symmetric) {
-  const int64_t tx = (nx + MT - 1) / MT, ty = (ny + MT - 1) / MT;
+  const int64_t tx = tiles_of(nx), ty = tiles_of(ny);
   return symmetric ? tx * (tx + 1) / 2 : tx * ty;
 }
 
@@ -280,20 +247,14 @@ int smd_pair_kernel_sums(const float* x, int64_t ldx, int nx, const float* y, in
   SMD_ARG_CHECK(workspace_bytes >= need, "smd_pair_kernel_sums: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
                 (long long)need);
   const int64_t tiles = pair_tiles(nx, ny, symmetric);
-  // HIP bounds a launch by gridDim.x * blockDim.x < 2^32 work-items: 2^24 - 1 workgroups of NT = 256 (nx = ny ~ 524k, full mode)
-  SMD_ARG_CHECK(tiles * NT < ((int64_t)1 << 32), "smd_pair_kernel_sums: %lld tiles of %d x %d exceed one launch (at most %lld)",
-                (long long)tiles, MT, MT, (long long)((((int64_t)1 << 32) - 1) / NT));
+  SMD_ARG_CHECK(fits_one_launch(tiles), "smd_pair_kernel_sums: %lld tiles of %d x %d exceed one launch (at most %lld)",
+                (long long)tiles, MT, MT, (long long)MAX_WORKGROUPS);      // reached at nx = ny ~ 524k, full mode
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (symmetric) { y = x; ldy = ldx; }
-  float* nrm_x = reinterpret_cast<float*>(workspace);
+  float* nrm_x = ws_at<float>(workspace, 0);
   float* nrm_y = symmetric ? nrm_x : nrm_x + nx;
-  double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + up8((int64_t)(nx + (symmetric ? 0 : ny)) * 4));
-  row_norms_kernel<<<(nx + 255) / 256, 256, 0, st>>>(x, nx, d, ldx, nrm_x);
-  SMD_LAUNCH_CHECK();
-  if (!symmetric) {
-    row_norms_kernel<<<(ny + 255) / 256, 256, 0, st>>>(y, ny, d, ldy, nrm_y);
-    SMD_LAUNCH_CHECK();
-  }
+  double* partial = ws_at<double>(workspace, up8((int64_t)(nx + (symmetric ? 0 : ny)) * 4));
+  if (const int e = launch_row_norms(x, nx, ldx, nrm_x, symmetric ? nullptr : y, ny, ldy, nrm_y, d, st)) return e;
+  if (symmetric) { y = x; ldy = ldx; }
   PairArgs a;
   a.x = x; a.y = y; a.ldx = ldx; a.ldy = ldy; a.nx = nx; a.ny = ny; a.d = d; a.symmetric = symmetric ? 1 : 0;
   a.degree = degree; a.tiles_y = (ny + MT - 1) / MT; a.g_rbf = gamma_rbf; a.g_poly = gamma_poly; a.c0 = coef0;

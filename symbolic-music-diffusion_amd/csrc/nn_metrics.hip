@@ -5,10 +5,8 @@
 //   knn_radii    r2[i] = the k-th smallest d2 from row i of X to its other rows (self excluded by index).
 //   ball_cover   for each query q: covered = OR_j (d2(q, x_j) <= r2[j]) and realism2 = max over kept j of r2[j] / max(d2, FLT_MIN).
 //
-// Orientation: the rows whose answer is sought (queries) are the COLUMNS of the accumulator tile, so a lane owns two queries
-// (lane & 31 of its wave's two 32-wide column blocks) and sees 32 candidates of each per tile in its registers: the running
-// state is two sorted k-lists (or two flags and two maxima) per lane.  The other side (candidates / centres) runs over the
-// accumulator rows and is walked in chunks of CHUNK tiles per workgroup.
+// Both are the query-column walk of gram_walk.h (orientation, chunking, the four-partial fold and the slots are described
+// there) with an operation each: two sorted k-lists of distances per lane, or two flags and two maxima.
 //
 // d2 = (-2 <x, y> + |x|^2) + |y|^2 clamped at 0, as in metrics.hip; x is the row that OWNS the radius (the query of knn_radii,
 // the centre of ball_cover), so the d2 that made a radius and the d2 that is compared with it are the same bits: a row that is
@@ -19,29 +17,11 @@
 #include <float.h>
 #include <math.h>
 
-#include "gram_tile.h"
-#include "../../include/smd_hip.h"
+#include "gram_walk.h"
 
 namespace {
 
-constexpr int CHUNK = 16;          // candidate / centre tiles per workgroup (2048 rows)
 constexpr int KMAX = SMD_KNN_MAX_K;
-
-inline int64_t tiles_of(int n) { return ((int64_t)n + MT - 1) / MT; }
-inline int64_t splits_of(int n) { return (tiles_of(n) + CHUNK - 1) / CHUNK; }
-
-// sorted ascending l[0..K): put v in if it is below the largest
-template <int K>
-__device__ __forceinline__ void topk_insert(float (&l)[K], float v) {
-  if (v < l[K - 1]) {
-#pragma unroll
-    for (int t = 0; t < K; ++t) {
-      const float lo = fminf(l[t], v);
-      v = fmaxf(l[t], v);
-      l[t] = lo;
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------- k-NN radii
 struct KnnArgs {
@@ -52,63 +32,42 @@ struct KnnArgs {
 };
 
 template <int K>
-__global__ __launch_bounds__(NT, 2) void knn_partial_kernel(KnnArgs a) {
-  __shared__ float As[BK * LDP];
-  __shared__ float Bs[BK * LDP];
-  __shared__ float nc[MT], nq[MT];
-  __shared__ float lists[4][K][MT];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w >> 1, wc = w & 1;
-  const int tile = smd_xcd_band(blockIdx.x, gridDim.x);      // neighbours share the query tile and an L2
-  const int qb = tile / a.splits, s = tile - qb * a.splits;
-  const int j0 = qb * MT;
-  const int c_end = min(a.tiles, (s + 1) * CHUNK);
-  if (t < MT) nq[t] = (j0 + t < a.n) ? a.nrm[j0 + t] : 0.0f;
+struct KnnOp {
+  struct Shared { float lists[4][K][MT]; };
+  float* part;
   float best[2][K];
-#pragma unroll
-  for (int n = 0; n < 2; ++n)
+  __device__ __forceinline__ void init(int n, int) {
 #pragma unroll
     for (int e = 0; e < K; ++e) best[n][e] = INFINITY;
-
-  f32x16_t acc[2][2];
-  for (int cb = s * CHUNK; cb < c_end; ++cb) {
-    const int i0 = cb * MT;
-    __syncthreads();                                          // the previous tile's epilogue has read nc
-    if (t >= MT) nc[t - MT] = (i0 + t - MT < a.n) ? a.nrm[i0 + t - MT] : 0.0f;
-    gram_tile(a.x, a.ld, a.n, i0, a.x, a.ld, a.n, j0, a.d, As, Bs, acc);   // rows: candidates, columns: queries
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-      const int jl = wc * 64 + n * 32 + (lane & 31), j = j0 + jl;
-      const float nj = nq[jl];
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int il = wr * 64 + m * 32 + cd_row(r, lane), i = i0 + il;
-          float d2 = fmaxf((-2.0f * acc[m][n][r] + nj) + nc[il], 0.0f);
-          if (i >= a.n || i == j) d2 = INFINITY;              // padding, and self by index: a duplicate of row j still counts
-          topk_insert<K>(best[n], d2);
-        }
-    }
   }
-  // the four partial lists of a query column (2 row halves of the tile x 2 lane halves) -> one
-  const int p = wr * 2 + (lane >> 5);
+  __device__ __forceinline__ void stage(Shared&, int, int, bool) {}
+  __device__ __forceinline__ void visit(Shared&, int n, const WalkElem& e) {
+    float d2 = d2_of(e.g, e.n_query, e.n_cand);
+    if (e.pad() || e.i == e.j) d2 = INFINITY;                   // padding, and self by index: a duplicate of row j still counts
+    list_insert<K>(best[n], d2);
+  }
+  __device__ __forceinline__ void park(Shared& sh, int p, int n, int jl) {
 #pragma unroll
-  for (int n = 0; n < 2; ++n)
-#pragma unroll
-    for (int e = 0; e < K; ++e) lists[p][e][wc * 64 + n * 32 + (lane & 31)] = best[n][e];
-  __syncthreads();
-  if (t < MT && j0 + t < a.n) {
+    for (int e = 0; e < K; ++e) sh.lists[p][e][jl] = best[n][e];
+  }
+  __device__ __forceinline__ void fold(Shared& sh, int jl, int64_t slot) {
     float l[K];
 #pragma unroll
-    for (int e = 0; e < K; ++e) l[e] = lists[0][e][t];
+    for (int e = 0; e < K; ++e) l[e] = sh.lists[0][e][jl];
 #pragma unroll
     for (int q = 1; q < 4; ++q)
 #pragma unroll
-      for (int e = 0; e < K; ++e) topk_insert<K>(l, lists[q][e][t]);
-    float* out = a.part + ((int64_t)s * a.n + j0 + t) * K;
+      for (int e = 0; e < K; ++e) list_insert<K>(l, sh.lists[q][e][jl]);
 #pragma unroll
-    for (int e = 0; e < K; ++e) out[e] = l[e];
+    for (int e = 0; e < K; ++e) part[slot * K + e] = l[e];
   }
+};
+
+template <int K>
+__global__ __launch_bounds__(NT, 2) void knn_partial_kernel(KnnArgs a) {
+  KnnOp<K> op;
+  op.part = a.part;
+  query_walk(Walk{a.x, a.ld, a.n, a.nrm, a.x, a.ld, a.n, a.nrm, a.d, a.tiles, a.splits}, op);
 }
 
 // r2[i] = the k-th smallest of the splits' lists of row i
@@ -122,7 +81,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict_
   for (int s = 1; s < splits; ++s) {
     const float* p = part + ((int64_t)s * n + i) * K;
 #pragma unroll
-    for (int e = 0; e < K; ++e) topk_insert<K>(l, p[e]);
+    for (int e = 0; e < K; ++e) list_insert<K>(l, p[e]);
   }
   r2[i] = l[K - 1];
 }
@@ -146,68 +105,44 @@ struct CoverArgs {
   uint8_t* part_cov;      // [splits][nq]
 };
 
-__global__ __launch_bounds__(NT, 2) void ball_cover_partial_kernel(CoverArgs a) {
-  __shared__ float As[BK * LDP];
-  __shared__ float Bs[BK * LDP];
-  __shared__ float nc[MT], nq[MT];
-  __shared__ float rc[MT], rk[MT];       // radius^2 of the tile's centres for coverage / for realism; -1 where it does not apply
-  __shared__ float pmax[4][MT];
-  __shared__ int pcov[4][MT];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w >> 1, wc = w & 1;
-  const int tile = smd_xcd_band(blockIdx.x, gridDim.x);
-  const int qb = tile / a.splits, s = tile - qb * a.splits;
-  const int j0 = qb * MT;
-  const int c_end = min(a.tiles_x, (s + 1) * CHUNK);
-  if (t < MT) nq[t] = (j0 + t < a.nq) ? a.nrm_q[j0 + t] : 0.0f;
-  float mx[2] = {0.0f, 0.0f};
-  int cov[2] = {0, 0};
+struct CoverOp {
+  struct Shared {
+    float rc[MT], rk[MT];     // radius^2 of the tile's centres for coverage / for realism; -1 where it does not apply
+    float pmax[4][MT];
+    int pcov[4][MT];
+  };
+  const CoverArgs& a;
+  float mx[2];
+  int cov[2];
+  __device__ __forceinline__ void init(int n, int) { mx[n] = 0.0f; cov[n] = 0; }
+  __device__ __forceinline__ void stage(Shared& sh, int il, int i, bool ok) {
+    const float r = ok ? a.r2[i] : -1.0f;                     // d2 >= 0 is never <= -1: padded centres cover nothing
+    sh.rc[il] = r;
+    sh.rk[il] = (ok && (!a.keep || a.keep[i])) ? r : -1.0f;
+  }
+  __device__ __forceinline__ void visit(Shared& sh, int n, const WalkElem& e) {
+    const float d2 = d2_of(e.g, e.n_cand, e.n_query);         // x = the centre: the d2 its radius was taken from
+    const bool diag = a.exclude_diagonal && e.i0 == e.j0;     // Q is X: pair (i, i) lies on the diagonal of the diagonal tiles
+    const bool self = diag && e.il == e.jl;
+    const float c = self ? -1.0f : sh.rc[e.il], k = self ? -1.0f : sh.rk[e.il];
+    cov[n] |= (d2 <= c) ? 1 : 0;
+    const float dd = fmaxf(d2, FLT_MIN);
+    // IEEE division only where the quotient can pass the running maximum: fl(k / dd) > mx needs k > mx dd (1 - 2^-24)
+    if (k > 0.999f * mx[n] * dd) mx[n] = fmaxf(mx[n], fminf(k / dd, FLT_MAX));
+  }
+  __device__ __forceinline__ void park(Shared& sh, int p, int n, int jl) {
+    sh.pmax[p][jl] = mx[n];
+    sh.pcov[p][jl] = cov[n];
+  }
+  __device__ __forceinline__ void fold(Shared& sh, int jl, int64_t slot) {
+    a.part_max[slot] = fmaxf(fmaxf(sh.pmax[0][jl], sh.pmax[1][jl]), fmaxf(sh.pmax[2][jl], sh.pmax[3][jl]));
+    a.part_cov[slot] = (uint8_t)(sh.pcov[0][jl] | sh.pcov[1][jl] | sh.pcov[2][jl] | sh.pcov[3][jl]);
+  }
+};
 
-  f32x16_t acc[2][2];
-  for (int cb = s * CHUNK; cb < c_end; ++cb) {
-    const int i0 = cb * MT;
-    __syncthreads();                                          // the previous tile's epilogue has read nc, rc, rk
-    if (t >= MT) {
-      const int il = t - MT, i = i0 + il;
-      const bool ok = i < a.nx;
-      const float r = ok ? a.r2[i] : -1.0f;                   // d2 >= 0 is never <= -1: padded centres cover nothing
-      nc[il] = ok ? a.nrm_x[i] : 0.0f;
-      rc[il] = r;
-      rk[il] = (ok && (!a.keep || a.keep[i])) ? r : -1.0f;
-    }
-    gram_tile(a.x, a.ldx, a.nx, i0, a.q, a.ldq, a.nq, j0, a.d, As, Bs, acc);   // rows: centres, columns: queries
-    const bool diag = a.exclude_diagonal && i0 == j0;         // Q is X: pair (i, i) lies on the diagonal of the diagonal tiles
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-      const int jl = wc * 64 + n * 32 + (lane & 31);
-      const float nj = nq[jl];
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int il = wr * 64 + m * 32 + cd_row(r, lane);
-          const float d2 = fmaxf((-2.0f * acc[m][n][r] + nc[il]) + nj, 0.0f);   // x = the centre: the d2 its radius was taken from
-          const bool self = diag && il == jl;
-          const float c = self ? -1.0f : rc[il], k = self ? -1.0f : rk[il];
-          cov[n] |= (d2 <= c) ? 1 : 0;
-          const float dd = fmaxf(d2, FLT_MIN);
-          // IEEE division only where the quotient can pass the running maximum: fl(k / dd) > mx needs k > mx dd (1 - 2^-24)
-          if (k > 0.999f * mx[n] * dd) mx[n] = fmaxf(mx[n], fminf(k / dd, FLT_MAX));
-        }
-    }
-  }
-  const int p = wr * 2 + (lane >> 5);
-#pragma unroll
-  for (int n = 0; n < 2; ++n) {
-    pmax[p][wc * 64 + n * 32 + (lane & 31)] = mx[n];
-    pcov[p][wc * 64 + n * 32 + (lane & 31)] = cov[n];
-  }
-  __syncthreads();
-  if (t < MT && j0 + t < a.nq) {
-    const float m = fmaxf(fmaxf(pmax[0][t], pmax[1][t]), fmaxf(pmax[2][t], pmax[3][t]));
-    const int c = pcov[0][t] | pcov[1][t] | pcov[2][t] | pcov[3][t];
-    a.part_max[(int64_t)s * a.nq + j0 + t] = m;
-    a.part_cov[(int64_t)s * a.nq + j0 + t] = (uint8_t)c;
-  }
+__global__ __launch_bounds__(NT, 2) void ball_cover_partial_kernel(CoverArgs a) {
+  CoverOp op{a};
+  query_walk(Walk{a.q, a.ldq, a.nq, a.nrm_q, a.x, a.ldx, a.nx, a.nrm_x, a.d, a.tiles_x, a.splits}, op);   // rows: centres
 }
 
 __global__ __launch_bounds__(256) void ball_cover_merge_kernel(const float* __restrict__ part_max, const uint8_t* __restrict__ part_cov,
@@ -241,28 +176,17 @@ int smd_knn_radii(const float* x, int64_t ld, int n, int d, int k, void* workspa
   SMD_ARG_CHECK(ld >= d, "smd_knn_radii: row stride ld=%lld must be >= d=%d", (long long)ld, d);
   SMD_ARG_CHECK(al4(x) && al4(r2) && al8(workspace), "smd_knn_radii: x, r2 must be 4-byte and workspace 8-byte aligned");
   const int64_t tiles = tiles_of(n), splits = splits_of(n);
-  // HIP bounds a launch by gridDim.x * blockDim.x < 2^32 work-items: 2^24 - 1 workgroups of NT = 256 (n ~ 2.1 M)
-  SMD_ARG_CHECK(tiles * splits * NT < ((int64_t)1 << 32), "smd_knn_radii: %lld tiles x %lld column splits exceed one launch (at most %lld workgroups)",
-                (long long)tiles, (long long)splits, (long long)((((int64_t)1 << 32) - 1) / NT));
+  SMD_ARG_CHECK(fits_one_launch(tiles * splits), "smd_knn_radii: %lld tiles x %lld column splits exceed one launch (at most %lld workgroups)",
+                (long long)tiles, (long long)splits, (long long)MAX_WORKGROUPS);      // reached at n ~ 2.1 M
   const int64_t need = smd_knn_radii_workspace_bytes(n, k);
   SMD_ARG_CHECK(workspace_bytes >= need, "smd_knn_radii: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* nrm = reinterpret_cast<float*>(workspace);
-  row_norms_kernel<<<(n + 255) / 256, 256, 0, st>>>(x, n, d, ld, nrm);
-  SMD_LAUNCH_CHECK();
+  float* nrm = ws_at<float>(workspace, 0);
+  if (const int e = launch_row_norms(x, n, ld, nrm, nullptr, 0, 0, nullptr, d, st)) return e;
   KnnArgs a;
   a.x = x; a.ld = ld; a.n = n; a.d = d; a.tiles = (int)tiles; a.splits = (int)splits; a.nrm = nrm;
-  a.part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + up8((int64_t)n * 4));
-  switch (k) {
-    case 1: return knn_launch<1>(a, r2, st);
-    case 2: return knn_launch<2>(a, r2, st);
-    case 3: return knn_launch<3>(a, r2, st);
-    case 4: return knn_launch<4>(a, r2, st);
-    case 5: return knn_launch<5>(a, r2, st);
-    case 6: return knn_launch<6>(a, r2, st);
-    case 7: return knn_launch<7>(a, r2, st);
-    default: return knn_launch<8>(a, r2, st);
-  }
+  a.part = ws_at<float>(workspace, up8((int64_t)n * 4));
+  return dispatch_k(k, [&](auto K) { return knn_launch<decltype(K)::value>(a, r2, st); });
 }
 
 int64_t smd_ball_cover_workspace_bytes(int nq, int nx) {
@@ -280,19 +204,16 @@ int smd_ball_cover(const float* q, int64_t ldq, int nq, const float* x, int64_t 
   SMD_ARG_CHECK(al4(q) && al4(x) && al4(r2) && al4(realism2) && al8(workspace),
                 "smd_ball_cover: q, x, r2, realism2 must be 4-byte and workspace 8-byte aligned");
   const int64_t tiles_q = tiles_of(nq), tiles_x = tiles_of(nx), splits = splits_of(nx);
-  SMD_ARG_CHECK(tiles_q * splits * NT < ((int64_t)1 << 32), "smd_ball_cover: %lld query tiles x %lld centre splits exceed one launch (at most %lld workgroups)",
-                (long long)tiles_q, (long long)splits, (long long)((((int64_t)1 << 32) - 1) / NT));
+  SMD_ARG_CHECK(fits_one_launch(tiles_q * splits), "smd_ball_cover: %lld query tiles x %lld centre splits exceed one launch (at most %lld workgroups)",
+                (long long)tiles_q, (long long)splits, (long long)MAX_WORKGROUPS);
   const int64_t need = smd_ball_cover_workspace_bytes(nq, nx);
   SMD_ARG_CHECK(workspace_bytes >= need, "smd_ball_cover: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* nrm_q = reinterpret_cast<float*>(workspace);
+  float* nrm_q = ws_at<float>(workspace, 0);
   float* nrm_x = nrm_q + nq;
-  float* part_max = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + up8(((int64_t)nq + nx) * 4));
+  float* part_max = ws_at<float>(workspace, up8(((int64_t)nq + nx) * 4));
   uint8_t* part_cov = reinterpret_cast<uint8_t*>(part_max + splits * nq);
-  row_norms_kernel<<<(nq + 255) / 256, 256, 0, st>>>(q, nq, d, ldq, nrm_q);
-  SMD_LAUNCH_CHECK();
-  row_norms_kernel<<<(nx + 255) / 256, 256, 0, st>>>(x, nx, d, ldx, nrm_x);
-  SMD_LAUNCH_CHECK();
+  if (const int e = launch_row_norms(q, nq, ldq, nrm_q, x, nx, ldx, nrm_x, d, st)) return e;
   CoverArgs a;
   a.q = q; a.x = x; a.ldq = ldq; a.ldx = ldx; a.nq = nq; a.nx = nx; a.d = d; a.exclude_diagonal = exclude_diagonal ? 1 : 0;
   a.tiles_x = (int)tiles_x; a.splits = (int)splits; a.nrm_q = nrm_q; a.nrm_x = nrm_x; a.r2 = r2; a.keep = keep;

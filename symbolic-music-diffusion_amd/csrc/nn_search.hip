@@ -2,10 +2,10 @@
 // smallest (d2, global index) in lexicographic order, distances and indices both; the nq x nx distance matrix is never written.
 // It is what --copy_metrics asks: which training row is a sample closest to, and is it closer than held-out data is.
 //
-// Orientation and distance are those of nn_metrics.hip: queries are the COLUMNS of the accumulator tile, a lane owns two queries
-// and keeps one sorted k-list of (d2, index) PAIRS for each; candidates run over the accumulator rows in chunks of CHUNK tiles
-// per workgroup.  d2 = (-2 <q, x> + |q|^2) + |x|^2 clamped at 0, the query owning the expression; the bits of a pair's d2 depend
-// on the two rows alone (one fmaf chain in k order per product and per norm), not on the tile the pair falls into.
+// It follows the query-column walk of gram_walk.h (orientation, chunking, the four-partial fold and the slots are described there)
+// with one sorted k-list of (d2, index) PAIRS per query.  d2 = (-2 <q, x> + |q|^2) + |x|^2 clamped at 0, the query owning the
+// expression as in knn_radii; the bits of a pair's d2 depend on the two rows alone (one fmaf chain in k order per product and
+// per norm), not on the tile the pair falls into.
 //
 // Order: (d2, index) pairs are compared as pairs EVERYWHERE -- in a lane's insertion, between the four partial lists of a query
 // column, between the column splits and against the previous result of an accumulating call.  Candidate indices are distinct, so
@@ -19,34 +19,11 @@
 #include <float.h>
 #include <math.h>
 
-#include "gram_tile.h"
-#include "../../include/smd_hip.h"
+#include "gram_walk.h"
 
 namespace {
 
-constexpr int CHUNK = 16;          // candidate tiles per workgroup (2048 rows)
 constexpr int KMAX = SMD_KNN_MAX_K;
-
-inline int64_t tiles_of(int n) { return ((int64_t)n + MT - 1) / MT; }
-inline int64_t splits_of(int n) { return (tiles_of(n) + CHUNK - 1) / CHUNK; }
-
-template <typename I>
-__device__ __forceinline__ bool pair_less(float a, I ia, float b, I ib) { return a < b || (a == b && ia < ib); }
-
-// sorted ascending pairs (l, li)[0..K): put (v, i) in if it is below the largest
-template <int K, typename I>
-__device__ __forceinline__ void pair_insert(float (&l)[K], I (&li)[K], float v, I i) {
-  if (pair_less(v, i, l[K - 1], li[K - 1])) {
-#pragma unroll
-    for (int t = 0; t < K; ++t) {
-      const bool c = pair_less(v, i, l[t], li[t]);
-      const float lo = c ? v : l[t], hi = c ? l[t] : v;
-      const I ilo = c ? i : li[t], ihi = c ? li[t] : i;
-      l[t] = lo; li[t] = ilo;
-      v = hi; i = ihi;
-    }
-  }
-}
 
 struct SearchArgs {
   const float* q; const float* x; int64_t ldq, ldx;
@@ -58,8 +35,13 @@ struct SearchArgs {
   int32_t* part_idx;      // [splits][nq][K], indices into this call's x
 };
 
+// query_walk() of gram_walk.h written out, with (d2, index) pair lists: as an operation of the shared walk this kernel computes the
+// same bits, but the compiler then schedules the MFMA stage loop with one LDS address register instead of two (the two reads of a
+// k step no longer issue back to back) and the search measures 1 - 5 % slower at d >= 146.  Until that is
+// understood, a change to the walk is made here as well.
 template <int K>
 __global__ __launch_bounds__(NT, 2) void nn_search_partial_kernel(SearchArgs a) {
+  using Pair = DistIdx<int32_t>;
   __shared__ float As[BK * LDP];
   __shared__ float Bs[BK * LDP];
   __shared__ float nc[MT], nq[MT];
@@ -71,16 +53,12 @@ __global__ __launch_bounds__(NT, 2) void nn_search_partial_kernel(SearchArgs a) 
   const int j0 = qb * MT;
   const int c_end = min(a.tiles_x, (s + 1) * CHUNK);
   if (t < MT) nq[t] = (j0 + t < a.nq) ? a.nrm_q[j0 + t] : 0.0f;
-  float best[2][K];
-  int32_t bidx[2][K];
+  Pair best[2][K];
   int32_t self[2];        // the candidate that IS the query (by index), -1 when there is none in x
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
 #pragma unroll
-    for (int e = 0; e < K; ++e) {
-      best[n][e] = INFINITY;
-      bidx[n][e] = -1;
-    }
+    for (int e = 0; e < K; ++e) best[n][e] = Pair{INFINITY, -1};
     const int64_t si = (int64_t)(j0 + wc * 64 + n * 32 + (lane & 31)) + a.self_shift;
     self[n] = (a.exclude_self && si >= 0 && si < a.nx) ? (int32_t)si : -1;
   }
@@ -90,10 +68,7 @@ __global__ __launch_bounds__(NT, 2) void nn_search_partial_kernel(SearchArgs a) 
     const int i0 = cb * MT;
     __syncthreads();                                          // the previous tile's epilogue has read nc
     if (t >= MT) nc[t - MT] = (i0 + t - MT < a.nx) ? a.nrm_x[i0 + t - MT] : 0.0f;
-    // The query tile is the same for every candidate tile, and the compiler would keep its eight row addresses and their masks
-    // in registers next to the lists for the whole walk (9 VGPRs spilled at K = 8).  An opaque copy of j0 has them formed per
-    // tile instead, where the loader's registers are free anyway.
-    int jq = j0;
+    int jq = j0;                                              // opaque: see query_walk()
     asm volatile("" : "+s"(jq));
     gram_tile(a.x, a.ldx, a.nx, i0, a.q, a.ldq, a.nq, jq, a.d, As, Bs, acc);   // rows: candidates, columns: queries
 #pragma unroll
@@ -104,9 +79,9 @@ __global__ __launch_bounds__(NT, 2) void nn_search_partial_kernel(SearchArgs a) 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int il = wr * 64 + m * 32 + cd_row(r, lane), i = i0 + il;
-          float d2 = fmaxf((-2.0f * acc[m][n][r] + nj) + nc[il], 0.0f);
+          float d2 = d2_of(acc[m][n][r], nj, nc[il]);
           if (i >= a.nx || i == self[n]) d2 = INFINITY;       // padding, and self by index: a duplicate of the query still counts
-          pair_insert<K, int32_t>(best[n], bidx[n], d2, i);
+          list_insert<K>(best[n], Pair{d2, i});
         }
     }
   }
@@ -116,27 +91,23 @@ __global__ __launch_bounds__(NT, 2) void nn_search_partial_kernel(SearchArgs a) 
   for (int n = 0; n < 2; ++n)
 #pragma unroll
     for (int e = 0; e < K; ++e) {
-      lists[p][e][wc * 64 + n * 32 + (lane & 31)] = best[n][e];
-      ilists[p][e][wc * 64 + n * 32 + (lane & 31)] = bidx[n][e];
+      lists[p][e][wc * 64 + n * 32 + (lane & 31)] = best[n][e].d2;
+      ilists[p][e][wc * 64 + n * 32 + (lane & 31)] = best[n][e].i;
     }
   __syncthreads();
   if (t < MT && j0 + t < a.nq) {
-    float l[K];
-    int32_t li[K];
+    Pair l[K];
 #pragma unroll
-    for (int e = 0; e < K; ++e) {
-      l[e] = lists[0][e][t];
-      li[e] = ilists[0][e][t];
-    }
+    for (int e = 0; e < K; ++e) l[e] = Pair{lists[0][e][t], ilists[0][e][t]};
 #pragma unroll
     for (int q = 1; q < 4; ++q)
 #pragma unroll
-      for (int e = 0; e < K; ++e) pair_insert<K, int32_t>(l, li, lists[q][e][t], ilists[q][e][t]);
+      for (int e = 0; e < K; ++e) list_insert<K>(l, Pair{lists[q][e][t], ilists[q][e][t]});
     const int64_t o = ((int64_t)s * a.nq + j0 + t) * K;
 #pragma unroll
     for (int e = 0; e < K; ++e) {
-      a.part_d2[o + e] = l[e];
-      a.part_idx[o + e] = li[e];
+      a.part_d2[o + e] = l[e].d2;
+      a.part_idx[o + e] = l[e].i;
     }
   }
 }
@@ -146,27 +117,24 @@ template <int K>
 __global__ __launch_bounds__(256) void nn_search_merge_kernel(const float* __restrict__ part_d2, const int32_t* __restrict__ part_idx,
                                                               int nq, int splits, int64_t x_base, int accumulate,
                                                               float* __restrict__ d2_out, int64_t* __restrict__ idx_out) {
+  using Pair = DistIdx<int64_t>;
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= nq) return;
-  float l[K];
-  int64_t li[K];
+  Pair l[K];
 #pragma unroll
-  for (int e = 0; e < K; ++e) {
-    l[e] = accumulate ? d2_out[(int64_t)j * K + e] : INFINITY;
-    li[e] = accumulate ? idx_out[(int64_t)j * K + e] : -1;
-  }
+  for (int e = 0; e < K; ++e) l[e] = accumulate ? Pair{d2_out[(int64_t)j * K + e], idx_out[(int64_t)j * K + e]} : Pair{INFINITY, -1};
   for (int s = 0; s < splits; ++s) {
     const int64_t o = ((int64_t)s * nq + j) * K;
 #pragma unroll
     for (int e = 0; e < K; ++e) {
       const int32_t i = part_idx[o + e];
-      pair_insert<K, int64_t>(l, li, part_d2[o + e], i < 0 ? (int64_t)-1 : x_base + i);
+      list_insert<K>(l, Pair{part_d2[o + e], i < 0 ? (int64_t)-1 : x_base + i});
     }
   }
 #pragma unroll
   for (int e = 0; e < K; ++e) {
-    d2_out[(int64_t)j * K + e] = l[e];
-    idx_out[(int64_t)j * K + e] = li[e];
+    d2_out[(int64_t)j * K + e] = l[e].d2;
+    idx_out[(int64_t)j * K + e] = l[e].i;
   }
 }
 
@@ -202,34 +170,21 @@ int smd_nn_search(const float* q, int64_t ldq, int nq, int64_t q_base, const flo
   SMD_ARG_CHECK(al4(q) && al4(x) && al4(d2_out) && al8(idx_out) && al8(workspace),
                 "smd_nn_search: q, x, d2_out must be 4-byte and idx_out, workspace 8-byte aligned");
   const int64_t tiles_q = tiles_of(nq), tiles_x = tiles_of(nx), splits = splits_of(nx);
-  // HIP bounds a launch by gridDim.x * blockDim.x < 2^32 work-items: 2^24 - 1 workgroups of NT = 256
-  SMD_ARG_CHECK(tiles_q * splits * NT < ((int64_t)1 << 32), "smd_nn_search: %lld query tiles x %lld candidate splits exceed one launch (at most %lld workgroups)",
-                (long long)tiles_q, (long long)splits, (long long)((((int64_t)1 << 32) - 1) / NT));
+  SMD_ARG_CHECK(fits_one_launch(tiles_q * splits), "smd_nn_search: %lld query tiles x %lld candidate splits exceed one launch (at most %lld workgroups)",
+                (long long)tiles_q, (long long)splits, (long long)MAX_WORKGROUPS);
   const int64_t need = smd_nn_search_workspace_bytes(nq, nx, k);
   SMD_ARG_CHECK(workspace_bytes >= need, "smd_nn_search: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* nrm_q = reinterpret_cast<float*>(workspace);
+  float* nrm_q = ws_at<float>(workspace, 0);
   float* nrm_x = nrm_q + nq;
-  row_norms_kernel<<<(nq + 255) / 256, 256, 0, st>>>(q, nq, d, ldq, nrm_q);
-  SMD_LAUNCH_CHECK();
-  row_norms_kernel<<<(nx + 255) / 256, 256, 0, st>>>(x, nx, d, ldx, nrm_x);
-  SMD_LAUNCH_CHECK();
+  if (const int e = launch_row_norms(q, nq, ldq, nrm_q, x, nx, ldx, nrm_x, d, st)) return e;
   SearchArgs a;
   a.q = q; a.x = x; a.ldq = ldq; a.ldx = ldx; a.nq = nq; a.nx = nx; a.d = d; a.tiles_x = (int)tiles_x; a.splits = (int)splits;
   a.self_shift = q_base - x_base; a.exclude_self = exclude_self ? 1 : 0; a.nrm_q = nrm_q; a.nrm_x = nrm_x;
-  a.part_d2 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + up8(((int64_t)nq + nx) * 4));
+  a.part_d2 = ws_at<float>(workspace, up8(((int64_t)nq + nx) * 4));
   a.part_idx = reinterpret_cast<int32_t*>(a.part_d2 + splits * nq * k);
   const int acc = accumulate ? 1 : 0;
-  switch (k) {
-    case 1: return search_launch<1>(a, x_base, acc, d2_out, idx_out, st);
-    case 2: return search_launch<2>(a, x_base, acc, d2_out, idx_out, st);
-    case 3: return search_launch<3>(a, x_base, acc, d2_out, idx_out, st);
-    case 4: return search_launch<4>(a, x_base, acc, d2_out, idx_out, st);
-    case 5: return search_launch<5>(a, x_base, acc, d2_out, idx_out, st);
-    case 6: return search_launch<6>(a, x_base, acc, d2_out, idx_out, st);
-    case 7: return search_launch<7>(a, x_base, acc, d2_out, idx_out, st);
-    default: return search_launch<8>(a, x_base, acc, d2_out, idx_out, st);
-  }
+  return dispatch_k(k, [&](auto K) { return search_launch<decltype(K)::value>(a, x_base, acc, d2_out, idx_out, st); });
 }
 
 }  // extern "C"

@@ -62,6 +62,12 @@ def _rows(t: torch.Tensor) -> torch.Tensor:
     return t if ok else t.contiguous()
 
 
+def _workspace(nbytes: int, device):
+    """(scratch tensor, nbytes) for one library call.  A size the library refuses (negative) still gets a buffer: the call
+    itself then reports what is wrong with the arguments."""
+    return torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device), nbytes
+
+
 def _degree(degree) -> int:
     if int(degree) != degree:
         raise ValueError(f"degree={degree!r}: the polynomial kernel takes an integer degree")
@@ -85,8 +91,7 @@ def pair_kernel_sums(x: torch.Tensor, y: Optional[torch.Tensor] = None, gamma_rb
     ny, dy = (nx, d) if sym else y.shape
     if dy != d:
         raise ValueError(f"pair_kernel_sums: d mismatch ({d} vs {dy})")
-    ws_bytes = L.smd_pair_kernel_sums_workspace_bytes(nx, ny, int(sym))
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace(L.smd_pair_kernel_sums_workspace_bytes(nx, ny, int(sym)), x.device)
     out = torch.empty(2, dtype=torch.float64, device=x.device)
     _lib.check(L.smd_pair_kernel_sums(x.data_ptr(), x.stride(0), nx, None if sym else y.data_ptr(), x.stride(0) if sym else y.stride(0),
                                       ny, d, int(sym), float(gamma_rbf), float(gamma_poly), float(coef0), _degree(degree),
@@ -110,8 +115,7 @@ def knn_radii(x: torch.Tensor, k: int = 3) -> torch.Tensor:
         raise ValueError(f"k={k!r}: knn_radii takes an integer k")
     x = _rows(x)
     n, d = x.shape
-    ws_bytes = L.smd_knn_radii_workspace_bytes(n, int(k))
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace(L.smd_knn_radii_workspace_bytes(n, int(k)), x.device)
     r2 = torch.empty(n, dtype=torch.float32, device=x.device)
     _lib.check(L.smd_knn_radii(x.data_ptr(), x.stride(0), n, d, int(k), ws.data_ptr(), ws_bytes, r2.data_ptr(), _stream(x.device)),
                "smd_knn_radii")
@@ -137,8 +141,7 @@ def ball_cover(q: torch.Tensor, x: torch.Tensor, r2: torch.Tensor, keep: Optiona
         if keep.shape != (nx,) or keep.device != x.device:
             raise ValueError(f"ball_cover: keep must be a mask of {nx} centres on their device")
         keep = (keep != 0).to(torch.uint8).contiguous()
-    ws_bytes = L.smd_ball_cover_workspace_bytes(nq, nx)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace(L.smd_ball_cover_workspace_bytes(nq, nx), x.device)
     covered = torch.empty(nq, dtype=torch.uint8, device=x.device)
     realism2 = torch.empty(nq, dtype=torch.float32, device=x.device)
     _lib.check(L.smd_ball_cover(q.data_ptr(), q.stride(0), nq, x.data_ptr(), x.stride(0), nx, d, r2.data_ptr(),
@@ -182,8 +185,7 @@ def _kmeans_assign(x: torch.Tensor, centres: torch.Tensor, prev_labels: Optional
                                     or not prev_labels.is_contiguous()):
         raise ValueError(f"kmeans_assign: prev_labels must be a contiguous int32 tensor of {n} labels on the rows' device")
     labels = torch.empty(n, dtype=torch.int32, device=x.device) if prev_labels is None else prev_labels
-    ws_bytes = L.smd_kmeans_assign_workspace_bytes(n, k)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace(L.smd_kmeans_assign_workspace_bytes(n, k), x.device)
     min_d2 = torch.empty(n, dtype=torch.float32, device=x.device)
     out = torch.empty(2, dtype=torch.int64, device=x.device)          # [inertia as fp64 bits, changed]
     _lib.check(L.smd_kmeans_assign(x.data_ptr(), x.stride(0), n, d, centres.data_ptr(), k, int(prev_labels is not None), ws.data_ptr(),
@@ -214,8 +216,7 @@ def kmeans_update(x: torch.Tensor, labels: torch.Tensor, centres: torch.Tensor) 
     if labels.shape != (n,) or labels.dtype != torch.int32 or labels.device != x.device:
         raise ValueError(f"kmeans_update: labels must be an int32 tensor of {n} labels on the rows' device")
     labels = labels.contiguous()
-    ws_bytes = L.smd_kmeans_update_workspace_bytes(n, d, k)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace(L.smd_kmeans_update_workspace_bytes(n, d, k), x.device)
     new = torch.empty_like(centres)
     counts = torch.empty(k, dtype=torch.int64, device=x.device)
     _lib.check(L.smd_kmeans_update(x.data_ptr(), x.stride(0), n, d, labels.data_ptr(), centres.data_ptr(), k, ws.data_ptr(), ws_bytes,
@@ -293,8 +294,7 @@ def moments(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         raise ValueError("moments takes an fp32 (n, d) cuda tensor")
     x = _rows(x)
     n, d = x.shape
-    ws_bytes = L.smd_moments_workspace_bytes(n, d)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=x.device)
+    ws, ws_bytes = _workspace(L.smd_moments_workspace_bytes(n, d), x.device)
     mean = torch.empty(d, dtype=torch.float64, device=x.device)
     cov = torch.empty(d, d, dtype=torch.float64, device=x.device)
     _lib.check(L.smd_moments(x.data_ptr(), x.stride(0), n, d, ws.data_ptr(), ws_bytes, mean.data_ptr(), cov.data_ptr(),
@@ -619,8 +619,7 @@ def nn_search(q: torch.Tensor, x: torch.Tensor, k: int = 1, *, q_base: int = 0, 
         for t, dt in ((d2, torch.float32), (idx, torch.int64)):
             if tuple(t.shape) != (nq, k) or t.dtype != dt or t.device != q.device or not t.is_contiguous():
                 raise ValueError(f"nn_search: out must be contiguous (d2 fp32, idx int64) tensors of shape ({nq}, {k}) on the queries' device")
-    ws_bytes = L.smd_nn_search_workspace_bytes(nq, nx, k)
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=q.device)
+    ws, ws_bytes = _workspace(L.smd_nn_search_workspace_bytes(nq, nx, k), q.device)
     _lib.check(L.smd_nn_search(q.data_ptr(), q.stride(0), nq, int(q_base), x.data_ptr(), x.stride(0), nx, int(x_base), d, k,
                                int(bool(exclude_self)), int(out is not None), ws.data_ptr(), ws_bytes, d2.data_ptr(), idx.data_ptr(),
                                _stream(q.device)), "smd_nn_search")

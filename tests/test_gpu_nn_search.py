@@ -161,6 +161,26 @@ def test_slabs_of_the_set_against_itself_with_exclude_self():
     assert int(plain[1][4099, 0]) == 17                 # the duplicate's lower index wins the tie
 
 
+@pytest.mark.parametrize("n,d,k", [(9, 1, 8), (129, 5, 3), (4100, 42, 8)])
+def test_knn_radii_are_the_bits_of_the_searchs_kth_distance(n, d, k):
+    """knn_radii and nn_search follow one walk (csrc/gram_walk.h) with one distance expression (d2_of), the query owning it, so the k-th
+    distance of the search of a set in itself is the radius bit for bit: a consistency condition between two entry points, both
+    the code under test, no tolerance.  200 rows (3 at n = 9) are overwritten one after the other with copies of other rows
+    (at n = 129 a row can be hit more than once), so exact zeros and tied distances occur."""
+    import smd_amd.metrics as M
+    torch.manual_seed(n)
+    x = (0.25 * torch.randn(n, d)).clamp(-1, 1)
+    copies = 3 if n == 9 else 200
+    dst, off = torch.randint(n, (copies,)), torch.randint(1, n, (copies,))
+    for a, b in zip(dst.tolist(), ((dst + off) % n).tolist()):        # b != a
+        x[a] = x[b]
+    xt = x.cuda()
+    r2 = M.knn_radii(xt, k)
+    d2, idx = M.nn_search(xt, xt, k, exclude_self=True)
+    assert bool((idx >= 0).all()) and bool((d2[:, 0] == 0).any())
+    assert torch.equal(r2.view(torch.int32), d2[:, k - 1].contiguous().view(torch.int32))
+
+
 def test_footprint_padding_and_repeatability(dev):
     """only d2_out, idx_out and the workspace are written; NaN in the ld > d padding changes nothing; two calls, the same bits"""
     import smd_amd.lib as lib
