@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libsmd_hip.so")
 SOURCES = ["tuning.hip", "gemm_nt.hip", "gemm_nt256.hip", "gemm_tn.hip", "gemm_tn256.hip", "norm.hip", "ln128.hip", "attention.hip", "encoder_fused.hip", "diffusion.hip", "bound.hip", "rng_jax.hip", "optim.hip",
            "metrics.hip", "nn_metrics.hip", "nn_search.hip", "kmeans.hip", "gemm_f32.hip", "net_f32.hip", "engine.hip", "capi.hip"]
-HEADERS = ["smd_common.h", "smd_kernels.h", "gemm_plan.h", "gemm_tile.h", "gram_tile.h", "gram_walk.h", "f32_kernels.h", "gemm_epilogue.h", "engine.h", "rng.h", "rng_threefry.h",
+HEADERS = ["smd_common.h", "smd_kernels.h", "gemm_plan.h", "gemm_tile.h", "gram_tile.h", "gram_walk.h", "step_walk.h", "f32_kernels.h", "gemm_epilogue.h", "engine.h", "rng.h", "rng_threefry.h",
            os.path.join("..", "..", "include", "smd_hip.h"), os.path.join("..", "..", "include", "smd_hip_lab.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result"]

@@ -6,25 +6,9 @@
 // The work split is reverse_step_kernel's (diffusion.hip): one workgroup per sample, 128 column threads x RG row groups,
 // VEC = 4 columns per thread when C % 4 == 0.  The timestep is read from device memory and the walk's next timestep comes
 // from a table, so one captured (noise, eps-net forward, terms) iteration replays for a whole walk.
-#include "smd_kernels.h"
-#include "rng.h"
+#include "step_walk.h"
 
 namespace {
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
 
 // ------------------------------------------------------------------ forward noising of an example
 template <int VEC, int RG>
@@ -47,9 +31,7 @@ __global__ __launch_bounds__(128 * RG) void bound_noise_kernel(BoundNoiseArgs a)
       float x0[VEC], ep[VEC], xt[VEC];
       ldv<VEC>(a.x0 + idx, x0);
       if (a.draw) {                        // Philox keyed by (seed, global sample index, t) on the bound's own stream
-        const float4 n4 = philox_normal4((uint32_t)(e >> 2), bglob, SMD_STREAM_BOUND, (uint32_t)t, key_lo, key_hi);
-        if constexpr (VEC == 4) { ep[0] = n4.x; ep[1] = n4.y; ep[2] = n4.z; ep[3] = n4.w; }
-        else ep[0] = pick4(n4, e & 3);
+        philox_normals<VEC>(ep, e, bglob, SMD_STREAM_BOUND, (uint32_t)t, key_lo, key_hi);
         stv<VEC>(a.eps + idx, ep);
       } else {
         ldv<VEC>(a.eps + idx, ep);
@@ -57,17 +39,7 @@ __global__ __launch_bounds__(128 * RG) void bound_noise_kernel(BoundNoiseArgs a)
 #pragma unroll
       for (int v = 0; v < VEC; ++v) xt[v] = __builtin_fmaf(sqrt_1m, ep[v], sqrt_ap * x0[v]);
       stv<VEC>(a.x_t + idx, xt);
-      if (a.xt_bf16) {
-        bf16_t* xb = a.xt_bf16 + ((size_t)b * a.S + s) * a.Cp + col0;
-        if constexpr (VEC == 4) {
-          bf16x4_t p;
-#pragma unroll
-          for (int v = 0; v < 4; ++v) p[v] = f2bf(xt[v]);
-          *reinterpret_cast<bf16x4_t*>(xb) = p;
-        } else {
-          xb[0] = f2bf(xt[0]);
-        }
-      }
+      if (a.xt_bf16) stv_bf16<VEC>(a.xt_bf16 + ((size_t)b * a.S + s) * a.Cp + col0, xt);
     }
   }
 }
@@ -83,7 +55,6 @@ __global__ __launch_bounds__(128 * RG) void bound_noise_kernel(BoundNoiseArgs a)
 template <int VEC, int RG>
 __global__ __launch_bounds__(128 * RG) void bound_terms_kernel(BoundTermsArgs a) {
   __shared__ float part[RG][3][128];
-  __shared__ float red[2][3];
   const int t = *a.t_ptr;
   if (t < 0 || t >= a.T) return;          // a no-op that advances nothing
   const float4 row = *reinterpret_cast<const float4*>(a.table + (size_t)t * 4);
@@ -132,23 +103,11 @@ __global__ __launch_bounds__(128 * RG) void bound_terms_kernel(BoundTermsArgs a)
       for (int g2 = 1; g2 < RG; ++g2) { sq += part[g2][0][ct]; se += part[g2][1][ct]; sn += part[g2][2][ct]; }
     }
   }
-  sq = wave_sum(sq); se = wave_sum(se); sn = wave_sum(sn);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0 && w < 2) { red[w][0] = sq; red[w][1] = se; red[w][2] = sn; }
-  __syncthreads();
-  if (threadIdx.x < 3) a.partial[((size_t)t * a.B + b) * 3 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x];
-  // *t_ptr = next_t[t] by the LAST workgroup to get here (every workgroup read t at its top, before its own arrival);
-  // `arrive` is zero between launches, as in reverse_step_kernel
-  if (a.next_t && threadIdx.x == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(a.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == gridDim.x - 1) {
-      __hip_atomic_exchange(a.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.t_ptr, a.next_t[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  const float sum = column_waves_sum3(sq, se, sn);
+  if (threadIdx.x < 3) a.partial[((size_t)t * a.B + b) * 3 + threadIdx.x] = sum;
+  if (a.next_t && threadIdx.x == 0 && last_arriver(a.arrive))
+    __hip_atomic_store(a.t_ptr, a.next_t[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-
-inline bool al16(uintptr_t p) { return (p & 15) == 0; }
 
 }  // namespace
 
@@ -161,13 +120,7 @@ int launch_bound_noise(const BoundNoiseArgs& a, hipStream_t st) {
   if (vec)
     SMD_ARG_CHECK(al16((uintptr_t)a.x0 | (uintptr_t)a.eps | (uintptr_t)a.x_t) && ((uintptr_t)a.xt_bf16 & 7) == 0,
                   "bound_noise: C=%d takes 16-byte loads: x0, eps, x_t must be 16-byte and the bf16 copy 8-byte aligned", a.C);
-  if (a.S >= 4) {
-    if (vec) hipLaunchKernelGGL((bound_noise_kernel<4, 4>), dim3(a.B), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((bound_noise_kernel<1, 4>), dim3(a.B), dim3(512), 0, st, a);
-  } else {
-    if (vec) hipLaunchKernelGGL((bound_noise_kernel<4, 1>), dim3(a.B), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL((bound_noise_kernel<1, 1>), dim3(a.B), dim3(128), 0, st, a);
-  }
+  SMD_LAUNCH_VEC_RG(bound_noise_kernel, vec, a, st);
   SMD_LAUNCH_CHECK();
   return 0;
 }
@@ -183,13 +136,7 @@ int launch_bound_terms(const BoundTermsArgs& a, hipStream_t st) {
   if (vec)
     SMD_ARG_CHECK(al16((uintptr_t)a.x0 | (uintptr_t)a.eps | (uintptr_t)a.eps_hat),
                   "bound_terms: C=%d takes 16-byte loads: x0, eps, eps_hat must be 16-byte aligned", a.C);
-  if (a.S >= 4) {
-    if (vec) hipLaunchKernelGGL((bound_terms_kernel<4, 4>), dim3(a.B), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((bound_terms_kernel<1, 4>), dim3(a.B), dim3(512), 0, st, a);
-  } else {
-    if (vec) hipLaunchKernelGGL((bound_terms_kernel<4, 1>), dim3(a.B), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL((bound_terms_kernel<1, 1>), dim3(a.B), dim3(128), 0, st, a);
-  }
+  SMD_LAUNCH_VEC_RG(bound_terms_kernel, vec, a, st);
   SMD_LAUNCH_CHECK();
   return 0;
 }

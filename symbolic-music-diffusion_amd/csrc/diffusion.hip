@@ -9,9 +9,9 @@
 //
 // All per-step scalars (timestep t, optimiser step) are read from device memory so the whole
 // step is hipGraph-replayable with frozen kernel arguments.
-#include "smd_kernels.h"
-#include "rng_threefry.h"
-#include "rng.h"
+#include <type_traits>
+
+#include "step_walk.h"
 
 namespace {
 
@@ -166,25 +166,6 @@ __global__ __launch_bounds__(256) void q_sample_quads_kernel(QSampleArgs a) {
   if (blockIdx.x == 0 && threadIdx.x == 0) a.s_out[b] = a.dsm ? sb : sa;
 }
 
-template <int VEC> struct VecT;
-template <> struct VecT<4> { typedef float4 type; };
-template <> struct VecT<1> { typedef float type; };
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = *p;
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else *p = v[0];
-}
-
 // ------------------------------------------------------------------ loss + gradient wrt pred
 // one workgroup of 1024 threads per sample; VEC = 4: 16-byte loads / 8-byte bf16 stores (C and Cp multiples of 4)
 template <int VEC>
@@ -208,21 +189,14 @@ __global__ __launch_bounds__(1024) void mse_loss_grad_kernel(const float* __rest
     ldv<VEC>(pred + (size_t)b * SC + e, p);
     ldv<VEC>(eps + (size_t)b * SC + e, q);
     const int srow = e / C, c = e - srow * C;
-    bf16_t* dst = dpred + ((size_t)b * S + srow) * Cp + c;
-    if constexpr (VEC == 4) {
-      bf16x4_t o;
+    float g[VEC];
 #pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const float d = sg * p[v] - qs * q[v];
-        acc += d * d;
-        o[v] = f2bf(d * gscale);
-      }
-      *reinterpret_cast<bf16x4_t*>(dst) = o;
-    } else {
-      const float d = sg * p[0] - qs * q[0];
+    for (int v = 0; v < VEC; ++v) {
+      const float d = sg * p[v] - qs * q[v];
       acc += d * d;
-      dst[0] = f2bf(d * gscale);
+      g[v] = d * gscale;
     }
+    stv_bf16<VEC>(dpred + ((size_t)b * S + srow) * Cp + c, g);
   }
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
@@ -240,7 +214,6 @@ __global__ __launch_bounds__(1024) void mse_loss_grad_kernel(const float* __rest
 // in flight instead of one; the per-column sums over the sequence axis are combined through LDS in a fixed order).
 template <int VEC, int RG>
 __global__ __launch_bounds__(128 * RG) void reverse_step_kernel(ReverseStepArgs a) {
-  __shared__ float red[2][3];
   __shared__ float part[RG > 1 ? RG : 1][3][128 * VEC];
   const int b = blockIdx.x;
   const int ct = threadIdx.x & 127, rg = threadIdx.x >> 7;
@@ -279,10 +252,7 @@ __global__ __launch_bounds__(128 * RG) void reverse_step_kernel(ReverseStepArgs 
 #pragma unroll
           for (int v = 0; v < VEC; ++v) z[v] = jax_normal_from_bits(jax_bits_at(tf_nk, tf_base + e + v, (uint64_t)a.tf_n_total));
         } else {
-          const float4 n4 = philox_normal4((uint32_t)(e >> 2), bglob, SMD_STREAM_Z, (uint32_t)t,
-                                           key_lo, key_hi);
-          if constexpr (VEC == 4) { z[0] = n4.x; z[1] = n4.y; z[2] = n4.z; z[3] = n4.w; }
-          else z[0] = pick4(n4, e & 3);
+          philox_normals<VEC>(z, e, bglob, SMD_STREAM_Z, (uint32_t)t, key_lo, key_hi);
         }
 #pragma unroll
         for (int v = 0; v < VEC; ++v) z[v] *= sigma;
@@ -307,10 +277,7 @@ __global__ __launch_bounds__(128 * RG) void reverse_step_kernel(ReverseStepArgs 
 #pragma unroll
             for (int v = 0; v < VEC; ++v) iz[v] = jax_normal_from_bits(jax_bits_at(tf_ik, tf_base + e + v, (uint64_t)a.tf_n_total));
           } else {
-            const float4 n4 = philox_normal4((uint32_t)(e >> 2), bglob, SMD_STREAM_INFILL, (uint32_t)t,
-                                             key_lo, key_hi);
-            if constexpr (VEC == 4) { iz[0] = n4.x; iz[1] = n4.y; iz[2] = n4.z; iz[3] = n4.w; }
-            else iz[0] = pick4(n4, e & 3);
+            philox_normals<VEC>(iz, e, bglob, SMD_STREAM_INFILL, (uint32_t)t, key_lo, key_hi);
           }
         }
 #pragma unroll
@@ -328,17 +295,7 @@ __global__ __launch_bounds__(128 * RG) void reverse_step_kernel(ReverseStepArgs 
       }
       stv<VEC>(a.x + idx, nx);
       if (slot >= 0) stv<VEC>(a.collection + ((size_t)slot * a.B) * a.S * a.C + idx, nx);
-      if (a.x_bf16) {
-        bf16_t* xb = a.x_bf16 + ((size_t)b * a.S + s) * a.Cp + col0;
-        if constexpr (VEC == 4) {
-          bf16x4_t p;
-#pragma unroll
-          for (int v = 0; v < 4; ++v) p[v] = f2bf(nx[v]);
-          *reinterpret_cast<bf16x4_t*>(xb) = p;
-        } else {
-          xb[0] = f2bf(nx[0]);
-        }
-      }
+      if (a.x_bf16) stv_bf16<VEC>(a.x_bf16 + ((size_t)b * a.S + s) * a.Cp + col0, nx);
     }
     if constexpr (RG > 1) {
       __syncthreads();
@@ -365,35 +322,19 @@ __global__ __launch_bounds__(128 * RG) void reverse_step_kernel(ReverseStepArgs 
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
       if (a.S > 1) {
-        m_eps += sqrtf(acc_e[v] + 1e-10f);
-        m_step += sqrtf(acc_s[v] + 1e-10f);
-        m_z += sqrtf(acc_z[v] + 1e-10f);
+        m_eps += norm_of(acc_e[v]);
+        m_step += norm_of(acc_s[v]);
+        m_z += norm_of(acc_z[v]);
       } else {
         m_eps += acc_e[v]; m_step += acc_s[v]; m_z += acc_z[v];
       }
     }
   }
-  if (a.metrics_partial) {
-    m_eps = wave_sum(m_eps); m_step = wave_sum(m_step); m_z = wave_sum(m_z);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0 && w < 2) { red[w][0] = m_eps; red[w][1] = m_step; red[w][2] = m_z; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-      float v = red[0][threadIdx.x] + red[1][threadIdx.x];
-      if (a.S == 1) v = sqrtf(v + 1e-10f);
-      a.metrics_partial[((size_t)t * a.B + b) * 3 + threadIdx.x] = v;
-    }
-  }
+  if (a.metrics_partial) store_metrics(a.metrics_partial, t, a.B, b, a.S, m_eps, m_step, m_z);
   // *t_advance = t - 1 by the LAST workgroup to get here (every workgroup read t at its top, i.e. before its own
   // arrival): the timestep decrement of the captured sampling step without a launch of its own.  `arrive` is zero
   // between launches (the last arriver resets it with a device-scope atomic).
-  if (a.t_advance && threadIdx.x == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(a.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == gridDim.x - 1) {
-      __hip_atomic_exchange(a.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.t_advance, t - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (a.t_advance && threadIdx.x == 0) last_arriver_store(a.arrive, a.t_advance, t - 1);
 }
 
 // ------------------------------------------------------------------ strided (DDIM) step
@@ -405,7 +346,6 @@ __global__ __launch_bounds__(128 * RG) void reverse_step_kernel(ReverseStepArgs 
 // sigma == 0: z is neither read nor drawn.  A timestep that is not on the walk (iteration < 0) is a no-op like t outside [0, T).
 template <int VEC, int RG>
 __global__ __launch_bounds__(128 * RG) void strided_step_kernel(StridedStepArgs a) {
-  __shared__ float red[2][3];
   __shared__ float part[RG > 1 ? RG : 1][3][128 * VEC];
   const int b = blockIdx.x;
   const int ct = threadIdx.x & 127, rg = threadIdx.x >> 7;
@@ -426,8 +366,8 @@ __global__ __launch_bounds__(128 * RG) void strided_step_kernel(StridedStepArgs 
   const uint64_t tf_base = (uint64_t)bglob * a.S * a.C;       // this sample's first element in the global jax array
   const uint32_t key_lo = a.key_ptr ? a.key_ptr[0] : a.key.seed_lo, key_hi = a.key_ptr ? a.key_ptr[1] : a.key.seed_hi;
   TfKey tf_nk{0, 0}, tf_ik{0, 0};
-  if (a.tf_noise_keys) { tf_nk.k0 = a.tf_noise_keys[2 * iter]; tf_nk.k1 = a.tf_noise_keys[2 * iter + 1]; }
-  if (a.tf_infill_keys) { tf_ik.k0 = a.tf_infill_keys[2 * iter]; tf_ik.k1 = a.tf_infill_keys[2 * iter + 1]; }
+  tf_nk = tf_key_row(a.tf_noise_keys, iter);
+  tf_ik = tf_key_row(a.tf_infill_keys, iter);
   float m_eps = 0.f, m_step = 0.f, m_z = 0.f;
   for (int cb0 = 0; cb0 < a.C; cb0 += 128 * VEC) {          // uniform trip count: the LDS combine below has barriers
     const int col0 = cb0 + ct * VEC;
@@ -448,9 +388,7 @@ __global__ __launch_bounds__(128 * RG) void strided_step_kernel(StridedStepArgs 
 #pragma unroll
           for (int v = 0; v < VEC; ++v) z[v] = jax_normal_from_bits(jax_bits_at(tf_nk, tf_base + e + v, (uint64_t)a.tf_n_total));
         } else {
-          const float4 n4 = philox_normal4((uint32_t)(e >> 2), bglob, SMD_STREAM_Z, (uint32_t)t, key_lo, key_hi);
-          if constexpr (VEC == 4) { z[0] = n4.x; z[1] = n4.y; z[2] = n4.z; z[3] = n4.w; }
-          else z[0] = pick4(n4, e & 3);
+          philox_normals<VEC>(z, e, bglob, SMD_STREAM_Z, (uint32_t)t, key_lo, key_hi);
         }
 #pragma unroll
         for (int v = 0; v < VEC; ++v) z[v] *= sigma;
@@ -479,9 +417,7 @@ __global__ __launch_bounds__(128 * RG) void strided_step_kernel(StridedStepArgs 
 #pragma unroll
             for (int v = 0; v < VEC; ++v) iz[v] = jax_normal_from_bits(jax_bits_at(tf_ik, tf_base + e + v, (uint64_t)a.tf_n_total));
           } else {
-            const float4 n4 = philox_normal4((uint32_t)(e >> 2), bglob, SMD_STREAM_INFILL, (uint32_t)t, key_lo, key_hi);
-            if constexpr (VEC == 4) { iz[0] = n4.x; iz[1] = n4.y; iz[2] = n4.z; iz[3] = n4.w; }
-            else iz[0] = pick4(n4, e & 3);
+            philox_normals<VEC>(iz, e, bglob, SMD_STREAM_INFILL, (uint32_t)t, key_lo, key_hi);
           }
         }
 #pragma unroll
@@ -500,17 +436,7 @@ __global__ __launch_bounds__(128 * RG) void strided_step_kernel(StridedStepArgs 
       }
       stv<VEC>(a.x + idx, nx);
       if (slot >= 0) stv<VEC>(a.collection + ((size_t)slot * a.B) * a.S * a.C + idx, nx);
-      if (a.x_bf16) {
-        bf16_t* xb = a.x_bf16 + ((size_t)b * a.S + s) * a.Cp + col0;
-        if constexpr (VEC == 4) {
-          bf16x4_t pk;
-#pragma unroll
-          for (int v = 0; v < 4; ++v) pk[v] = f2bf(nx[v]);
-          *reinterpret_cast<bf16x4_t*>(xb) = pk;
-        } else {
-          xb[0] = f2bf(nx[0]);
-        }
-      }
+      if (a.x_bf16) stv_bf16<VEC>(a.x_bf16 + ((size_t)b * a.S + s) * a.Cp + col0, nx);
     }
     if constexpr (RG > 1) {
       __syncthreads();
@@ -536,34 +462,18 @@ __global__ __launch_bounds__(128 * RG) void strided_step_kernel(StridedStepArgs 
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
       if (a.S > 1) {
-        m_eps += sqrtf(acc_e[v] + 1e-10f);
-        m_step += sqrtf(acc_s[v] + 1e-10f);
-        m_z += sqrtf(acc_z[v] + 1e-10f);
+        m_eps += norm_of(acc_e[v]);
+        m_step += norm_of(acc_s[v]);
+        m_z += norm_of(acc_z[v]);
       } else {
         m_eps += acc_e[v]; m_step += acc_s[v]; m_z += acc_z[v];
       }
     }
   }
-  if (a.metrics_partial) {
-    m_eps = wave_sum(m_eps); m_step = wave_sum(m_step); m_z = wave_sum(m_z);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0 && w < 2) { red[w][0] = m_eps; red[w][1] = m_step; red[w][2] = m_z; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-      float v = red[0][threadIdx.x] + red[1][threadIdx.x];
-      if (a.S == 1) v = sqrtf(v + 1e-10f);
-      a.metrics_partial[((size_t)t * a.B + b) * 3 + threadIdx.x] = v;
-    }
-  }
+  if (a.metrics_partial) store_metrics(a.metrics_partial, t, a.B, b, a.S, m_eps, m_step, m_z);
   // *t_advance = plan[t].next_t by the LAST workgroup to get here (every workgroup read t at its top, before its own
   // arrival); `arrive` is zero between launches, as in reverse_step_kernel
-  if (a.t_advance && threadIdx.x == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(a.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == gridDim.x - 1) {
-      __hip_atomic_exchange(a.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.t_advance, next_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (a.t_advance && threadIdx.x == 0) last_arriver_store(a.arrive, a.t_advance, next_t);
 }
 
 // ------------------------------------------------------------------ multistep (DPM-Solver++(2M)) step
@@ -574,10 +484,9 @@ __global__ __launch_bounds__(128 * RG) void strided_step_kernel(StridedStepArgs 
 //   x0_prev = x0 (the value just used, before the infill blend).
 // Deterministic: there is no noise term, and the z-norm metric is the norm of zeros, as the strided step's at sigma = 0.
 // a1 == 0 (the first and the last iteration, every iteration at order 1): x0_prev is not read, so whatever an earlier walk
-// left there cannot reach the state.  The shared lines are repeated as in strided_step_kernel (follow-up).
+// left there cannot reach the state.  The row loop is repeated as in strided_step_kernel, on the helpers of step_walk.h ("Shared helpers").
 template <int VEC, int RG>
 __global__ __launch_bounds__(128 * RG) void multistep_step_kernel(MultistepStepArgs a) {
-  __shared__ float red[2][3];
   __shared__ float part[RG > 1 ? RG : 1][2][128 * VEC];
   const int b = blockIdx.x;
   const int ct = threadIdx.x & 127, rg = threadIdx.x >> 7;
@@ -598,7 +507,7 @@ __global__ __launch_bounds__(128 * RG) void multistep_step_kernel(MultistepStepA
   const uint64_t tf_base = (uint64_t)bglob * a.S * a.C;       // this sample's first element in the global jax array
   const uint32_t key_lo = a.key_ptr ? a.key_ptr[0] : a.key.seed_lo, key_hi = a.key_ptr ? a.key_ptr[1] : a.key.seed_hi;
   TfKey tf_ik{0, 0};
-  if (a.tf_infill_keys) { tf_ik.k0 = a.tf_infill_keys[2 * iter]; tf_ik.k1 = a.tf_infill_keys[2 * iter + 1]; }
+  tf_ik = tf_key_row(a.tf_infill_keys, iter);
   float m_eps = 0.f, m_step = 0.f, m_z = 0.f;
   for (int cb0 = 0; cb0 < a.C; cb0 += 128 * VEC) {          // uniform trip count: the LDS combine below has barriers
     const int col0 = cb0 + ct * VEC;
@@ -639,9 +548,7 @@ __global__ __launch_bounds__(128 * RG) void multistep_step_kernel(MultistepStepA
 #pragma unroll
             for (int v = 0; v < VEC; ++v) iz[v] = jax_normal_from_bits(jax_bits_at(tf_ik, tf_base + e + v, (uint64_t)a.tf_n_total));
           } else {
-            const float4 n4 = philox_normal4((uint32_t)(e >> 2), bglob, SMD_STREAM_INFILL, (uint32_t)t, key_lo, key_hi);
-            if constexpr (VEC == 4) { iz[0] = n4.x; iz[1] = n4.y; iz[2] = n4.z; iz[3] = n4.w; }
-            else iz[0] = pick4(n4, e & 3);
+            philox_normals<VEC>(iz, e, bglob, SMD_STREAM_INFILL, (uint32_t)t, key_lo, key_hi);
           }
         }
 #pragma unroll
@@ -660,17 +567,7 @@ __global__ __launch_bounds__(128 * RG) void multistep_step_kernel(MultistepStepA
       stv<VEC>(a.x + idx, nx);
       stv<VEC>(a.x0_prev + idx, x0);                              // the next iteration's history: this thread's own elements
       if (slot >= 0) stv<VEC>(a.collection + ((size_t)slot * a.B) * a.S * a.C + idx, nx);
-      if (a.x_bf16) {
-        bf16_t* xb = a.x_bf16 + ((size_t)b * a.S + s) * a.Cp + col0;
-        if constexpr (VEC == 4) {
-          bf16x4_t pk;
-#pragma unroll
-          for (int v = 0; v < 4; ++v) pk[v] = f2bf(nx[v]);
-          *reinterpret_cast<bf16x4_t*>(xb) = pk;
-        } else {
-          xb[0] = f2bf(nx[0]);
-        }
-      }
+      if (a.x_bf16) stv_bf16<VEC>(a.x_bf16 + ((size_t)b * a.S + s) * a.Cp + col0, nx);
     }
     if constexpr (RG > 1) {
       __syncthreads();
@@ -697,33 +594,17 @@ __global__ __launch_bounds__(128 * RG) void multistep_step_kernel(MultistepStepA
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
       if (a.S > 1) {
-        m_eps += sqrtf(acc_e[v] + 1e-10f);
-        m_step += sqrtf(acc_s[v] + 1e-10f);
-        m_z += sqrtf(1e-10f);
+        m_eps += norm_of(acc_e[v]);
+        m_step += norm_of(acc_s[v]);
+        m_z += norm_of(0.f);
       } else {
         m_eps += acc_e[v]; m_step += acc_s[v];
       }
     }
   }
-  if (a.metrics_partial) {
-    m_eps = wave_sum(m_eps); m_step = wave_sum(m_step); m_z = wave_sum(m_z);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0 && w < 2) { red[w][0] = m_eps; red[w][1] = m_step; red[w][2] = m_z; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-      float v = red[0][threadIdx.x] + red[1][threadIdx.x];
-      if (a.S == 1) v = sqrtf(v + 1e-10f);
-      a.metrics_partial[((size_t)t * a.B + b) * 3 + threadIdx.x] = v;
-    }
-  }
+  if (a.metrics_partial) store_metrics(a.metrics_partial, t, a.B, b, a.S, m_eps, m_step, m_z);
   // *t_advance = plan[t].next_t by the LAST workgroup to get here, as in strided_step_kernel
-  if (a.t_advance && threadIdx.x == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(a.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == gridDim.x - 1) {
-      __hip_atomic_exchange(a.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.t_advance, next_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (a.t_advance && threadIdx.x == 0) last_arriver_store(a.arrive, a.t_advance, next_t);
 }
 
 __global__ void advance_t_kernel(int* t_ptr) { *t_ptr -= 1; }
@@ -788,7 +669,7 @@ __global__ __launch_bounds__(256) void langevin_step_kernel(LangevinStepArgs a) 
       a.x[idx] = nx;
       if (a.collect_out) a.collect_out[idx] = nx;
     }
-    if (a.S > 1) { m_g += sqrtf(acc_g + 1e-10f); m_s += sqrtf(acc_s + 1e-10f); m_z += sqrtf(acc_z + 1e-10f); }
+    if (a.S > 1) { m_g += norm_of(acc_g); m_s += norm_of(acc_s); m_z += norm_of(acc_z); }
     else { m_g += acc_g; m_s += acc_s; m_z += acc_z; }
   }
   if (a.metrics_partial) {
@@ -798,7 +679,7 @@ __global__ __launch_bounds__(256) void langevin_step_kernel(LangevinStepArgs a) 
     __syncthreads();
     if (threadIdx.x < 3) {
       float v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-      if (a.S == 1) v = sqrtf(v + 1e-10f);
+      if (a.S == 1) v = norm_of(v);
       a.metrics_partial[(size_t)b * 3 + threadIdx.x] = v;
     }
   }
@@ -903,87 +784,63 @@ int launch_mse_loss_grad(const float* pred, const float* eps, int B, int S, int 
   return 0;
 }
 
-int launch_reverse_step(const ReverseStepArgs& a, hipStream_t st, int* form_out) {
-  SMD_ARG_CHECK(a.x && a.eps_hat && a.coef && a.t_ptr, "reverse_step: null pointer");
-  SMD_ARG_CHECK(a.B > 0 && a.S > 0 && a.C > 0 && (!a.x_bf16 || a.Cp >= a.C), "reverse_step: bad shape");
-  SMD_ARG_CHECK((a.infill_masks != nullptr) == (a.infill_samples != nullptr), "reverse_step: infill needs samples and masks");
-  SMD_ARG_CHECK(!a.collection || a.slot_table, "reverse_step: collection needs slot_table");
-  SMD_ARG_CHECK(a.T > 0, "reverse_step: T=%d (number of timesteps: bounds the coefficient table)", a.T);
-  SMD_ARG_CHECK(!a.t_advance || a.arrive, "reverse_step: t_advance needs the arrival counter");
-  SMD_ARG_CHECK(!(a.tf_noise_keys || a.tf_infill_keys) || (a.tf_n_total >= (int64_t)(a.sample_offset + a.B) * a.S * a.C &&
-                                                            a.tf_n_total <= (1ll << 32)),
-                "reverse_step: tf_n_total=%lld must cover this rank's window and be <= 2^32", (long long)a.tf_n_total);
-  const bool vec = a.C % 4 == 0 && (!a.x_bf16 || a.Cp % 4 == 0);
-  if (vec) {
-    const uintptr_t f32 = (uintptr_t)a.x | (uintptr_t)a.eps_hat | (uintptr_t)a.z_in | (uintptr_t)a.infill_samples |
-                          (uintptr_t)a.infill_masks | (uintptr_t)a.infill_z_in | (uintptr_t)a.collection;
-    SMD_ARG_CHECK((f32 & 15) == 0 && ((uintptr_t)a.x_bf16 & 7) == 0,
-                  "reverse_step: C=%d takes 16-byte loads: state, eps_hat, draws, infill arrays and collection must be 16-byte aligned", a.C);
-  }
-  if (a.S >= 4) {
-    if (vec) hipLaunchKernelGGL((reverse_step_kernel<4, 4>), dim3(a.B), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((reverse_step_kernel<1, 4>), dim3(a.B), dim3(512), 0, st, a);
+namespace {
+// The argument checks of the three sampler steps, in the order their launchers have always made them.  `name` heads every
+// message; vec receives the vector path's choice.
+template <typename Args>
+int check_step_args(const Args& a, const char* name, bool& vec) {
+  constexpr bool reverse = std::is_same<Args, ReverseStepArgs>::value, multistep = std::is_same<Args, MultistepStepArgs>::value;
+  bool plan = true, threefry = a.tf_infill_keys != nullptr;
+  uintptr_t f32 = (uintptr_t)a.x | (uintptr_t)a.eps_hat | (uintptr_t)a.infill_samples | (uintptr_t)a.infill_masks |
+                  (uintptr_t)a.infill_z_in | (uintptr_t)a.collection;
+  if constexpr (!reverse) plan = a.plan != nullptr;
+  if constexpr (multistep) {
+    f32 |= (uintptr_t)a.x0_prev;
   } else {
-    if (vec) hipLaunchKernelGGL((reverse_step_kernel<4, 1>), dim3(a.B), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL((reverse_step_kernel<1, 1>), dim3(a.B), dim3(128), 0, st, a);
+    f32 |= (uintptr_t)a.z_in;
+    threefry = threefry || a.tf_noise_keys;
   }
+  SMD_ARG_CHECK(a.x && a.eps_hat && a.coef && plan && a.t_ptr, "%s: null pointer", name);
+  if constexpr (multistep)
+    SMD_ARG_CHECK(a.x0_prev, "%s: null history (x0_prev: one float32 array of the state's shape per chain)", name);
+  SMD_ARG_CHECK(a.B > 0 && a.S > 0 && a.C > 0 && (!a.x_bf16 || a.Cp >= a.C), "%s: bad shape", name);
+  SMD_ARG_CHECK((a.infill_masks != nullptr) == (a.infill_samples != nullptr), "%s: infill needs samples and masks", name);
+  if constexpr (reverse) SMD_ARG_CHECK(!a.collection || a.slot_table, "%s: collection needs slot_table", name);
+  SMD_ARG_CHECK(a.T > 0, "%s: T=%d (number of timesteps: bounds the coefficient table%s)", name, a.T, reverse ? "" : " and the plan");
+  SMD_ARG_CHECK(!a.t_advance || a.arrive, "%s: t_advance needs the arrival counter", name);
+  if constexpr (!reverse) SMD_ARG_CHECK(al16((uintptr_t)a.plan), "%s: the plan rows are read as 16-byte vectors", name);
+  SMD_ARG_CHECK(!threefry || (a.tf_n_total >= (int64_t)(a.sample_offset + a.B) * a.S * a.C && a.tf_n_total <= (1ll << 32)),
+                "%s: tf_n_total=%lld must cover this rank's window and be <= 2^32", name, (long long)a.tf_n_total);
+  vec = a.C % 4 == 0 && (!a.x_bf16 || a.Cp % 4 == 0);
+  if (vec)
+    SMD_ARG_CHECK(al16(f32) && ((uintptr_t)a.x_bf16 & 7) == 0,
+                  "%s: C=%d takes 16-byte loads: state, %seps_hat, %sinfill arrays and collection must be 16-byte aligned", name, a.C,
+                  multistep ? "history, " : "", multistep ? "" : "draws, ");
+  return 0;
+}
+}  // namespace
+
+int launch_reverse_step(const ReverseStepArgs& a, hipStream_t st, int* form_out) {
+  bool vec;
+  if (const int rc = check_step_args(a, "reverse_step", vec)) return rc;
+  SMD_LAUNCH_VEC_RG(reverse_step_kernel, vec, a, st);
   SMD_LAUNCH_CHECK();
   if (form_out) { form_out[0] = vec ? 4 : 1; form_out[1] = a.S >= 4 ? 4 : 1; }
   return 0;
 }
 
 int launch_strided_step(const StridedStepArgs& a, hipStream_t st) {
-  SMD_ARG_CHECK(a.x && a.eps_hat && a.coef && a.plan && a.t_ptr, "strided_step: null pointer");
-  SMD_ARG_CHECK(a.B > 0 && a.S > 0 && a.C > 0 && (!a.x_bf16 || a.Cp >= a.C), "strided_step: bad shape");
-  SMD_ARG_CHECK((a.infill_masks != nullptr) == (a.infill_samples != nullptr), "strided_step: infill needs samples and masks");
-  SMD_ARG_CHECK(a.T > 0, "strided_step: T=%d (number of timesteps: bounds the coefficient table and the plan)", a.T);
-  SMD_ARG_CHECK(!a.t_advance || a.arrive, "strided_step: t_advance needs the arrival counter");
-  SMD_ARG_CHECK(((uintptr_t)a.plan & 15) == 0, "strided_step: the plan rows are read as 16-byte vectors");
-  SMD_ARG_CHECK(!(a.tf_noise_keys || a.tf_infill_keys) || (a.tf_n_total >= (int64_t)(a.sample_offset + a.B) * a.S * a.C &&
-                                                            a.tf_n_total <= (1ll << 32)),
-                "strided_step: tf_n_total=%lld must cover this rank's window and be <= 2^32", (long long)a.tf_n_total);
-  const bool vec = a.C % 4 == 0 && (!a.x_bf16 || a.Cp % 4 == 0);
-  if (vec) {
-    const uintptr_t f32 = (uintptr_t)a.x | (uintptr_t)a.eps_hat | (uintptr_t)a.z_in | (uintptr_t)a.infill_samples |
-                          (uintptr_t)a.infill_masks | (uintptr_t)a.infill_z_in | (uintptr_t)a.collection;
-    SMD_ARG_CHECK((f32 & 15) == 0 && ((uintptr_t)a.x_bf16 & 7) == 0,
-                  "strided_step: C=%d takes 16-byte loads: state, eps_hat, draws, infill arrays and collection must be 16-byte aligned", a.C);
-  }
-  if (a.S >= 4) {
-    if (vec) hipLaunchKernelGGL((strided_step_kernel<4, 4>), dim3(a.B), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((strided_step_kernel<1, 4>), dim3(a.B), dim3(512), 0, st, a);
-  } else {
-    if (vec) hipLaunchKernelGGL((strided_step_kernel<4, 1>), dim3(a.B), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL((strided_step_kernel<1, 1>), dim3(a.B), dim3(128), 0, st, a);
-  }
+  bool vec;
+  if (const int rc = check_step_args(a, "strided_step", vec)) return rc;
+  SMD_LAUNCH_VEC_RG(strided_step_kernel, vec, a, st);
   SMD_LAUNCH_CHECK();
   return 0;
 }
 
 int launch_multistep_step(const MultistepStepArgs& a, hipStream_t st) {
-  SMD_ARG_CHECK(a.x && a.eps_hat && a.coef && a.plan && a.t_ptr, "multistep_step: null pointer");
-  SMD_ARG_CHECK(a.x0_prev, "multistep_step: null history (x0_prev: one float32 array of the state's shape per chain)");
-  SMD_ARG_CHECK(a.B > 0 && a.S > 0 && a.C > 0 && (!a.x_bf16 || a.Cp >= a.C), "multistep_step: bad shape");
-  SMD_ARG_CHECK((a.infill_masks != nullptr) == (a.infill_samples != nullptr), "multistep_step: infill needs samples and masks");
-  SMD_ARG_CHECK(a.T > 0, "multistep_step: T=%d (number of timesteps: bounds the coefficient table and the plan)", a.T);
-  SMD_ARG_CHECK(!a.t_advance || a.arrive, "multistep_step: t_advance needs the arrival counter");
-  SMD_ARG_CHECK(((uintptr_t)a.plan & 15) == 0, "multistep_step: the plan rows are read as 16-byte vectors");
-  SMD_ARG_CHECK(!a.tf_infill_keys || (a.tf_n_total >= (int64_t)(a.sample_offset + a.B) * a.S * a.C && a.tf_n_total <= (1ll << 32)),
-                "multistep_step: tf_n_total=%lld must cover this rank's window and be <= 2^32", (long long)a.tf_n_total);
-  const bool vec = a.C % 4 == 0 && (!a.x_bf16 || a.Cp % 4 == 0);
-  if (vec) {
-    const uintptr_t f32 = (uintptr_t)a.x | (uintptr_t)a.eps_hat | (uintptr_t)a.x0_prev | (uintptr_t)a.infill_samples |
-                          (uintptr_t)a.infill_masks | (uintptr_t)a.infill_z_in | (uintptr_t)a.collection;
-    SMD_ARG_CHECK((f32 & 15) == 0 && ((uintptr_t)a.x_bf16 & 7) == 0,
-                  "multistep_step: C=%d takes 16-byte loads: state, history, eps_hat, infill arrays and collection must be 16-byte aligned", a.C);
-  }
-  if (a.S >= 4) {
-    if (vec) hipLaunchKernelGGL((multistep_step_kernel<4, 4>), dim3(a.B), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((multistep_step_kernel<1, 4>), dim3(a.B), dim3(512), 0, st, a);
-  } else {
-    if (vec) hipLaunchKernelGGL((multistep_step_kernel<4, 1>), dim3(a.B), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL((multistep_step_kernel<1, 1>), dim3(a.B), dim3(128), 0, st, a);
-  }
+  bool vec;
+  if (const int rc = check_step_args(a, "multistep_step", vec)) return rc;
+  SMD_LAUNCH_VEC_RG(multistep_step_kernel, vec, a, st);
   SMD_LAUNCH_CHECK();
   return 0;
 }

@@ -64,7 +64,10 @@ def partials64(v, S):
     return sq.sum(dim=1) if S > 1 else sq
 
 
-@pytest.mark.parametrize("arch,B,C", [("transformer", 3, 42), ("transformer", 3, 512), ("dense", 5, 512)])
+# the last three rows: VEC = 1 with one row group; two trips of the column loop, the last with 18 live threads (VEC = 1) and
+# with one live thread (VEC = 4)
+@pytest.mark.parametrize("arch,B,C", [("transformer", 3, 42), ("transformer", 3, 512), ("dense", 5, 512),
+                                      ("dense", 5, 42), ("transformer", 3, 146), ("dense", 3, 1028)])
 def test_fused_update_alone_against_float64(arch, B, C):
     """One launch at a time on random x, z, masks: the network's own eps_hat is read back and the update is recomputed in
     float64 from the float32 tables the kernel read.  C = 42: VEC = 1 and a masked last column block; C = 512: VEC = 4;
