@@ -147,6 +147,14 @@ int smd_engine_backward_from(smd_engine* e, const float* dpred, int stage, void*
  * a real uniform used_alpha in [alphas_prod[T], 1).  used_alphas ([B] device floats, or NULL) replaces the label -> alpha
  * lookup of the following smd_engine_loss_backward calls (parity mode: the reference's own jax.random.uniform draws). */
 int smd_engine_set_used_alphas(smd_engine* e, const float* used_alphas);
+/* Per-sample loss weights of the following smd_engine_loss_backward calls (DDPM objective only; no reference counterpart:
+ * min-SNR-gamma weighting of Hang et al. 2023 and the importance weights of a non-uniform timestep draw).  With ap = the
+ * squared noise level q-sample stored, w_b = iw_b min(1, min_snr_gamma (1 - ap) / ap) -- for eps-prediction min(SNR, gamma) / SNR
+ * -- and the gradient of the step is that of mean_b(w_b loss_b); smd_engine_loss_per_sample stays the UNWEIGHTED loss and
+ * smd_engine_weight_per_sample returns the w_b ([B] device floats, valid after a weighted call).  iw: [B] device floats or NULL
+ * (= 1); min_snr_gamma <= 0 or +inf: no SNR factor.  (NULL, 0), the state of a new handle, runs the unweighted kernel. */
+int smd_engine_set_loss_weights(smd_engine* e, const float* iw, float min_snr_gamma);
+const float* smd_engine_weight_per_sample(const smd_engine* e); /* [B] device pointer */
 const float* smd_engine_loss_per_sample(const smd_engine* e);   /* [B] device pointer */
 const float* smd_engine_pred(const smd_engine* e);              /* [B*S][C] device pointer */
 
@@ -482,6 +490,29 @@ int smd_mse_fwd_bwd(const float* pred, const float* eps, int B, int S, int C, in
                     float* loss_per_sample, smd_bf16* dpred_bf16, void* stream);
 int smd_adam_clip_ema(float* params, const float* grads, float* m, float* v, float* ema, int64_t n,
                       const smd_train_hyper* h, uint32_t* step_ptr, float* norm_partial, float* metrics_out, void* stream);
+/* Weighted training (no reference counterpart).
+ * smd_weighted_mse_fwd_bwd: smd_mse_fwd_bwd with a weight per sample, w_b = iw_b min(1, min_snr_gamma (1 - s_b^2) / s_b^2) with
+ *   s = noise_level [B] (what smd_q_sample stored); iw NULL = 1; min_snr_gamma <= 0 or +inf: no SNR factor (noise_level may then
+ *   be NULL); s = 1 gives w = 0, not a NaN.  dpred_bf16 = 2 w_b (pred - eps) * inv_global_count (columns >= C not written),
+ *   loss_per_sample [B] the UNWEIGHTED mean -- the bits smd_mse_fwd_bwd writes -- and weight_per_sample [B] = w_b.  Alignment as
+ *   for smd_mse_fwd_bwd.
+ * smd_timestep_draw: B timesteps from the table p [n] by its inclusive cdf [n]: labels_out[b] = label_base + (first i with
+ *   cdf[i] > u_b, the last index when there is none), iw_out[b] = 1 / (n p[i]) (the weight that keeps the objective unbiased).
+ *   u_b = u_in[b], or with u_in NULL 24 Philox bits in [0, 1) keyed by (seed, b + sample_offset, step) on a stream of their own;
+ *   step_ptr (device, NULL-able) replaces `step`, as in smd_q_sample.
+ * smd_timestep_update: the loss-second-moment resampler of Nichol & Dhariwal 2021.  history [n][10] and counts [n] are updated
+ *   in place with the Bg pairs (labels[j] - label_base, loss[j]) IN ORDER (a row fills front to back, a full row shifts left and
+ *   appends; labels outside the table are dropped); then, once every count is 10, p_out[i] = sqrt(mean_j history[i][j]^2)
+ *   normalised to sum 1, times (1 - uniform_mix), plus uniform_mix / n -- before that p_out = 1 / n -- cdf_out = its inclusive
+ *   prefix sums and *warmed_out = 1 / 0.  One workgroup, fixed summation order, no atomics: the same input gives the same bits. */
+int smd_weighted_mse_fwd_bwd(const float* pred, const float* eps, const float* noise_level, const float* iw, float min_snr_gamma,
+                             int B, int S, int C, int Cp, float inv_global_count, float* loss_per_sample,
+                             float* weight_per_sample, smd_bf16* dpred_bf16, void* stream);
+int smd_timestep_draw(const float* cdf, const float* p, int n, int label_base, int B, uint32_t seed_lo, uint32_t seed_hi,
+                      uint32_t sample_offset, uint32_t step, const uint32_t* step_ptr, const float* u_in, int32_t* labels_out,
+                      float* iw_out, void* stream);
+int smd_timestep_update(const int32_t* labels, const float* loss, int Bg, float* history, int32_t* counts, int n, int label_base,
+                        float uniform_mix, float* p_out, float* cdf_out, int32_t* warmed_out, void* stream);
 /* Philox4x32-10 normals: out[b][e], counter (e/4, b + sample_offset, stream_id, 0) */
 int smd_rng_normal(float* out, int B, int per_sample, uint32_t seed_lo, uint32_t seed_hi, uint32_t stream_id,
                    uint32_t sample_offset, void* stream);

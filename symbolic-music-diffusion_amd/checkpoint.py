@@ -26,6 +26,9 @@ from . import flax_io
 from .train_utils import EarlyStopping
 
 
+SAMPLER_PREFIX = "timestep_sampler/"
+
+
 def _named(engine, flat: torch.Tensor, prefix: str) -> Dict[str, torch.Tensor]:
     return {f"{prefix}/{k}": v.detach().cpu().contiguous() for k, v in engine.named_views(flat).items()}
 
@@ -42,8 +45,12 @@ def _rotate(ckpt_dir: str, prefix: str, keep: int) -> None:
 
 
 def save_checkpoint(ckpt_dir: str, target, step: int, keep: int = 50, prefix: str = "checkpoint_",
-                    fmt: str = "safetensors", flax_naming: str = "shared", flax_attention_class: str = "MultiHeadDotProductAttention") -> str:
-    """target = (optimizer, ema, early_stop) like the reference call (train_ncsn.py:397-399)."""
+                    fmt: str = "safetensors", flax_naming: str = "shared", flax_attention_class: str = "MultiHeadDotProductAttention",
+                    timestep_sampler=None, train_options: Optional[Dict[str, object]] = None) -> str:
+    """target = (optimizer, ema, early_stop) like the reference call (train_ncsn.py:397-399).  ``timestep_sampler`` (a
+    trainer.TimestepSampler): its tables go into a safetensors checkpoint as ``timestep_sampler/<name>``; the flax layout has no
+    place for them and drops them.  ``train_options`` (e.g. loss_weighting, min_snr_gamma, timestep_sampler) ride in the
+    safetensors metadata as strings."""
     optimizer, ema, early_stop = target
     eng = optimizer.engine
     os.makedirs(ckpt_dir, exist_ok=True)
@@ -71,6 +78,9 @@ def save_checkpoint(ckpt_dir: str, target, step: int, keep: int = 50, prefix: st
             "ema_mu": str(getattr(ema, "mu", 0.0)), "format": "smd_amd-1",
             "trunk_dtype": str(getattr(eng, "trunk_dtype", "bf16")), "gemm_dtype": str(eng.cfg.dtype),
             "fp8_dgrad": str(int(getattr(eng, "fp8_dgrad", 1)) if eng.cfg.dtype == "fp8" else 0)}
+    if timestep_sampler is not None:
+        tensors.update({f"{SAMPLER_PREFIX}{k}": v.contiguous() for k, v in timestep_sampler.state_dict().items()})
+    meta.update({str(k): str(v) for k, v in (train_options or {}).items()})
     path = os.path.join(ckpt_dir, f"{prefix}{step}")
     save_file(tensors, path + ".tmp", metadata=meta)
     os.replace(path + ".tmp", path)
@@ -118,6 +128,20 @@ def restore_checkpoint(ckpt_dir: str, engine, load_optimizer_state: bool = True)
         meta = f.metadata() or {}
     es = json.loads(meta.get("early_stop", "{}"))
     return True, EarlyStopping(**es) if es else EarlyStopping()
+
+
+def restore_timestep_sampler(ckpt_dir: str, sampler) -> bool:
+    """Loads the timestep sampler's tables from the newest checkpoint; False when it holds none (a flax-format file, or a run
+    that trained with the uniform draw): the sampler then starts its warm-up again."""
+    path = ckpt_dir if os.path.isfile(ckpt_dir) else latest_checkpoint(ckpt_dir)
+    if path is None or flax_io.is_flax_file(path):
+        return False
+    tensors = load_file(path)
+    sd = {k[len(SAMPLER_PREFIX):]: v for k, v in tensors.items() if k.startswith(SAMPLER_PREFIX)}
+    if not sd:
+        return False
+    sampler.load_state_dict(sd)
+    return True
 
 
 def load_ema_params(ckpt_dir: str, engine) -> bool:

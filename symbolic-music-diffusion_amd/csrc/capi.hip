@@ -158,6 +158,13 @@ int smd_engine_set_used_alphas(smd_engine* e, const float* used_alphas) {
   e->impl.set_used_alphas(used_alphas);
   return 0;
 }
+int smd_engine_set_loss_weights(smd_engine* e, const float* iw, float min_snr_gamma) {
+  NEED(e);
+  SMD_ARG_CHECK(!(min_snr_gamma != min_snr_gamma), "smd_engine_set_loss_weights: min_snr_gamma is NaN");
+  e->impl.set_loss_weights(iw, min_snr_gamma);
+  return 0;
+}
+const float* smd_engine_weight_per_sample(const smd_engine* e) { return e ? e->impl.weight_per_sample() : nullptr; }
 int64_t smd_engine_debug_snapshot_bytes(const smd_engine* e) { return e ? e->impl.debug_snapshot_bytes() : -1; }
 int smd_engine_debug_snapshots(smd_engine* e, void* buf, int64_t bytes) {
   NEED(e);
@@ -645,6 +652,23 @@ int smd_q_sample_lab(const smd_q_sample_args* p, int32_t* form_out, void* stream
   return rc;
 }
 
+int smd_weighted_mse_fwd_bwd(const float* pred, const float* eps, const float* noise_level, const float* iw, float min_snr_gamma,
+                             int Bn, int Sn, int C, int Cp, float inv_global_count, float* loss_per_sample,
+                             float* weight_per_sample, smd_bf16* dpred_bf16, void* stream) {
+  return launch_weighted_mse_loss_grad(pred, eps, noise_level, iw, min_snr_gamma, Bn, Sn, C, Cp, inv_global_count, loss_per_sample,
+                                       weight_per_sample, B(dpred_bf16), S(stream));
+}
+int smd_timestep_draw(const float* cdf, const float* p, int n, int label_base, int Bn, uint32_t seed_lo, uint32_t seed_hi,
+                      uint32_t sample_offset, uint32_t step, const uint32_t* step_ptr, const float* u_in, int32_t* labels_out,
+                      float* iw_out, void* stream) {
+  return launch_timestep_draw(cdf, p, n, label_base, Bn, seed_lo, seed_hi, sample_offset, step, step_ptr, u_in, labels_out, iw_out,
+                              S(stream));
+}
+int smd_timestep_update(const int32_t* labels, const float* loss, int Bg, float* history, int32_t* counts, int n, int label_base,
+                        float uniform_mix, float* p_out, float* cdf_out, int32_t* warmed_out, void* stream) {
+  return launch_timestep_update(labels, loss, Bg, history, counts, n, label_base, uniform_mix, p_out, cdf_out, warmed_out,
+                                S(stream));
+}
 int smd_loss_grad_lab(const float* pred, const float* eps, int Bn, int Sn, int C, int Cp, float inv_global_count, float* loss_per_sample,
                       smd_bf16* dpred_bf16, const float* dsm_sigma, int32_t* form_out, void* stream) {
   SMD_ARG_CHECK(al4(pred) && al4(eps) && al4(loss_per_sample) && al4(dsm_sigma) && al2(dpred_bf16),

@@ -209,6 +209,58 @@ __global__ __launch_bounds__(1024) void mse_loss_grad_kernel(const float* __rest
   }
 }
 
+// The DDPM form of mse_loss_grad_kernel with a weight per sample: w_b = iw_b min(1, gamma (1 - ap) / ap),
+// ap = s_b^2 -- the min-SNR-gamma weight min(SNR, gamma) / SNR of an eps-prediction loss times the importance weight of a
+// non-uniform timestep draw.  dpred = 2 w_b d / (Bg S C); loss_per_sample stays the UNWEIGHTED mean of d^2, accumulated in the
+// order of mse_loss_grad_kernel (same walk, same reduction: the same bits), and weight_per_sample[b] = w_b.  With iw null and
+// no SNR factor w_b is exactly 1 and dpred has mse_loss_grad_kernel's bits too.
+// 1 - s^2 is formed as (1 - s)(1 + s): 1 - s is exact for s in [1/2, 2], so the factor keeps its relative precision where
+// ap -> 1 (the low-noise timesteps the weight is there for); ap = 1 gives w = 0, ap = 0 gives min(1, inf) = 1.
+__device__ __forceinline__ float loss_weight(float s, float iw, float gamma, bool snr) {
+  if (!snr) return iw;
+  const float ap = s * s, om = (1.0f - s) * (1.0f + s);
+  return iw * fminf(1.0f, (gamma * om) / ap);
+}
+template <int VEC>
+__global__ __launch_bounds__(1024) void weighted_mse_loss_grad_kernel(const float* __restrict__ pred,
+                                                                      const float* __restrict__ eps, int S, int C, int Cp,
+                                                                      float inv_global_count,
+                                                                      const float* __restrict__ noise_level,
+                                                                      const float* __restrict__ iw, float gamma, int snr,
+                                                                      float* __restrict__ loss_per_sample,
+                                                                      float* __restrict__ weight_per_sample,
+                                                                      bf16_t* __restrict__ dpred) {
+  __shared__ float red[16];
+  const int b = blockIdx.x, SC = S * C;
+  const float w = loss_weight(snr ? noise_level[b] : 1.0f, iw ? iw[b] : 1.0f, gamma, snr != 0);
+  const float gscale = (2.0f * inv_global_count) * w;
+  float acc = 0.f;
+  for (int e = threadIdx.x * VEC; e < SC; e += 1024 * VEC) {
+    float p[VEC], q[VEC];
+    ldv<VEC>(pred + (size_t)b * SC + e, p);
+    ldv<VEC>(eps + (size_t)b * SC + e, q);
+    const int srow = e / C, c = e - srow * C;
+    float g[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const float d = p[v] - q[v];
+      acc += d * d;
+      g[v] = d * gscale;
+    }
+    stv_bf16<VEC>(dpred + ((size_t)b * S + srow) * Cp + c, g);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t += red[i];
+    loss_per_sample[b] = t / (float)SC;
+    weight_per_sample[b] = w;
+  }
+}
+
 // ------------------------------------------------------------------ fused reverse step
 // One workgroup per sample: 128 column threads x RG row groups (RG = 4 for sequence states: four rows of every column
 // in flight instead of one; the per-column sums over the sequence axis are combined through LDS in a fixed order).
@@ -781,6 +833,26 @@ int launch_mse_loss_grad(const float* pred, const float* eps, int B, int S, int 
                        loss_per_sample, dpred_bf16, dsm_sigma);
   SMD_LAUNCH_CHECK();
   if (vec_out) *vec_out = vec ? 4 : 1;
+  return 0;
+}
+
+int launch_weighted_mse_loss_grad(const float* pred, const float* eps, const float* noise_level, const float* iw, float gamma,
+                                  int B, int S, int C, int Cp, float inv_global_count, float* loss_per_sample,
+                                  float* weight_per_sample, bf16_t* dpred_bf16, hipStream_t st) {
+  SMD_ARG_CHECK(pred && eps && loss_per_sample && weight_per_sample && dpred_bf16 && B > 0 && S > 0 && C > 0 && Cp >= C,
+                "weighted_mse_loss_grad: bad arguments");
+  const int snr = gamma > 0.0f && gamma < __builtin_inff();      // gamma <= 0, +inf (and NaN): no SNR factor
+  SMD_ARG_CHECK(!snr || noise_level, "weighted_mse_loss_grad: gamma=%g needs the per-sample noise levels", (double)gamma);
+  const bool vec = C % 4 == 0 && Cp % 4 == 0;
+  SMD_ARG_CHECK(!vec || ((((uintptr_t)pred | (uintptr_t)eps) & 15) == 0 && ((uintptr_t)dpred_bf16 & 7) == 0),
+                "weighted_mse_loss_grad: C=%d takes 16-byte loads: pred and eps must be 16-byte aligned (dpred 8-byte)", C);
+  if (vec)
+    hipLaunchKernelGGL(weighted_mse_loss_grad_kernel<4>, dim3(B), dim3(1024), 0, st, pred, eps, S, C, Cp, inv_global_count,
+                       noise_level, iw, gamma, snr, loss_per_sample, weight_per_sample, dpred_bf16);
+  else
+    hipLaunchKernelGGL(weighted_mse_loss_grad_kernel<1>, dim3(B), dim3(1024), 0, st, pred, eps, S, C, Cp, inv_global_count,
+                       noise_level, iw, gamma, snr, loss_per_sample, weight_per_sample, dpred_bf16);
+  SMD_LAUNCH_CHECK();
   return 0;
 }
 

@@ -183,6 +183,12 @@ class SmdEngine {
   // gradient are 0.5 sum (sigma score + eps)^2 and its batch mean's derivative.
   int loss_kind = 0;
   void set_used_alphas(const float* a) { used_alphas_ = a; }
+  // Per-sample loss weights of the NEXT loss_backward calls (DDPM objective only): iw (device, [B], may be
+  // null = 1) times the min-SNR-gamma factor min(1, gamma (1 - ap) / ap); gamma <= 0 or +inf: no such factor.  (null, 0), the
+  // default, launches mse_loss_grad_kernel as ever; anything else its weighted sibling, which also fills weight_per_sample().
+  void set_loss_weights(const float* iw, float gamma) { loss_iw_ = iw; min_snr_gamma_ = gamma; }
+  bool loss_weighted() const { return loss_iw_ != nullptr || min_snr_gamma_ > 0.0f; }
+  const float* weight_per_sample() const { return W.loss_weight; }
   // Debugging aid (tools/det_first_diff.py): when a buffer is set, backward_stem copies the state of the SHARED, per-layer
   // overwritten gradient buffers behind every encoder-layer kernel into it (per layer, in execution order: da2 partial
   // tiles after mlp_hs_bwd, dh after the ln2 backward, dA_E after attn_block_bwd, dh after the ln1 backward; plus the layer's
@@ -283,6 +289,8 @@ class SmdEngine {
   float *grads_ = nullptr, *m_ = nullptr, *v_ = nullptr, *ema_ = nullptr, *metrics_ = nullptr;
   uint32_t* step_ptr_ = nullptr;
   const float* used_alphas_ = nullptr;
+  const float* loss_iw_ = nullptr;
+  float min_snr_gamma_ = 0.0f;
   char* dbg_snap_ = nullptr;
   const float* coef_ = nullptr;
   const float* sqrt_ap_ = nullptr;
@@ -371,6 +379,7 @@ class SmdEngine {
     float *f_a = nullptr, *f_qkv = nullptr, *f_o = nullptr, *f_u = nullptr, *f_ya = nullptr, *f_o1 = nullptr;
     float *f_emb = nullptr, *f_f1 = nullptr, *f_p = nullptr;
     size_t tn_scratch_elems = 0;
+    float* loss_weight = nullptr;         // [B] weights of the weighted loss (training; carved last: no other buffer moves)
   } W;
   int64_t plan(void* base, int batch, int training, Work* w) const;
 };

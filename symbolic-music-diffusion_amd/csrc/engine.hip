@@ -378,6 +378,7 @@ int64_t SmdEngine::plan(void* base, int batch, int training, Work* w) const {
     const size_t Mp = (R + 63) / 64 * 64;
     t.tn_scratch_elems = tr_path ? 0 : (size_t)2 * (2 * M) * Mp;
     t.tn_scratch = t.tn_scratch_elems ? c.take<bf16_t>(t.tn_scratch_elems) : nullptr;
+    t.loss_weight = c.take<float>(B);
   }
   if (fp32 && !training) {
     if (L > 0) {
@@ -1181,7 +1182,13 @@ int SmdEngine::loss_backward(const float* x0, const int* labels, const float* ep
     q.xt_bf16 = W.x_bf16; q.eps_out = W.eps; q.s_out = W.s;
     RC(launch_q_sample(q, st));
     RC(run_network(nullptr, st));
-    RC(launch_mse_loss_grad(W.pred, W.eps, batch_, S, C, Cp_, inv_global_count, W.loss, W.dpred, st, loss_kind ? W.s : nullptr));
+    if (loss_weighted()) {
+      SMD_ARG_CHECK(!loss_kind, "loss_backward: loss weights (set_loss_weights) apply to the DDPM objective only");
+      RC(launch_weighted_mse_loss_grad(W.pred, W.eps, W.s, loss_iw_, min_snr_gamma_, batch_, S, C, Cp_, inv_global_count, W.loss,
+                                       W.loss_weight, W.dpred, st));
+    } else {
+      RC(launch_mse_loss_grad(W.pred, W.eps, batch_, S, C, Cp_, inv_global_count, W.loss, W.dpred, st, loss_kind ? W.s : nullptr));
+    }
     if (grads_zeroed) {
       hipError_t e = hipStreamWaitEvent(st, grads_zeroed, 0);
       if (e != hipSuccess) { smd_set_error("loss_backward: %s", hipGetErrorString(e)); return (int)e; }

@@ -272,6 +272,23 @@ int launch_mse_loss_grad(const float* pred, const float* eps, int B, int S, int 
                          hipStream_t st, const float* dsm_sigma = nullptr,    // dsm_sigma [B]: the score-matching form
                          int* vec_out = nullptr);                             // nullable: VEC of the kernel this launch ran (4 / 1)
 
+// the DDPM loss with a weight per sample: w_b = iw_b min(1, gamma (1 - s_b^2) / s_b^2); iw null: 1;
+// gamma <= 0 or +inf: no SNR factor (noise_level may then be null).  dpred = 2 w_b (pred-eps) / (Bglobal*S*C), loss_per_sample
+// the UNWEIGHTED mean (launch_mse_loss_grad's bits), weight_per_sample [B] = w_b.
+int launch_weighted_mse_loss_grad(const float* pred, const float* eps, const float* noise_level, const float* iw, float gamma,
+                                  int B, int S, int C, int Cp, float inv_global_count, float* loss_per_sample,
+                                  float* weight_per_sample, bf16_t* dpred_bf16, hipStream_t st);
+
+// ------------------------------------------------------------------ loss-aware timestep sampler (timestep.hip)
+// labels_out[b] = label_base + (first i with cdf[i] > u_b), iw_out[b] = 1 / (n p[i]); u_b from u_in or the Philox stream
+// SMD_STREAM_TIMESTEP keyed by (seed, b + sample_offset, step); step_ptr (device, nullable) replaces `step`
+int launch_timestep_draw(const float* cdf, const float* p, int n, int label_base, int B, uint32_t seed_lo, uint32_t seed_hi,
+                         uint32_t sample_offset, uint32_t step, const uint32_t* step_ptr, const float* u_in, int* labels_out,
+                         float* iw_out, hipStream_t st);
+// the ten-deep loss history per timestep and the tables drawn from: one workgroup, samples applied in batch order
+int launch_timestep_update(const int* labels, const float* loss, int Bg, float* history, int* counts, int n, int label_base,
+                           float uniform_mix, float* p_out, float* cdf_out, int* warmed_out, hipStream_t st);
+
 // fused reverse step (reference utils/ebm_utils.py:327-394)
 struct ReverseStepArgs {
   float* x = nullptr;                 // [B][S][C] state, updated in place

@@ -126,7 +126,8 @@ class Engine:
             _lib.check(self.L.smd_engine_set_option(h, k.strip().encode(), int(v)), f"SMD_ENGINE_OPTS {kv}")
         self._label_min = 1
         self._loss_kind = 0
-        self.generation = 0          # bumped by whatever invalidates a captured step of this handle: bind, schedule, options
+        self._loss_weighted = False  # the handle holds loss weights other than (NULL, 0)
+        self.generation = 0         # bumped by whatever invalidates a captured step of this handle: bind, schedule, options
         self.grads = self.m = self.v = self.ema = None
         self.step_counter = None
         self.metrics = None
@@ -323,12 +324,21 @@ class Engine:
     def loss_backward(self, x0: torch.Tensor, labels: Optional[torch.Tensor] = None,
                       eps: Optional[torch.Tensor] = None, seed: int = 0, sample_offset: int = 0,
                       global_batch: Optional[int] = None, stage: int = 0, *, used_alphas: Optional[torch.Tensor] = None,
-                      continuous_noise: bool = True, objective: str = "ddpm") -> None:
+                      continuous_noise: bool = True, objective: str = "ddpm", loss_weights: Optional[torch.Tensor] = None,
+                      min_snr_gamma: float = 0.0) -> None:
         """``continuous_noise=False``: labels in [0, T) (utils/losses.py:272-275) and a real uniform used_alpha for label 0;
         ``used_alphas`` ([B] floats) passes the draws of :283-286 explicitly.  ``objective="dsm"``: the denoising
-        score-matching loss (:129-179) on the same network; ``used_alphas`` then carries the per-sample used_sigmas."""
+        score-matching loss (:129-179) on the same network; ``used_alphas`` then carries the per-sample used_sigmas.
+        ``loss_weights`` ([B] floats) / ``min_snr_gamma`` > 0: the weighted DDPM loss (include/smd_hip.h
+        smd_engine_set_loss_weights); the defaults run the unweighted kernel."""
         B = x0.shape[0] if x0 is not None else self.batch
         kind = {"ddpm": 0, "dsm": 1}[objective]
+        weighted = loss_weights is not None or float(min_snr_gamma) > 0.0
+        if weighted and kind != 0:
+            raise ValueError("loss weights (loss_weights / min_snr_gamma) apply to the DDPM objective only")
+        if weighted or self._loss_weighted:
+            _lib.check(self.L.smd_engine_set_loss_weights(self.h, _ptr(loss_weights), float(min_snr_gamma)), "set_loss_weights")
+            self._loss_weighted = weighted
         if kind != self._loss_kind:
             _lib.check(self.L.smd_engine_set_option(self.h, b"loss_kind", kind), "set_option loss_kind")
             self._loss_kind = kind
@@ -429,6 +439,10 @@ class Engine:
 
     def loss_per_sample(self) -> torch.Tensor:
         return self._borrow(self.L.smd_engine_loss_per_sample(self.h), (self.batch,))
+
+    def weight_per_sample(self) -> torch.Tensor:
+        """The per-sample weights of the last WEIGHTED loss_backward (include/smd_hip.h smd_engine_weight_per_sample)."""
+        return self._borrow(self.L.smd_engine_weight_per_sample(self.h), (self.batch,))
 
     def last_pred(self) -> torch.Tensor:
         return self._borrow(self.L.smd_engine_pred(self.h), (self.batch, *self.cfg.sample_shape))

@@ -278,6 +278,15 @@ ENGINE_FLAGS: List[FlagDef] = [
        "update DPM-Solver++(2M) of Lu et al. 2022 (deterministic: --ddim_eta=0; DESIGN.md section 18)."),
     _D("ddim_spacing", "enum", "uniform", "--ddim_steps: the timesteps are evenly spaced in t (uniform) or in "
        "lambda = log(sqrt(ap) / sqrt(1 - ap)) snapped to timesteps (logsnr: at most --ddim_steps of them).", ("uniform", "logsnr")),
+    _D("loss_weighting", "enum", "none", "train_ncsn --loss=ddpm: weight of every timestep in the loss, none (the reference) or "
+       "min_snr = min(SNR, --min_snr_gamma) / SNR (Hang et al. 2023; DESIGN.md section 25).  Works on any number of ranks.",
+       ("none", "min_snr")),
+    _D("min_snr_gamma", "float", 5.0, "--loss_weighting=min_snr: the SNR above which a timestep's weight falls as gamma / SNR."),
+    _D("timestep_sampler", "enum", "uniform", "train_ncsn --loss=ddpm: how training timesteps are drawn, uniform (the reference) "
+       "or loss_second_moment = p_t ~ sqrt(E[L_t^2]) from a ten-deep loss history with the loss re-weighted by 1 / (n p_t) "
+       "(Nichol & Dhariwal 2021; single process only; DESIGN.md section 25).", ("uniform", "loss_second_moment")),
+    _D("resume", "bool", False, "train_ncsn: start from the newest checkpoint under --model_dir (parameters, optimiser state, EMA, "
+       "early stopping and, from a safetensors checkpoint, the timestep sampler's tables) instead of a fresh initialisation."),
     _D("ckpt_format", "enum", "safetensors", "Checkpoint file format written by train_ncsn: safetensors, or the "
        "reference's flax-0.3.0 msgpack state dict (both are recognised when restoring).", ("safetensors", "flax")),
     _D("rng_impl", "enum", "philox", "Random streams: the engine's fused Philox draws, or jax.random-compatible "

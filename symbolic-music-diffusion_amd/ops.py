@@ -14,6 +14,8 @@ tensors out, launched on torch's current HIP stream; fake-tensor (meta) rules ar
   smd_amd::q_sample(x0, alphas_prod_ext, labels, eps)   utils/losses.py:271-296
   smd_amd::bound_noise(x0, eps, table, t)               x_t of the variational bound at the device timestep t (DESIGN.md 17)
   smd_amd::bound_terms(x0, eps, eps_hat, table, t, clip)   its three per-example sums [B][3]
+  smd_amd::timestep_draw(cdf, p, u, label_base)         loss-aware timestep labels and importance weights (DESIGN.md 25)
+  smd_amd::weighted_mse(pred, eps, s, iw, gamma, inv)   the weighted DDPM loss and its gradient w.r.t. pred
 
 ``engine`` is the integer id of a live ``smd_amd.engine.Engine`` (``register_engine``); custom-op schemas carry tensors
 and scalars only.
@@ -237,3 +239,56 @@ def bound_terms(x0: torch.Tensor, eps: torch.Tensor, eps_hat: torch.Tensor, tabl
 @bound_terms.register_fake
 def _(x0, eps, eps_hat, table, t, clip):
     return x0.new_empty((x0.shape[0], 3), dtype=torch.float32)
+
+
+# ---- weighted training
+@torch.library.custom_op("smd_amd::timestep_draw", mutates_args=())
+def timestep_draw(cdf: torch.Tensor, p: torch.Tensor, u: torch.Tensor, label_base: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(labels int32 [B], iw fp32 [B]) from the uniforms ``u`` [B]: label_base + (first i with cdf[i] > u), iw = 1 / (n p[i])
+    (include/smd_hip.h smd_timestep_draw; trainer.TimestepSampler.draw also makes the uniforms)."""
+    _need_gpu(cdf, p, u)
+    if cdf.dtype != torch.float32 or p.dtype != torch.float32 or u.dtype != torch.float32 or cdf.dim() != 1 or p.shape != cdf.shape or u.dim() != 1:
+        raise ValueError("timestep_draw: cdf, p fp32 [n], u fp32 [B]")
+    cdf, p, u = cdf.contiguous(), p.contiguous(), u.contiguous()
+    B = u.shape[0]
+    labels = torch.empty((B,), dtype=torch.int32, device=u.device)
+    iw = torch.empty((B,), dtype=torch.float32, device=u.device)
+    with torch.cuda.device(u.device):
+        _lib.check(_lib.get_lib().smd_timestep_draw(cdf.data_ptr(), p.data_ptr(), cdf.shape[0], int(label_base), B, 0, 0, 0, 0, None,
+                                                    u.data_ptr(), labels.data_ptr(), iw.data_ptr(), _stream()), "timestep_draw")
+    return labels, iw
+
+
+@timestep_draw.register_fake
+def _(cdf, p, u, label_base):
+    return u.new_empty(u.shape, dtype=torch.int32), u.new_empty(u.shape, dtype=torch.float32)
+
+
+@torch.library.custom_op("smd_amd::weighted_mse", mutates_args=())
+def weighted_mse(pred: torch.Tensor, eps: torch.Tensor, noise_level: torch.Tensor, iw: torch.Tensor, min_snr_gamma: float,
+                 inv_global_count: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(loss_per_sample [B] unweighted, weight_per_sample [B], dpred bf16 [B*S][C]) of the weighted DDPM loss: w = iw min(1,
+    gamma (1 - s^2) / s^2), dpred = 2 w (pred - eps) inv_global_count (include/smd_hip.h smd_weighted_mse_fwd_bwd)."""
+    _need_gpu(pred, eps, noise_level, iw)
+    if pred.dtype != torch.float32 or eps.dtype != torch.float32 or eps.shape != pred.shape or pred.dim() not in (2, 3):
+        raise ValueError("weighted_mse: pred, eps fp32 (B, S, C) or (B, C) tensors of one shape")
+    B, S, Cn = _bsc(pred)
+    if noise_level.dtype != torch.float32 or iw.dtype != torch.float32 or noise_level.numel() != B or iw.numel() != B:
+        raise ValueError("weighted_mse: noise_level, iw fp32 [B]")
+    pred, eps, noise_level, iw = pred.contiguous(), eps.contiguous(), noise_level.contiguous(), iw.contiguous()
+    loss = torch.empty((B,), dtype=torch.float32, device=pred.device)
+    w = torch.empty_like(loss)
+    dpred = torch.empty((B * S, Cn), dtype=torch.bfloat16, device=pred.device)
+    with torch.cuda.device(pred.device):
+        _lib.check(_lib.get_lib().smd_weighted_mse_fwd_bwd(pred.data_ptr(), eps.data_ptr(), noise_level.data_ptr(), iw.data_ptr(),
+                                                           float(min_snr_gamma), B, S, Cn, Cn, float(inv_global_count), loss.data_ptr(),
+                                                           w.data_ptr(), dpred.data_ptr(), _stream()), "weighted_mse")
+    return loss, w, dpred
+
+
+@weighted_mse.register_fake
+def _(pred, eps, noise_level, iw, min_snr_gamma, inv_global_count):
+    B = pred.shape[0]
+    rows = B if pred.dim() == 2 else B * pred.shape[1]
+    return (pred.new_empty((B,), dtype=torch.float32), pred.new_empty((B,), dtype=torch.float32),
+            pred.new_empty((rows, pred.shape[-1]), dtype=torch.bfloat16))

@@ -34,6 +34,20 @@ def alphas_cumprod(betas: np.ndarray) -> np.ndarray:
     return np.cumprod((np.float32(1.0) - betas).astype(np.float32), dtype=np.float32)
 
 
+def min_snr_weight(alphas_prod_like, gamma: float) -> np.ndarray:
+    """Min-SNR-gamma loss weight of an eps-prediction loss (Hang et al. 2023), float64: min(SNR, gamma) / SNR with
+    SNR = ap / (1 - ap), i.e. min(1, gamma (1 - ap) / ap) -- 1 where SNR <= gamma, gamma / SNR above.  ``gamma`` <= 0 or +inf: no
+    weighting (all ones).  ap = 1 (SNR = inf) gives 0 and ap = 0 gives 1, never a NaN.  The weighted loss kernel evaluates the
+    same expression per sample from the squared noise level q-sample stored."""
+    ap = np.asarray(alphas_prod_like, dtype=np.float64)
+    gamma = float(gamma)
+    if not (gamma > 0.0) or np.isinf(gamma):
+        return np.ones_like(ap)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = gamma * (1.0 - ap) / ap
+    return np.minimum(1.0, np.where(ap > 0.0, f, np.inf))
+
+
 def reverse_coefficient_table(betas: np.ndarray) -> np.ndarray:
     """[T][8] float32: sqrt(1/ap), sqrt(1-ap)*sqrt(1/ap), mu1, mu2, sigma, ap, sqrt(ap), sqrt(1-ap)
     (utils/ebm_utils.py:332-358, sigma = exp(0.5*log(max(var,1e-20))) as at :356-364)."""

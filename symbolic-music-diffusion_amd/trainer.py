@@ -68,10 +68,128 @@ class LazyMetrics(dict):
         return {k: (float(v) if torch.is_tensor(v) else v) for k, v in self.items()}
 
 
+LOSS_WEIGHTINGS = ("none", "min_snr")
+TIMESTEP_SAMPLERS = ("uniform", "loss_second_moment")
+
+
+def validate_training_options(loss: str = "ddpm", loss_weighting: str = "none", timestep_sampler: str = "uniform",
+                              world_size: int = 1) -> None:
+    """The combinations of --loss / --loss_weighting / --timestep_sampler this engine trains; anything else
+    raises a ValueError that says what is refused.  train_ncsn.py calls this before it touches a device."""
+    if loss_weighting not in LOSS_WEIGHTINGS:
+        raise ValueError(f"--loss_weighting must be one of {LOSS_WEIGHTINGS}, got {loss_weighting!r}")
+    if timestep_sampler not in TIMESTEP_SAMPLERS:
+        raise ValueError(f"--timestep_sampler must be one of {TIMESTEP_SAMPLERS}, got {timestep_sampler!r}")
+    if loss != "ddpm" and (loss_weighting != "none" or timestep_sampler != "uniform"):
+        raise ValueError(f"--loss_weighting={loss_weighting} / --timestep_sampler={timestep_sampler} apply to --loss=ddpm only "
+                         f"(got --loss={loss}): the weights are defined for the eps-prediction DDPM loss")
+    if timestep_sampler == "loss_second_moment" and world_size > 1:
+        raise ValueError(f"--timestep_sampler=loss_second_moment is single-process only (world size {world_size}): every rank "
+                         "would need the labels and losses of the whole batch (an all-gather per step) to keep the tables "
+                         "equal; run one process, or --timestep_sampler=uniform (--loss_weighting=min_snr works on any "
+                         "number of ranks)")
+
+
+class TimestepSampler:
+    """The loss-second-moment timestep resampler of Nichol & Dhariwal 2021 on the device: timesteps are
+    drawn with p_t ~ sqrt(E[L_t^2]) from a ten-deep history of per-timestep losses (uniform until every timestep has ten), and
+    the loss is re-weighted by 1 / (n p_t) so that the objective stays the uniform one in expectation.
+
+    ``n`` timesteps starting at ``label_base``: the range of the run's uniform label draw -- ``for_schedule`` takes it from
+    (len(sigmas), continuous_noise) exactly as q-sample does (labels in [label_min, label_min + T), utils/losses.py:272-275).
+    The tables (history [n][10], counts [n], p [n], cdf [n]) live on the device and are touched by two kernels only
+    (include/smd_hip.h smd_timestep_draw / smd_timestep_update): no host synchronisation per step."""
+
+    DEPTH = 10
+    STATE_KEYS = ("history", "counts", "p", "cdf")
+
+    def __init__(self, n: int, label_base: int, device, uniform_mix: float = 1e-3):
+        if n <= 0:
+            raise ValueError(f"TimestepSampler: n={n}")
+        self.n, self.label_base, self.uniform_mix = int(n), int(label_base), float(uniform_mix)
+        self.device = torch.device(device)
+        self.history = torch.zeros(self.n, self.DEPTH, dtype=torch.float32, device=self.device)
+        self.counts = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self.p = torch.full((self.n,), 1.0 / self.n, dtype=torch.float32, device=self.device)
+        self.cdf = torch.cumsum(self.p.double(), 0).float()
+        self._warmed = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.last_labels: Optional[torch.Tensor] = None      # what the last draw() returned (tests, logging)
+        self.last_iw: Optional[torch.Tensor] = None
+
+    @classmethod
+    def for_schedule(cls, sigmas, continuous_noise: bool, device, uniform_mix: float = 1e-3) -> "TimestepSampler":
+        # the engine's label draw: label_min + r % T with T = len(sigmas), label_min = 1 with continuous noise else 0
+        # (csrc/diffusion.hip q_sample; jax_random.diffusion_loss_draws: randint(cn, T + cn))
+        return cls(len(sigmas), 1 if continuous_noise else 0, device, uniform_mix)
+
+    @property
+    def warmed(self) -> bool:
+        """Every timestep has ten losses (reads one int back: synchronises)."""
+        return bool(self._warmed.item())
+
+    def draw(self, B: int, rng, step: Optional[int] = None, sample_offset: int = 0, *, global_batch: Optional[int] = None,
+             u: Optional[torch.Tensor] = None, step_ptr: Optional[torch.Tensor] = None):
+        """(labels int32 [B], iw float32 [B]) for the samples [sample_offset, sample_offset + B) of the global batch: keyed by the
+        global sample index, so a shard draws what the whole batch would.  Philox keys: the uniforms come from the engine's
+        stream SMD_STREAM_TIMESTEP at (seed, sample, step); ``step_ptr`` (a device uint32, e.g. the optimiser's step counter)
+        replaces ``step``.  A ThreefryKey: u = jax.random.uniform(split(rng, 4)[3], (global_batch,)) -- the reference has no such
+        draw; its loss uses split(rng, 3).  ``u`` passes the uniforms explicitly."""
+        from . import jax_random as _jr
+        from . import lib as _lib
+        labels = torch.empty(B, dtype=torch.int32, device=self.device)
+        iw = torch.empty(B, dtype=torch.float32, device=self.device)
+        seed = 0
+        if u is not None:
+            u = torch.as_tensor(u).to(self.device, torch.float32).contiguous()
+            if u.numel() != B:
+                raise ValueError(f"TimestepSampler.draw: u has {u.numel()} entries for batch {B}")
+        elif isinstance(rng, ThreefryKey):
+            gb = B if global_batch is None else int(global_batch)
+            u = _jr.uniform(_jr.split(rng, 4)[3], (B,), self.device, n_total=gb, offset=sample_offset)
+        else:
+            seed = int(rng.seed)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.get_lib().smd_timestep_draw(
+                self.cdf.data_ptr(), self.p.data_ptr(), self.n, self.label_base, B, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                int(sample_offset), int(step or 0) & 0xFFFFFFFF, None if step_ptr is None else step_ptr.data_ptr(),
+                None if u is None else u.data_ptr(), labels.data_ptr(), iw.data_ptr(),
+                torch.cuda.current_stream().cuda_stream), "timestep_draw")
+        self.last_labels, self.last_iw = labels, iw
+        return labels, iw
+
+    def update(self, labels: torch.Tensor, loss: torch.Tensor) -> None:
+        """Feeds the (label, unweighted per-sample loss) pairs of a WHOLE batch, in sample order, into the history and
+        refreshes p and cdf."""
+        from . import lib as _lib
+        labels = torch.as_tensor(labels).to(self.device, torch.int32).contiguous()
+        loss = torch.as_tensor(loss).to(self.device, torch.float32).contiguous()
+        if labels.numel() != loss.numel() or labels.numel() == 0:
+            raise ValueError(f"TimestepSampler.update: {labels.numel()} labels for {loss.numel()} losses")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.get_lib().smd_timestep_update(
+                labels.data_ptr(), loss.data_ptr(), labels.numel(), self.history.data_ptr(), self.counts.data_ptr(), self.n,
+                self.label_base, self.uniform_mix, self.p.data_ptr(), self.cdf.data_ptr(), self._warmed.data_ptr(),
+                torch.cuda.current_stream().cuda_stream), "timestep_update")
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        return {k: getattr(self, k).detach().cpu().clone() for k in self.STATE_KEYS}
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        for k in self.STATE_KEYS:
+            dst, src = getattr(self, k), torch.as_tensor(sd[k])
+            if tuple(src.shape) != tuple(dst.shape):
+                raise ValueError(f"TimestepSampler.load_state_dict: {k} has shape {tuple(src.shape)}, this sampler {tuple(dst.shape)} "
+                                 "(another --num_sigmas?)")
+            dst.copy_(src.to(dst.dtype))
+        self._warmed.copy_((self.counts >= self.DEPTH).all().to(torch.int32).reshape(1))
+
+
 def train_step(objective, batch, optimizer: Optimizer, sigmas, rng: PRNGKey, learning_rate: float, *,
                grad_clip: float = 1.0, mu: float = 0.999, labels=None, eps=None, comm: "Optional[GradComm]" = None,
                lr_gamma: float = 1.0, lr_interval: int = 1, sample_offset: int = 0,
-               global_batch: Optional[int] = None, continuous_noise: bool = True, used_alphas=None):
+               global_batch: Optional[int] = None, continuous_noise: bool = True, used_alphas=None,
+               loss_weighting: str = "none", min_snr_gamma: float = 5.0,
+               timestep_sampler: "Optional[TimestepSampler]" = None, loss_weights=None):
     """train_ncsn.py:260-288: value_and_grad(mean diffusion_loss) -> clip_grads -> Adam
     (+ EMA, fused).  ``learning_rate`` is the step's LR as in the reference; pass ``lr_gamma`` /
     ``lr_interval`` instead to let the kernel evaluate the stepped schedule from its own step
@@ -82,7 +200,22 @@ def train_step(objective, batch, optimizer: Optimizer, sigmas, rng: PRNGKey, lea
     backward as one engine call).  ANY other callable ``objective(batch, model, sigmas, rng, continuous_noise, 'mean')`` written in
     torch is differentiated as the reference differentiates it (jax.value_and_grad, :279-283): ``model`` is then a
     ``DifferentiableModel`` whose ``model(x, cond)`` runs the engine's forward and whose autograd backward is the engine's backward
-    pass from d objective / d eps_hat (one model call per objective; second-order objectives like 'ssm' are not supported)."""
+    pass from d objective / d eps_hat (one model call per objective; second-order objectives like 'ssm' are not supported).
+
+    Weighted training (``objective is diffusion_loss`` only): ``loss_weighting="min_snr"`` weights every
+    sample by min(SNR, min_snr_gamma) / SNR of its noise level, ``timestep_sampler`` (a TimestepSampler) draws the labels from
+    its loss-aware table, weights the samples by 1 / (n p) and is fed the step's per-sample losses; ``loss_weights`` ([B]) passes
+    importance weights explicitly.  metrics['loss'] is then the weighted objective that is optimised, mean(w loss), and
+    metrics['loss_unweighted'] the plain mean.  With the defaults nothing changes."""
+    if loss_weighting not in LOSS_WEIGHTINGS:
+        raise ValueError(f"train_step: loss_weighting must be one of {LOSS_WEIGHTINGS}, got {loss_weighting!r}")
+    weighted = loss_weighting != "none" or timestep_sampler is not None or loss_weights is not None
+    if weighted and objective is not diffusion_loss:
+        raise ValueError("train_step: loss_weighting / timestep_sampler / loss_weights apply to objective=diffusion_loss (the DDPM "
+                         f"loss) only, got {getattr(objective, '__name__', objective)!r}")
+    if timestep_sampler is not None and comm is not None and comm.world_size > 1:
+        raise ValueError(f"train_step: a timestep_sampler is single-process only (world size {comm.world_size}): its tables need "
+                         "the labels and losses of the whole batch")
     eng = optimizer.engine
     batch = torch.as_tensor(batch).to(eng.device, torch.float32).contiguous()
     if objective is not diffusion_loss and objective is not denoising_score_matching_loss:
@@ -99,6 +232,7 @@ def train_step(objective, batch, optimizer: Optimizer, sigmas, rng: PRNGKey, lea
     world = 1 if comm is None else comm.world_size
     gb = batch.shape[0] * world if global_batch is None else global_batch
     ua = None if used_alphas is None else torch.as_tensor(used_alphas).to(eng.device, torch.float32).contiguous()
+    iw = None
     if dsm:
         # utils/losses.py:149-164: the noise level travels per sample (used_alphas carries the used_sigmas)
         sig = torch.as_tensor(np.asarray(sigmas, dtype=np.float32)).to(eng.device)
@@ -112,11 +246,26 @@ def train_step(objective, batch, optimizer: Optimizer, sigmas, rng: PRNGKey, lea
         # the reference's own draws (utils/losses.py:271-294) for this rank's rows of the global batch
         lab, e = diffusion_loss_draws(rng, tuple(batch.shape), len(sigmas), eng.device, sample_offset=sample_offset,
                                       global_batch=gb, continuous_noise=continuous_noise)
+        if timestep_sampler is not None:
+            # the sampler's labels replace the uniform ones (eps stays the reference's draw); the step key is the step: no counter
+            lab, iw = timestep_sampler.draw(batch.shape[0], rng, sample_offset=sample_offset, global_batch=gb)
         if not continuous_noise and ua is None:
             ua = diffusion_loss_used_alphas(rng, lab, eng._sched_tensors["ape"], sample_offset=sample_offset,
                                             global_batch=gb)
+    elif timestep_sampler is not None and lab is None:
+        # keyed like q-sample's own label draw: (seed, global sample index, the optimiser's step counter read on the device)
+        lab, iw = timestep_sampler.draw(batch.shape[0], rng, sample_offset=sample_offset, global_batch=gb,
+                                        step_ptr=None if isinstance(rng, ThreefryKey) else eng.step_counter)
     kw = dict(seed=rng.seed, sample_offset=sample_offset, global_batch=gb, used_alphas=ua, continuous_noise=continuous_noise,
               objective="dsm" if dsm else "ddpm")
+    if weighted:
+        if loss_weights is not None:
+            iw = torch.as_tensor(loss_weights).to(eng.device, torch.float32).contiguous()
+            if iw.numel() != batch.shape[0]:
+                raise ValueError(f"train_step: loss_weights has {iw.numel()} entries for batch {batch.shape[0]}")
+        kw.update(loss_weights=iw, min_snr_gamma=float(min_snr_gamma) if loss_weighting == "min_snr" else 0.0)
+        if iw is None and not kw["min_snr_gamma"] > 0.0:
+            raise ValueError(f"train_step: loss_weighting='min_snr' needs min_snr_gamma > 0 (inf: no SNR factor), got {min_snr_gamma}")
     # optimiser placement (engine option "opt_overlap"): 0 = the whole sweep on this stream.  Deferring the
     # output-stage slice to the side stream (bit 0) measured +1 % at best on a process's FIRST training engine and HALVED the
     # step rate of every second later engine of the same process (profiles/r4q_extras_opt_overlap.txt: the per-step
@@ -147,8 +296,15 @@ def train_step(objective, batch, optimizer: Optimizer, sigmas, rng: PRNGKey, lea
         comm.wait()
     # gradients were scaled by 1/(global_batch*S*C) at the loss, so the all-reduce SUM is the global mean
     eng.optimizer_step(learning_rate, lr_gamma, lr_interval, grad_clip, mu, 1.0)
-    loss = eng.loss_per_sample().mean()
+    per_sample = eng.loss_per_sample()
+    loss = per_sample.mean()
     metrics = LazyMetrics(loss=loss, grad=eng.metrics[1], lr=eng.metrics[2])
+    if weighted:
+        # the objective that was optimised, from the weights the loss kernel wrote; the plain mean stays comparable between runs
+        metrics["loss"] = (eng.weight_per_sample() * per_sample).mean()
+        metrics["loss_unweighted"] = loss
+        if timestep_sampler is not None:
+            timestep_sampler.update(lab, per_sample)         # the UNWEIGHTED per-sample losses, in sample order
     return optimizer, metrics
 
 

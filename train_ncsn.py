@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import logging
 import os
+import re
 import sys
 import time
 
@@ -92,12 +93,38 @@ def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world
         if optimizer.engine.ema is not None:
             optimizer.engine.ema.copy_(model.params)
     early_stop = train_utils.EarlyStopping(patience=1)                            # :333
+    # weighted training: min-SNR loss weights and / or the loss-aware timestep sampler
+    train_options = {"loss_weighting": FLAGS.loss_weighting, "min_snr_gamma": FLAGS.min_snr_gamma,
+                     "timestep_sampler": FLAGS.timestep_sampler}
+    sampler = None
+    if FLAGS.timestep_sampler == "loss_second_moment":
+        from smd_amd.trainer import TimestepSampler
+        sampler = TimestepSampler.for_schedule(sigmas, FLAGS.continuous_noise, dev)
+    if rank == 0:
+        log.info("loss weighting: %s (min_snr_gamma %g); timestep sampler: %s", FLAGS.loss_weighting, FLAGS.min_snr_gamma,
+                 FLAGS.timestep_sampler)
+    resumed_from = -1
+    if FLAGS.resume:
+        found, restored = checkpoint.restore_checkpoint(output_dir, optimizer.engine)
+        if found:
+            early_stop = restored
+            resumed_from = int(re.findall(r"(\d+)$", checkpoint.latest_checkpoint(output_dir))[0])
+            if rank == 0:
+                log.info("resumed from %s at optimiser step %d", checkpoint.latest_checkpoint(output_dir), optimizer.step)
+            if sampler is not None:
+                if checkpoint.restore_timestep_sampler(output_dir, sampler):
+                    log.info("timestep sampler: tables restored from the checkpoint (warmed up: %s)", sampler.warmed)
+                else:
+                    log.info("timestep sampler: the checkpoint holds no tables (a flax-format file, or a run with the uniform "
+                             "draw): the warm-up restarts")
+        elif rank == 0:
+            log.info("--resume: no checkpoint under %s, starting fresh", output_dir)
     ema = train_utils.EMAHelper(FLAGS.mu, optimizer.engine.ema if FLAGS.ema else model.params.clone(),
                                 fused=FLAGS.ema)                                  # :336 (untouched init when --ema=False)
 
     # :345-352 (ssm needs a second backward through the network and is a toy-only objective upstream)
     objective = {"ddpm": ncsn.diffusion_loss, "dsm": ncsn.denoising_score_matching_loss}[FLAGS.loss]
-    sampling_step = -1
+    sampling_step = resumed_from                    # checkpoints are numbered by this counter: a resumed run goes on counting
     for epoch in range(FLAGS.epochs):
         start_time = time.time()
         if hasattr(train_batches, "set_epoch"):
@@ -110,7 +137,8 @@ def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world
                 objective, batch, optimizer, sigmas, train_rng, FLAGS.learning_rate,
                 grad_clip=FLAGS.grad_clip, mu=FLAGS.mu, comm=comm, lr_gamma=FLAGS.lr_gamma,
                 lr_interval=FLAGS.lr_schedule_interval, sample_offset=rank * FLAGS.batch_size,
-                global_batch=FLAGS.batch_size * world, continuous_noise=FLAGS.continuous_noise)
+                global_batch=FLAGS.batch_size * world, continuous_noise=FLAGS.continuous_noise,
+                loss_weighting=FLAGS.loss_weighting, min_snr_gamma=FLAGS.min_snr_gamma, timestep_sampler=sampler)
             if FLAGS.ema:
                 ema = ema.update(optimizer.target)                                # :364-365 (fused: no-op)
 
@@ -133,7 +161,8 @@ def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world
                     if (not FLAGS.early_stopping and FLAGS.save_ckpt) or \
                             (FLAGS.early_stopping and improved and FLAGS.save_ckpt):          # :395-399
                         checkpoint.save_checkpoint(output_dir, (optimizer, ema, early_stop), sampling_step,
-                                                   keep=FLAGS.checkpoints_to_keep, fmt=FLAGS.ckpt_format)
+                                                   keep=FLAGS.checkpoints_to_keep, fmt=FLAGS.ckpt_format,
+                                                   timestep_sampler=sampler, train_options=train_options)
                 # early stop is decided BEFORE snapshot sampling, as the reference returns first (:401-403)
                 if comm is not None:                                                           # keep ranks in step
                     flag = torch.tensor([1.0 if (FLAGS.early_stopping and early_stop.should_stop) else 0.0],
@@ -181,6 +210,14 @@ def main(argv):
     if FLAGS.dtype == "fp32":
         raise SystemExit("--dtype=fp32: fp32 is an inference precision in this engine; train with --dtype=bf16 or fp8 and "
                          "sample the checkpoint with sample_ncsn.py --dtype=fp32")
+    try:
+        from smd_amd.trainer import validate_training_options
+        validate_training_options(FLAGS.loss, FLAGS.loss_weighting, FLAGS.timestep_sampler, world)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if FLAGS.timestep_sampler == "loss_second_moment" and FLAGS.ckpt_format == "flax" and rank == 0:
+        log.info("--ckpt_format=flax has no place for the timestep sampler's tables: they are not saved, a resumed run restarts "
+                 "its warm-up")
     torch.cuda.set_device(local_rank)
     if world > 1:
         import torch.distributed as dist
