@@ -87,6 +87,10 @@ int smd_engine_padded_channels(const smd_engine* e);
  *                        _forward_train, _loss_backward, _backward_from and _optimizer_step ("fp32 is an inference precision
  *                        in this engine"): train in bf16, audit or publish samples in fp32 from the same parameter buffer.
  *   "label_min" 1/0      Philox labels in [1, T] (continuous_noise) or [0, T);  "loss_kind" 0/1  DDPM / score matching
+ *   "prediction" 0       what the network's output means to smd_engine_loss_backward (any time; DDPM objective only: an
+ *                        argument error together with "loss_kind" 1, and for values outside 0..2): 0 eps (the reference), 1 x0,
+ *                        2 v = s eps - sqrt(1 - s^2) x0 (Salimans & Ho 2022).  See smd_engine_set_loss_weights for the targets
+ *                        and weights.  Samplers and the bound take the kind through their coefficient tables, not from here.
  *   "grad_memset" 2      0 never / 1 always / 2 only with the tr_path = 0 fallback: zero the gradient buffer before a step
  *                        (every gradient element is written, not accumulated, by the default kernels)
  *   "nt256_min_tiles" 0  > 0: Dense layers take the 256x256 GEMM from this many output tiles up (default rule: 192)
@@ -152,9 +156,21 @@ int smd_engine_set_used_alphas(smd_engine* e, const float* used_alphas);
  * squared noise level q-sample stored, w_b = iw_b min(1, min_snr_gamma (1 - ap) / ap) -- for eps-prediction min(SNR, gamma) / SNR
  * -- and the gradient of the step is that of mean_b(w_b loss_b); smd_engine_loss_per_sample stays the UNWEIGHTED loss and
  * smd_engine_weight_per_sample returns the w_b ([B] device floats, valid after a weighted call).  iw: [B] device floats or NULL
- * (= 1); min_snr_gamma <= 0 or +inf: no SNR factor.  (NULL, 0), the state of a new handle, runs the unweighted kernel. */
+ * (= 1); min_snr_gamma <= 0 or +inf: no SNR factor.  (NULL, 0), the state of a new handle, runs the unweighted kernel.
+ * With option "prediction" (s = the stored noise level, ap = s^2, sb = sqrt((1 - s)(1 + s)),
+ * SNR = ap / (1 - ap)) the loss compares the network's output `out` with another target and the SNR factor changes with it:
+ *   kind      target            x0 from out: c0 x_t - c1 out             SNR factor of w_b
+ *   0 eps     eps               c0 = sqrt(1/ap), c1 = sqrt(1/ap - 1)     min(1, gamma / SNR)
+ *   1 x0      x0                c0 = 0,          c1 = -1                 min(SNR, gamma)             ap = 1: gamma, ap = 0: 0
+ *   2 v       s eps - sb x0     c0 = sqrt(ap),   c1 = sqrt(1 - ap)       min(SNR, gamma) / (SNR + 1) ap = 1: 0,     ap = 0: 0
+ * (the v factor is evaluated as min(ap, gamma (1 - ap)): finite everywhere).  Kinds 1 and 2 always run the weighted form: with
+ * (NULL, 0) every w_b is exactly 1 and smd_engine_weight_per_sample is valid all the same.  smd_engine_loss_per_sample is the
+ * unweighted mean of (out - target)^2, in the output space of the kind; stage 3 (loss only) reports the same. */
 int smd_engine_set_loss_weights(smd_engine* e, const float* iw, float min_snr_gamma);
 const float* smd_engine_weight_per_sample(const smd_engine* e); /* [B] device pointer */
+/* [B] device pointer: the noise level s_b = sqrt(used alpha) q-sample stored in the last smd_engine_loss_backward (what the
+ * weights above are evaluated on; the host turns an x0 / v loss into eps units with it) */
+const float* smd_engine_noise_level_per_sample(const smd_engine* e);
 const float* smd_engine_loss_per_sample(const smd_engine* e);   /* [B] device pointer */
 const float* smd_engine_pred(const smd_engine* e);              /* [B*S][C] device pointer */
 
@@ -508,6 +524,12 @@ int smd_adam_clip_ema(float* params, const float* grads, float* m, float* v, flo
 int smd_weighted_mse_fwd_bwd(const float* pred, const float* eps, const float* noise_level, const float* iw, float min_snr_gamma,
                              int B, int S, int C, int Cp, float inv_global_count, float* loss_per_sample,
                              float* weight_per_sample, smd_bf16* dpred_bf16, void* stream);
+/* smd_weighted_mse_fwd_bwd for a network that predicts x0 (kind 1) or v (kind 2): target and w_b as tabulated at
+ * smd_engine_set_loss_weights, x0 [B][S][C] fp32 (16-byte aligned like pred when C and Cp are multiples of 4).  eps may be NULL for
+ * kind 1; noise_level may be NULL for kind 1 without an SNR factor.  kind 0 forwards to smd_weighted_mse_fwd_bwd (x0 unused). */
+int smd_param_mse_fwd_bwd(const float* pred, const float* eps, const float* x0, const float* noise_level, const float* iw,
+                          float min_snr_gamma, int kind, int B, int S, int C, int Cp, float inv_global_count,
+                          float* loss_per_sample, float* weight_per_sample, smd_bf16* dpred_bf16, void* stream);
 int smd_timestep_draw(const float* cdf, const float* p, int n, int label_base, int B, uint32_t seed_lo, uint32_t seed_hi,
                       uint32_t sample_offset, uint32_t step, const uint32_t* step_ptr, const float* u_in, int32_t* labels_out,
                       float* iw_out, void* stream);

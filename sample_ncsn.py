@@ -51,6 +51,24 @@ def load_model(FLAGS, shape, device):
     return model, rng
 
 
+def _prediction(FLAGS) -> str:
+    """The resolved --prediction (main settles it against the checkpoint before anything runs); eps when it was never given."""
+    return getattr(FLAGS, "prediction", "") or "eps"
+
+
+def resolve_prediction_flag(FLAGS) -> str:
+    """--prediction against what the checkpoint under --model_dir records (smd_amd.checkpoint.resolve_prediction): empty takes
+    the checkpoint's kind (eps when it names none: a flax-format file, an older checkpoint, no checkpoint), a contradiction is a
+    ValueError.  A kind other than eps needs --sampling=ddpm."""
+    from smd_amd import checkpoint
+    kind = checkpoint.resolve_prediction(FLAGS.prediction, checkpoint.checkpoint_prediction(FLAGS.model_dir),
+                                         f"the checkpoint under {FLAGS.model_dir}")
+    if kind != "eps" and FLAGS.sampling != "ddpm":
+        raise ValueError(f"--prediction={kind} needs --sampling=ddpm (got --sampling={FLAGS.sampling}): the Langevin samplers "
+                         "(--sampling=ald, --sampling=cas) take the network's output as a score")
+    return kind
+
+
 def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sample_offset=0, global_num_samples=None):
     """sample_ncsn.py:313-365."""
     from smd_amd import ncsn
@@ -60,7 +78,7 @@ def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sampl
         model, sigmas, sample_rng, sample_shape, num_samples=num_samples, sampling=FLAGS.sampling,
         epsilon=FLAGS.ld_epsilon, steps=FLAGS.ld_steps, denoise=FLAGS.denoise, sample_offset=sample_offset,
         use_graph=FLAGS.graph, global_num_samples=global_num_samples, ddim_steps=FLAGS.ddim_steps, ddim_eta=FLAGS.ddim_eta,
-        ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing)
+        ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS))
     torch.cuda.synchronize()
     log.info("Generated samples in %f seconds", time.time() - t0)
     return generated, collection, ld_metrics
@@ -89,12 +107,12 @@ def infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=0, g
         generated, collection, ld_metrics = ncsn.strided_dynamics(
             ld_rng, model, sigmas, init, FLAGS.ddim_steps, FLAGS.ddim_eta, True, infill_samples=samples, infill_masks=masks,
             use_graph=FLAGS.graph, sample_offset=sample_offset, global_num_samples=global_num_samples, order=FLAGS.ddim_order,
-            spacing=FLAGS.ddim_spacing)
+            spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS))
         return generated, collection, ncsn.collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = ncsn.diffusion_dynamics(
         ld_rng, model, sigmas, init, FLAGS.ld_epsilon, FLAGS.ld_steps, FLAGS.denoise, True,
         infill_samples=samples, infill_masks=masks, use_graph=FLAGS.graph, sample_offset=sample_offset,
-        global_num_samples=global_num_samples)
+        global_num_samples=global_num_samples, prediction=_prediction(FLAGS))
     return generated, collection, ncsn.collate_sampling_metrics(ld_metrics.cpu().numpy())
 
 
@@ -116,19 +134,21 @@ def diffusion_stochastic_encoder(samples, sigmas, rng, device="cuda:0", sample_o
 
 
 def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl, dev, use_graph=True, points=9, ddim_steps=0,
-                        ddim_eta=0.0, ddim_encode=False, ddim_order=1, ddim_spacing="uniform"):
+                        ddim_eta=0.0, ddim_encode=False, ddim_order=1, ddim_spacing="uniform", prediction="eps"):
     """sample_ncsn.py:425-435 + diffusion_decoder (:269-310) for this rank's rows [lo, hi): goals = roll(starts, 1); both are
     encoded with the same key (the same noise); every one of the 9 interpolated latents is decoded with the SAME
     ld_rng = split(PRNGKey(sample_seed), 3)[1].  Returns (generated (9, n, ...), collection (9, 41, n, ...), collated metrics).
     ``ddim_steps`` > 0: the points are decoded with the strided sampler; with ``ddim_encode`` starts and goals are encoded by its
     deterministic inversion (ncsn.ddim_encode) instead of the single re-noising.  ``ddim_order`` / ``ddim_spacing``: the solver
-    and the grid of the decoding walks (ncsn.strided_dynamics)."""
+    and the grid of the decoding walks (ncsn.strided_dynamics); ``prediction``: what the network's output means, for the
+    inversion and every decoding walk."""
     from smd_amd import ncsn
     num = len(real)
     starts = real[lo:hi]
     goals = np.roll(real, shift=1, axis=0)[lo:hi]
     if ddim_steps and ddim_encode:
-        zs, zg = (ncsn.ddim_encode(model, sigmas, np.ascontiguousarray(v, dtype=np.float32), ddim_steps, use_graph=use_graph).cpu().numpy()
+        zs, zg = (ncsn.ddim_encode(model, sigmas, np.ascontiguousarray(v, dtype=np.float32), ddim_steps, use_graph=use_graph,
+                                   prediction=prediction).cpu().numpy()
                   for v in (starts, goals))
     else:
         zs, zg = (diffusion_stochastic_encoder(v, sigmas, rng, dev, lo, num) for v in (starts, goals))
@@ -138,9 +158,10 @@ def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl,
         z = ((1 - alpha) * zs + alpha * zg).astype(np.float32)
         if ddim_steps:
             g, c, ld = ncsn.strided_dynamics(ld_rng, model, sigmas, z, ddim_steps, ddim_eta, use_graph=use_graph, sample_offset=lo,
-                                             global_num_samples=num, order=ddim_order, spacing=ddim_spacing)
+                                             global_num_samples=num, order=ddim_order, spacing=ddim_spacing, prediction=prediction)
         else:
-            g, c, ld = ncsn.diffusion_dynamics(ld_rng, model, sigmas, z, use_graph=use_graph, sample_offset=lo, global_num_samples=num)
+            g, c, ld = ncsn.diffusion_dynamics(ld_rng, model, sigmas, z, use_graph=use_graph, sample_offset=lo, global_num_samples=num,
+                                               prediction=prediction)
         gens.append(g.cpu().numpy())
         colls.append(c.cpu().numpy())
         log.info("Generated samples %i out of %i", i, points)
@@ -343,7 +364,8 @@ def compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world):
     rng = ncsn.split(ncsn.make_key(FLAGS.sample_seed, FLAGS.rng_impl), num=4)[3]
     t0 = time.time()
     out = ncsn.variational_bound(rng, model, sigmas, np.ascontiguousarray(real[lo:hi], dtype=np.float32), FLAGS.bound_steps,
-                                 sample_offset=lo, global_num_samples=len(real), use_graph=FLAGS.graph)
+                                 sample_offset=lo, global_num_samples=len(real), use_graph=FLAGS.graph,
+                                 prediction=_prediction(FLAGS))
     model.drop_sampler_cache()
     parts = [out]
     if world > 1:
@@ -353,7 +375,8 @@ def compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world):
     if rank != 0:
         return
     terms = np.concatenate([p["terms"] for p in parts], axis=1)
-    eps_mse = np.concatenate([p["eps_mse"] for p in parts], axis=1)
+    # sum (eps - out)^2 means nothing when the network's output is x0 or v: variational_bound then returns None for it
+    eps_mse = np.concatenate([p["eps_mse"] for p in parts], axis=1) if out["eps_mse"] is not None else None
     prior = np.concatenate([p["prior"] for p in parts])
     exact = out["total"] is not None
     total = np.concatenate([p["total"] for p in parts]) if exact else None
@@ -362,8 +385,10 @@ def compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world):
     bits = float(total.mean() / (per * np.log(2.0))) if exact else None
     summary = dict(nats_per_dim=nats, bits_per_dim=bits, total=float(total.mean()) if exact else None, prior=float(prior.mean()),
                    timesteps=[int(t) for t in out["timesteps"]], terms=[float(v) for v in terms.mean(axis=1)],
-                   eps_mse=[float(v) for v in eps_mse.mean(axis=1)], dtype=FLAGS.dtype, num_examples=int(len(real)), clip=1.0,
+                   eps_mse=None if eps_mse is None else [float(v) for v in eps_mse.mean(axis=1)], dtype=FLAGS.dtype, num_examples=int(len(real)), clip=1.0,
                    var_0=float(out["var_0"]), exact=bool(exact))
+    if out.get("prediction", "eps") != "eps":               # an x0 / v model says so (and has eps_mse: null); eps files are as ever
+        summary["prediction"] = out["prediction"]
     log_dir = FLAGS.sampling_dir
     os.makedirs(os.path.join(log_dir, "ncsn"), exist_ok=True)
     with open(os.path.join(log_dir, "ncsn/bound.json"), "w") as f:
@@ -403,6 +428,12 @@ def main(argv):
     check_ddim_flags(FLAGS)
     check_bound_flags(FLAGS)
     check_copy_flags(FLAGS)
+    try:
+        FLAGS.prediction = resolve_prediction_flag(FLAGS)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if rank == 0:
+        log.info("prediction: %s", FLAGS.prediction)
     torch.cuda.set_device(local_rank)
     dev = f"cuda:{local_rank}"
     if world > 1:
@@ -461,7 +492,8 @@ def main(argv):
         generated, collection, ld_metrics = interpolate_samples(model, sigmas, real, lo, hi, rng, FLAGS.sample_seed, FLAGS.rng_impl,
                                                                 dev, FLAGS.graph, ddim_steps=FLAGS.ddim_steps,
                                                                 ddim_eta=FLAGS.ddim_eta, ddim_encode=FLAGS.ddim_encode,
-                                                                ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing)
+                                                                ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing,
+                                                                prediction=FLAGS.prediction)
     else:                                                                   # :437-439
         generated, collection, ld_metrics = generate_samples(FLAGS, model, rng, shape, hi - lo, sigmas, sample_offset=lo,
                                                              global_num_samples=num)

@@ -144,6 +144,51 @@ def restore_timestep_sampler(ckpt_dir: str, sampler) -> bool:
     return True
 
 
+def checkpoint_train_options(ckpt_dir: str) -> Dict[str, str]:
+    """The string metadata of the newest checkpoint (``train_options`` of save_checkpoint among it); {} when there is no
+    checkpoint or it is a flax-format file, which has no place for any."""
+    path = ckpt_dir if os.path.isfile(ckpt_dir) else latest_checkpoint(ckpt_dir)
+    if path is None or flax_io.is_flax_file(path):
+        return {}
+    from safetensors import safe_open
+    with safe_open(path, framework="pt") as f:
+        return dict(f.metadata() or {})
+
+
+def checkpoint_prediction(ckpt_dir: str) -> Optional[str]:
+    """What the checkpoint's network predicts, "eps" / "x0" / "v" (DESIGN.md section 26), or None when the checkpoint does not say:
+    a flax-format file, or a safetensors file written before the field existed -- both are eps models unless the caller knows
+    better."""
+    return checkpoint_train_options(ckpt_dir).get("prediction") or None
+
+
+def resolve_prediction(flag: str, recorded: Optional[str], what: str = "the checkpoint") -> str:
+    """The kind to run with: ``flag`` is --prediction ("" = not given), ``recorded`` what ``checkpoint_prediction`` found.  A flag
+    that contradicts the record raises a ValueError -- sampling a v-trained network as eps produces noise without any error
+    further down; no record and no flag means eps."""
+    from .schedule import PREDICTIONS
+    for name, v in (("--prediction", flag), (what, recorded)):
+        if v and v not in PREDICTIONS:
+            raise ValueError(f"{name}: prediction must be one of {PREDICTIONS}, got {v!r}")
+    if flag and recorded and flag != recorded:
+        raise ValueError(f"--prediction={flag} contradicts {what}, which was trained with --prediction={recorded}: drop the flag "
+                         f"or pass --prediction={recorded}")
+    return flag or recorded or "eps"
+
+
+def check_resume_prediction(ckpt_dir: str, prediction: str) -> None:
+    """--resume with another --prediction than the run was trained with is refused (ValueError): the parameters would be trained
+    on towards another target.  A safetensors checkpoint without the field is an eps model; a flax-format file cannot say and is
+    taken at the caller's word; no checkpoint: nothing to check."""
+    path = ckpt_dir if os.path.isfile(ckpt_dir) else latest_checkpoint(ckpt_dir)
+    if path is None or flax_io.is_flax_file(path):
+        return
+    recorded = checkpoint_prediction(path) or "eps"
+    if recorded != prediction:
+        raise ValueError(f"--resume: {path} was trained with --prediction={recorded}, this run asks for --prediction={prediction}; "
+                         f"resume with --prediction={recorded} or start a new --model_dir")
+
+
 def load_ema_params(ckpt_dir: str, engine) -> bool:
     path = ckpt_dir if os.path.isfile(ckpt_dir) else latest_checkpoint(ckpt_dir)
     if path is None:

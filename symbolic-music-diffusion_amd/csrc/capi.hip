@@ -103,7 +103,19 @@ int smd_engine_set_option(smd_engine* e, const char* key, int value) {
   if (std::string(key) == "grad_memset") { e->impl.grad_memset = value; return 0; }
   if (std::string(key) == "tail_on_main") { e->impl.tail_on_main = value ? 1 : 0; return 0; }
   if (std::string(key) == "film_side_fwd") { e->impl.film_side_fwd = value ? 1 : 0; return 0; }
-  if (std::string(key) == "loss_kind") { e->impl.loss_kind = value ? 1 : 0; return 0; }
+  if (std::string(key) == "loss_kind") {
+    SMD_ARG_CHECK(!value || e->impl.prediction == 0, "set_option: loss_kind=1 (score matching) with prediction=%d: x0 / v "
+                  "prediction is defined for the DDPM objective only", e->impl.prediction);
+    e->impl.loss_kind = value ? 1 : 0;
+    return 0;
+  }
+  if (std::string(key) == "prediction") {      // 0 eps, 1 x0, 2 v; settable at any time
+    SMD_ARG_CHECK(value >= 0 && value <= 2, "set_option: prediction=%d (0 eps, 1 x0, 2 v)", value);
+    SMD_ARG_CHECK(value == 0 || !e->impl.loss_kind, "set_option: prediction=%d with loss_kind=1 (score matching): x0 / v "
+                  "prediction is defined for the DDPM objective only", value);
+    e->impl.prediction = value;
+    return 0;
+  }
   if (std::string(key) == "label_min") { e->impl.label_min = value ? 1 : 0; return 0; }
   if (std::string(key) == "mlp_hs") { e->impl.mlp_hs = value ? 1 : 0; return 0; }
   if (std::string(key) == "fp8" || std::string(key) == "fp32") return e->impl.set_precision_option(key, value);
@@ -165,6 +177,7 @@ int smd_engine_set_loss_weights(smd_engine* e, const float* iw, float min_snr_ga
   return 0;
 }
 const float* smd_engine_weight_per_sample(const smd_engine* e) { return e ? e->impl.weight_per_sample() : nullptr; }
+const float* smd_engine_noise_level_per_sample(const smd_engine* e) { return e ? e->impl.noise_levels() : nullptr; }
 int64_t smd_engine_debug_snapshot_bytes(const smd_engine* e) { return e ? e->impl.debug_snapshot_bytes() : -1; }
 int smd_engine_debug_snapshots(smd_engine* e, void* buf, int64_t bytes) {
   NEED(e);
@@ -657,6 +670,12 @@ int smd_weighted_mse_fwd_bwd(const float* pred, const float* eps, const float* n
                              float* weight_per_sample, smd_bf16* dpred_bf16, void* stream) {
   return launch_weighted_mse_loss_grad(pred, eps, noise_level, iw, min_snr_gamma, Bn, Sn, C, Cp, inv_global_count, loss_per_sample,
                                        weight_per_sample, B(dpred_bf16), S(stream));
+}
+int smd_param_mse_fwd_bwd(const float* pred, const float* eps, const float* x0, const float* noise_level, const float* iw,
+                          float min_snr_gamma, int kind, int Bn, int Sn, int C, int Cp, float inv_global_count,
+                          float* loss_per_sample, float* weight_per_sample, smd_bf16* dpred_bf16, void* stream) {
+  return launch_param_mse_loss_grad(pred, eps, x0, noise_level, iw, min_snr_gamma, kind, Bn, Sn, C, Cp, inv_global_count,
+                                    loss_per_sample, weight_per_sample, B(dpred_bf16), S(stream));
 }
 int smd_timestep_draw(const float* cdf, const float* p, int n, int label_base, int Bn, uint32_t seed_lo, uint32_t seed_hi,
                       uint32_t sample_offset, uint32_t step, const uint32_t* step_ptr, const float* u_in, int32_t* labels_out,

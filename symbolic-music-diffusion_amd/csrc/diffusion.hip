@@ -261,6 +261,66 @@ __global__ __launch_bounds__(1024) void weighted_mse_loss_grad_kernel(const floa
   }
 }
 
+// The weighted DDPM loss of a network that predicts x0 (KIND 1) or v = s eps - sb x0 (KIND 2) instead of eps (DESIGN.md
+// section 26): weighted_mse_loss_grad_kernel with the target formed per element from eps and the caller's x0, s = the noise
+// level q-sample stored, sb = sqrt((1 - s)(1 + s)) (1 - s is exact for s in [1/2, 2], as in loss_weight).  Same layout, walk and
+// reduction order; dpred = 2 w_b (out - target) / (Bg S C), loss_per_sample the UNWEIGHTED mean of (out - target)^2 and
+// weight_per_sample[b] = w_b.  The min-SNR-gamma weight of Hang et al. 2023 for these targets, with SNR = ap / (1 - ap):
+//   x0: min(SNR, gamma)               = min(ap / om, gamma)  -- ap = 1: min(inf, gamma) = gamma; ap = 0: 0
+//   v : min(SNR, gamma) / (SNR + 1)   = min(ap, gamma om)    -- ap = 1: 0; ap = 0: 0; no quotient at all
+// Label 1 has ap = 1 exactly, so the ap = 1 column is met in every run.  Without an SNR factor w_b = iw_b (1 when iw is null).
+template <int KIND>
+__device__ __forceinline__ float param_loss_weight(float s, float iw, float gamma, bool snr) {
+  if (!snr) return iw;
+  const float ap = s * s, om = (1.0f - s) * (1.0f + s);
+  return iw * (KIND == 1 ? fminf(ap / om, gamma) : fminf(ap, gamma * om));
+}
+template <int VEC, int KIND>
+__global__ __launch_bounds__(1024) void param_mse_loss_grad_kernel(const float* __restrict__ pred, const float* __restrict__ eps,
+                                                                   const float* __restrict__ x0, int S, int C, int Cp,
+                                                                   float inv_global_count,
+                                                                   const float* __restrict__ noise_level,
+                                                                   const float* __restrict__ iw, float gamma, int snr,
+                                                                   float* __restrict__ loss_per_sample,
+                                                                   float* __restrict__ weight_per_sample,
+                                                                   bf16_t* __restrict__ dpred) {
+  static_assert(KIND == 1 || KIND == 2, "eps-prediction keeps its own kernels");
+  __shared__ float red[16];
+  const int b = blockIdx.x, SC = S * C;
+  const float s = (KIND == 2 || snr) ? noise_level[b] : 1.0f;      // x0 without an SNR factor reads no noise level
+  const float sb = sqrtf((1.0f - s) * (1.0f + s));
+  const float w = param_loss_weight<KIND>(s, iw ? iw[b] : 1.0f, gamma, snr != 0);
+  const float gscale = (2.0f * inv_global_count) * w;
+  float acc = 0.f;
+  for (int e = threadIdx.x * VEC; e < SC; e += 1024 * VEC) {
+    float p[VEC], q[VEC], x[VEC];
+    ldv<VEC>(pred + (size_t)b * SC + e, p);
+    ldv<VEC>(x0 + (size_t)b * SC + e, x);
+    if constexpr (KIND == 2) ldv<VEC>(eps + (size_t)b * SC + e, q);
+    const int srow = e / C, c = e - srow * C;
+    float g[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      // (explicit fma: both instantiations round identically, as q-sample's x_t does)
+      const float target = KIND == 1 ? x[v] : __builtin_fmaf(s, q[v], -(sb * x[v]));
+      const float d = p[v] - target;
+      acc += d * d;
+      g[v] = d * gscale;
+    }
+    stv_bf16<VEC>(dpred + ((size_t)b * S + srow) * Cp + c, g);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t += red[i];
+    loss_per_sample[b] = t / (float)SC;
+    weight_per_sample[b] = w;
+  }
+}
+
 // ------------------------------------------------------------------ fused reverse step
 // One workgroup per sample: 128 column threads x RG row groups (RG = 4 for sequence states: four rows of every column
 // in flight instead of one; the per-column sums over the sequence axis are combined through LDS in a fixed order).
@@ -852,6 +912,34 @@ int launch_weighted_mse_loss_grad(const float* pred, const float* eps, const flo
   else
     hipLaunchKernelGGL(weighted_mse_loss_grad_kernel<1>, dim3(B), dim3(1024), 0, st, pred, eps, S, C, Cp, inv_global_count,
                        noise_level, iw, gamma, snr, loss_per_sample, weight_per_sample, dpred_bf16);
+  SMD_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_param_mse_loss_grad(const float* pred, const float* eps, const float* x0, const float* noise_level, const float* iw,
+                               float gamma, int kind, int B, int S, int C, int Cp, float inv_global_count, float* loss_per_sample,
+                               float* weight_per_sample, bf16_t* dpred_bf16, hipStream_t st) {
+  SMD_ARG_CHECK(kind >= 0 && kind <= 2, "param_mse_loss_grad: kind=%d (0 eps, 1 x0, 2 v)", kind);
+  if (kind == 0)
+    return launch_weighted_mse_loss_grad(pred, eps, noise_level, iw, gamma, B, S, C, Cp, inv_global_count, loss_per_sample,
+                                         weight_per_sample, dpred_bf16, st);
+  SMD_ARG_CHECK(pred && x0 && loss_per_sample && weight_per_sample && dpred_bf16 && B > 0 && S > 0 && C > 0 && Cp >= C,
+                "param_mse_loss_grad: bad arguments");
+  SMD_ARG_CHECK(kind != 2 || (eps && noise_level), "param_mse_loss_grad: the v target needs eps and the per-sample noise levels");
+  const int snr = gamma > 0.0f && gamma < __builtin_inff();      // gamma <= 0, +inf (and NaN): no SNR factor
+  SMD_ARG_CHECK(!snr || noise_level, "param_mse_loss_grad: gamma=%g needs the per-sample noise levels", (double)gamma);
+  const bool vec = C % 4 == 0 && Cp % 4 == 0;
+  SMD_ARG_CHECK(!vec || ((((uintptr_t)pred | (uintptr_t)eps | (uintptr_t)x0) & 15) == 0 && ((uintptr_t)dpred_bf16 & 7) == 0),
+                "param_mse_loss_grad: C=%d takes 16-byte loads: pred, eps and x0 must be 16-byte aligned (dpred 8-byte)", C);
+#define SMD_PARAM_MSE(VEC, KIND)                                                                                                  \
+  hipLaunchKernelGGL((param_mse_loss_grad_kernel<VEC, KIND>), dim3(B), dim3(1024), 0, st, pred, eps, x0, S, C, Cp, inv_global_count, \
+                     noise_level, iw, gamma, snr, loss_per_sample, weight_per_sample, dpred_bf16)
+  if (kind == 1) {
+    if (vec) SMD_PARAM_MSE(4, 1); else SMD_PARAM_MSE(1, 1);
+  } else {
+    if (vec) SMD_PARAM_MSE(4, 2); else SMD_PARAM_MSE(1, 2);
+  }
+#undef SMD_PARAM_MSE
   SMD_LAUNCH_CHECK();
   return 0;
 }

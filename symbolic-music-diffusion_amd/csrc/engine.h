@@ -189,6 +189,11 @@ class SmdEngine {
   void set_loss_weights(const float* iw, float gamma) { loss_iw_ = iw; min_snr_gamma_ = gamma; }
   bool loss_weighted() const { return loss_iw_ != nullptr || min_snr_gamma_ > 0.0f; }
   const float* weight_per_sample() const { return W.loss_weight; }
+  // What the network's output means to the DDPM objective: 0 eps (the reference), 1 x0, 2 v =
+  // s eps - sqrt(1 - s^2) x0.  0 launches the two eps kernels as ever; 1 and 2 launch param_mse_loss_grad_kernel, always the
+  // weighted form (it fills weight_per_sample(); without weights every w_b is exactly 1).  The samplers and the bound take the
+  // kind through their coefficient tables (schedule.py), not from here.
+  int prediction = 0;
   // Debugging aid (tools/det_first_diff.py): when a buffer is set, backward_stem copies the state of the SHARED, per-layer
   // overwritten gradient buffers behind every encoder-layer kernel into it (per layer, in execution order: da2 partial
   // tiles after mlp_hs_bwd, dh after the ln2 backward, dA_E after attn_block_bwd, dh after the ln1 backward; plus the layer's

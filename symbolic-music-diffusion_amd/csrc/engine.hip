@@ -1182,7 +1182,11 @@ int SmdEngine::loss_backward(const float* x0, const int* labels, const float* ep
     q.xt_bf16 = W.x_bf16; q.eps_out = W.eps; q.s_out = W.s;
     RC(launch_q_sample(q, st));
     RC(run_network(nullptr, st));
-    if (loss_weighted()) {
+    if (prediction != 0) {
+      SMD_ARG_CHECK(!loss_kind, "loss_backward: prediction=%d (x0 / v) applies to the DDPM objective only", prediction);
+      RC(launch_param_mse_loss_grad(W.pred, W.eps, x0, W.s, loss_iw_, min_snr_gamma_, prediction, batch_, S, C, Cp_,
+                                    inv_global_count, W.loss, W.loss_weight, W.dpred, st));
+    } else if (loss_weighted()) {
       SMD_ARG_CHECK(!loss_kind, "loss_backward: loss weights (set_loss_weights) apply to the DDPM objective only");
       RC(launch_weighted_mse_loss_grad(W.pred, W.eps, W.s, loss_iw_, min_snr_gamma_, batch_, S, C, Cp_, inv_global_count, W.loss,
                                        W.loss_weight, W.dpred, st));

@@ -279,6 +279,13 @@ int launch_weighted_mse_loss_grad(const float* pred, const float* eps, const flo
                                   int B, int S, int C, int Cp, float inv_global_count, float* loss_per_sample,
                                   float* weight_per_sample, bf16_t* dpred_bf16, hipStream_t st);
 
+// the same for a network that predicts x0 (kind 1: target x0, w_b = iw_b min(SNR, gamma)) or v (kind 2: target s eps - sb x0,
+// sb = sqrt((1 - s)(1 + s)), w_b = iw_b min(s^2, gamma (1 - s^2))) -- DESIGN.md section 26; x0 [B][S][C] fp32.  kind 0 forwards to
+// launch_weighted_mse_loss_grad.  eps may be null for kind 1, noise_level for kind 1 without an SNR factor.
+int launch_param_mse_loss_grad(const float* pred, const float* eps, const float* x0, const float* noise_level, const float* iw,
+                               float gamma, int kind, int B, int S, int C, int Cp, float inv_global_count, float* loss_per_sample,
+                               float* weight_per_sample, bf16_t* dpred_bf16, hipStream_t st);
+
 // ------------------------------------------------------------------ loss-aware timestep sampler (timestep.hip)
 // labels_out[b] = label_base + (first i with cdf[i] > u_b), iw_out[b] = 1 / (n p[i]); u_b from u_in or the Philox stream
 // SMD_STREAM_TIMESTEP keyed by (seed, b + sample_offset, step); step_ptr (device, nullable) replaces `step`

@@ -127,6 +127,7 @@ class Engine:
         self._label_min = 1
         self._loss_kind = 0
         self._loss_weighted = False  # the handle holds loss weights other than (NULL, 0)
+        self.prediction = "eps"      # what the network's output means: eps / x0 / v (set_prediction)
         self.generation = 0         # bumped by whatever invalidates a captured step of this handle: bind, schedule, options
         self.grads = self.m = self.v = self.ema = None
         self.step_counter = None
@@ -221,9 +222,35 @@ class Engine:
             self._wseen = self._wstate["ver"]
 
     def set_option(self, key: str, value: int) -> None:
+        if key == "prediction":          # the kind also lives in this object's tables and cache keys: one way to change it
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) < len(_sched.PREDICTIONS):
+                raise ValueError(f"set_option: prediction={value!r} (0 eps, 1 x0, 2 v)")
+            self.set_prediction(int(value))
+            return
+        if key == "loss_kind" and int(value) and self.prediction != "eps":
+            raise ValueError(f"set_option: loss_kind=1 (score matching) with prediction={self.prediction!r}: x0 / v prediction is "
+                             "defined for the DDPM objective only")
         _lib.check(self.L.smd_engine_set_option(self.h, key.encode(), int(value)), "set_option")
         if key != "w8_dirty":
             self.generation += 1
+
+    def set_prediction(self, prediction) -> None:
+        """What the network's output means, "eps" (the reference), "x0" or "v" (DESIGN.md section 26): the handle's option
+        "prediction" -- the target and SNR weight of loss_backward -- and the first two columns of the bound reverse-step
+        table, which is rebuilt when the kind changes.  loss_backward refuses objective="dsm" with a kind other than eps."""
+        kind = _sched.prediction_kind(prediction)
+        name = _sched.PREDICTIONS[kind]
+        if name == self.prediction:
+            return
+        if kind != 0 and self._loss_kind != 0:
+            # the objective is chosen per loss_backward call (which refuses 'dsm' with this kind): back to the DDPM loss first
+            _lib.check(self.L.smd_engine_set_option(self.h, b"loss_kind", 0), "set_option loss_kind")
+            self._loss_kind = 0
+        _lib.check(self.L.smd_engine_set_option(self.h, b"prediction", kind), "set_option prediction")
+        self.prediction = name
+        self.generation += 1
+        if self.betas is not None:
+            self.set_schedule(self.betas, with_sampler=self._sched_tensors["film"] is not None)
 
     def _join_foreign_pending(self) -> None:
         """A deferred output-stage update of ANOTHER handle on these parameters (opt_overlap bit 0) must be complete before
@@ -239,7 +266,7 @@ class Engine:
             raise ValueError(f"schedule has {len(betas)} steps, model built for {self.cfg.num_timesteps}")
         self.betas = betas
         self.generation += 1
-        coef = _sched.reverse_coefficient_table(betas)
+        coef = _sched.reverse_coefficient_table(betas, self.prediction)
         ape = np.concatenate([np.ones(1, np.float32), _sched.alphas_cumprod(betas)])
         dev = self.device
         t = dict(coef=torch.from_numpy(coef).to(dev), sqrt_ap=torch.from_numpy(np.ascontiguousarray(coef[:, 6])).to(dev),
@@ -325,14 +352,20 @@ class Engine:
                       eps: Optional[torch.Tensor] = None, seed: int = 0, sample_offset: int = 0,
                       global_batch: Optional[int] = None, stage: int = 0, *, used_alphas: Optional[torch.Tensor] = None,
                       continuous_noise: bool = True, objective: str = "ddpm", loss_weights: Optional[torch.Tensor] = None,
-                      min_snr_gamma: float = 0.0) -> None:
+                      min_snr_gamma: float = 0.0, prediction=None) -> None:
         """``continuous_noise=False``: labels in [0, T) (utils/losses.py:272-275) and a real uniform used_alpha for label 0;
         ``used_alphas`` ([B] floats) passes the draws of :283-286 explicitly.  ``objective="dsm"``: the denoising
         score-matching loss (:129-179) on the same network; ``used_alphas`` then carries the per-sample used_sigmas.
         ``loss_weights`` ([B] floats) / ``min_snr_gamma`` > 0: the weighted DDPM loss (include/smd_hip.h
-        smd_engine_set_loss_weights); the defaults run the unweighted kernel."""
+        smd_engine_set_loss_weights); the defaults run the unweighted kernel.  ``prediction`` ("eps" / "x0" / "v"): calls
+        ``set_prediction`` first; None keeps the handle's kind.  A kind other than eps is refused with ``objective="dsm"``."""
         B = x0.shape[0] if x0 is not None else self.batch
         kind = {"ddpm": 0, "dsm": 1}[objective]
+        if kind != 0 and _sched.prediction_kind(self.prediction if prediction is None else prediction) != 0:
+            raise ValueError(f"prediction={self.prediction if prediction is None else prediction!r} applies to objective='ddpm' "
+                             f"only, got objective={objective!r}")
+        if prediction is not None:
+            self.set_prediction(prediction)
         weighted = loss_weights is not None or float(min_snr_gamma) > 0.0
         if weighted and kind != 0:
             raise ValueError("loss weights (loss_weights / min_snr_gamma) apply to the DDPM objective only")
@@ -443,6 +476,10 @@ class Engine:
     def weight_per_sample(self) -> torch.Tensor:
         """The per-sample weights of the last WEIGHTED loss_backward (include/smd_hip.h smd_engine_weight_per_sample)."""
         return self._borrow(self.L.smd_engine_weight_per_sample(self.h), (self.batch,))
+
+    def noise_level_per_sample(self) -> torch.Tensor:
+        """The noise levels sqrt(used alpha) of the last loss_backward's q-sample (smd_engine_noise_level_per_sample)."""
+        return self._borrow(self.L.smd_engine_noise_level_per_sample(self.h), (self.batch,))
 
     def last_pred(self) -> torch.Tensor:
         return self._borrow(self.L.smd_engine_pred(self.h), (self.batch, *self.cfg.sample_shape))

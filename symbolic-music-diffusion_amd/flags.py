@@ -294,6 +294,21 @@ ENGINE_FLAGS: List[FlagDef] = [
 ]
 
 
+_PREDICTION_HELP = ("--loss=ddpm / --sampling=ddpm: what the network's output means, eps (the reference), x0, or "
+                    "v = sqrt(ap) eps - sqrt(1 - ap) x0 (Salimans & Ho 2022; DESIGN.md section 26).  train_ncsn trains towards that "
+                    "target (with --loss_weighting=min_snr: that kind's weight) and records the kind in a safetensors checkpoint; "
+                    "--resume refuses another kind.  sample_ncsn: empty = what the checkpoint says, else eps; a value that "
+                    "contradicts the checkpoint is refused.  --ckpt_format=flax has no place for the kind: the flag is then "
+                    "REQUIRED to sample an x0 or v model.  The training log of an x0 / v run adds loss_eps, its unweighted loss in eps "
+                    "units: compare it with an eps run's loss_unweighted (without --loss_weighting: its loss).")
+
+
+def prediction_flag(include_sample: bool) -> FlagDef:
+    """--prediction: an enum over eps, x0, v whose default is eps for train_ncsn and empty for sample_ncsn."""
+    return _D("prediction", "enum", "" if include_sample else "eps", _PREDICTION_HELP,
+              ("", "eps", "x0", "v") if include_sample else ("eps", "x0", "v"))
+
+
 def make_flags(include_sample: bool = False) -> FlagValues:
-    defs = list(TRAIN_FLAGS) + (list(SAMPLE_FLAGS) if include_sample else []) + list(ENGINE_FLAGS)
+    defs = list(TRAIN_FLAGS) + (list(SAMPLE_FLAGS) if include_sample else []) + list(ENGINE_FLAGS) + [prediction_flag(include_sample)]
     return FlagValues(defs)

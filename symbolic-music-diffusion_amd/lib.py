@@ -134,6 +134,7 @@ _SIGS = {
     "smd_engine_set_used_alphas": (C.c_int, [c_void, c_void]),
     "smd_engine_set_loss_weights": (C.c_int, [c_void, c_void, C.c_float]),
     "smd_engine_weight_per_sample": (c_void, [c_void]),
+    "smd_engine_noise_level_per_sample": (c_void, [c_void]),
     "smd_engine_forward_train": (C.c_int, [c_void] * 5),
     "smd_engine_backward_from": (C.c_int, [c_void, c_void, C.c_int, c_void]),
     "smd_engine_debug_snapshot_bytes": (c_i64, [c_void]),
@@ -214,6 +215,8 @@ _SIGS = {
     "smd_mse_fwd_bwd": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void]),
     "smd_weighted_mse_fwd_bwd": (C.c_int, [c_void, c_void, c_void, c_void, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                            c_void, c_void, c_void, c_void]),
+    "smd_param_mse_fwd_bwd": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_float, c_void, c_void, c_void, c_void]),
     "smd_timestep_draw": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_u32, c_u32, c_u32, c_u32, c_void, c_void, c_void,
                                     c_void, c_void]),
     "smd_timestep_update": (C.c_int, [c_void, c_void, C.c_int, c_void, c_void, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void,

@@ -238,16 +238,21 @@ def reduce_fn(x, mode):
     raise ValueError("Unsupported reduction option.")
 
 
-def _ensure_schedule(engine: Engine, betas, with_sampler: bool) -> None:
+def _ensure_schedule(engine: Engine, betas, with_sampler: bool, prediction="eps") -> None:
+    """The handle's schedule tables for ``betas`` and the kind ``prediction`` of the network's output (the
+    kind lives in the first two columns of the reverse-step table and in the handle's loss)."""
     betas = np.asarray(betas, dtype=np.float32)
+    engine.set_prediction(prediction)                # rebuilds a bound table itself when the kind changes
     need_film = with_sampler and (engine._sched_tensors is None or engine._sched_tensors["film"] is None)
     if engine.betas is None or need_film or not np.array_equal(engine.betas, betas):
         engine.set_schedule(betas, with_sampler=with_sampler)
 
 
 def diffusion_loss(batch, model: Model, betas, rng: PRNGKey, continuous_noise=False, reduction="mean", *,
-                   labels=None, eps=None, used_alphas=None):
+                   labels=None, eps=None, used_alphas=None, prediction="eps"):
     """utils/losses.py:250-308 (forward only; the training step fuses it with the backward).
+    ``prediction`` "x0" / "v": the loss of a network that predicts x0 / v = sqrt(ap) eps - sqrt(1 - ap) x0, in that output's space
+    (no reference counterpart).
     ``labels`` / ``eps`` pass the draws of :272-275 / :294 explicitly (parity mode); otherwise they
     come from the engine's Philox streams keyed by ``rng`` (or, with a ThreefryKey, are the reference's own).
     continuous_noise only moves the label range (:272-275): True -> [1, T], every uniform of :283-286 degenerates to its
@@ -255,7 +260,7 @@ def diffusion_loss(batch, model: Model, betas, rng: PRNGKey, continuous_noise=Fa
     ``used_alphas`` passes those draws explicitly.  (The discrete-conditioning branch itself is commented out upstream.)"""
     eng = model.train_engine(ema=False)
     batch = torch.as_tensor(batch).to(eng.device, torch.float32).contiguous()
-    _ensure_schedule(eng, betas, with_sampler=False)
+    _ensure_schedule(eng, betas, with_sampler=False, prediction=prediction)
     eng.bind(batch.shape[0], training=True)
     lab = None if labels is None else torch.as_tensor(labels).to(eng.device, torch.int32).contiguous()
     e = None if eps is None else torch.as_tensor(eps).to(eng.device, torch.float32).contiguous()
@@ -706,8 +711,11 @@ def _graph_walk(model: "Model", dev, chains: list, replays: int, unroll: int, re
 def diffusion_dynamics(rng: PRNGKey, model: Model, betas, init, epsilon=None, T=None, denoise=None, infill=False,
                        infill_samples=None, infill_masks=None, *, noises: Optional[Callable] = None,
                        infill_noises: Optional[Callable] = None, t_start: Optional[int] = None, t_stop: int = 0,
-                       use_graph: bool = True, sample_offset: int = 0, global_num_samples: Optional[int] = None):
+                       use_graph: bool = True, sample_offset: int = 0, global_num_samples: Optional[int] = None,
+                       prediction="eps"):
     """utils/ebm_utils.py:280-405.  Returns (state, collection (41, ...), ld_metrics (4, T, 1)).
+    ``prediction`` "x0" / "v": the network's output is x0 / v, and the reverse-step table turns it into x0 (DESIGN.md section
+    26); the metrics row ``grad`` stays the norm of the network's OUTPUT, as in the reference -- under v it is |v_hat|.
 
     epsilon / T / denoise are null parameters as in the reference.  ``noises(t)`` /
     ``infill_noises(t)`` supply the normal draws of :360-362 / :342-345 explicitly (parity mode);
@@ -773,7 +781,7 @@ def diffusion_dynamics(rng: PRNGKey, model: Model, betas, init, epsilon=None, T=
         zp = lambda t: None if t is None else torch.cat([t, torch.zeros((pad, *t.shape[1:]), dtype=t.dtype, device=dev)])
         x, start, inf_s, inf_m = zp(x), zp(start), zp(inf_s), zp(inf_m)
     for c, e in enumerate(engines):
-        _ensure_schedule(e, betas, with_sampler=True)
+        _ensure_schedule(e, betas, with_sampler=True, prediction=prediction)
         e.bind(sizes[c], training=False)
     # A captured step is valid for LATER runs too as long as every pointer it holds is: the state / collection / metrics
     # buffers, the device-resident timestep, Philox key (smd_sample_io.key_ptr) and jax.random key tables are kept with the
@@ -884,7 +892,7 @@ def diffusion_dynamics(rng: PRNGKey, model: Model, betas, init, epsilon=None, T=
 def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], coef: np.ndarray, plan: np.ndarray, walk_key: tuple, *,
                   collect: bool, infill: bool = False, infill_samples=None, infill_masks=None, noises: Optional[Callable] = None,
                   infill_noises: Optional[Callable] = None, use_graph: bool = True, one_chain: bool = False, sample_offset: int = 0,
-                  global_num_samples: Optional[int] = None, multistep: bool = False):
+                  global_num_samples: Optional[int] = None, multistep: bool = False, prediction="eps"):
     """A table-driven walk over the timesteps ``order`` (smd_engine_strided_step) in the arrangement of diffusion_dynamics:
     eager launches with explicit draws, else one graph-replayed chain, else (B >= 128, bf16 / fp8) the pipelined pair.  Its
     cached graphs and persistent buffers live in their own ``slot`` of the model's sampler cache, beside diffusion_dynamics'
@@ -930,7 +938,7 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
         zp = lambda t: None if t is None else torch.cat([t, torch.zeros((pad, *t.shape[1:]), dtype=t.dtype, device=dev)])
         x, start, inf_s, inf_m = zp(x), zp(start), zp(inf_s), zp(inf_m)
     for c, e in enumerate(engines):
-        _ensure_schedule(e, betas, with_sampler=True)
+        _ensure_schedule(e, betas, with_sampler=True, prediction=prediction)       # (``coef`` carries the kind for the walk itself)
         e.bind(sizes[c], training=False)
     sig = tuple((id(e), e.generation) for e in engines) + (_lib.tuning_epoch(),)
     ckey = (walk_key, B, tuple(sizes), pad, nchains, unroll, bool(infill), jax_mode, nT, int(sample_offset), int(n_glob),
@@ -1050,7 +1058,7 @@ def _walk_ld_metrics(model: Model, betas, taus, mp):
 def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, infill=False, infill_samples=None,
                      infill_masks=None, *, noises: Optional[Callable] = None, infill_noises: Optional[Callable] = None,
                      use_graph: bool = True, sample_offset: int = 0, global_num_samples: Optional[int] = None, order: int = 1,
-                     spacing: str = "uniform"):
+                     spacing: str = "uniform", prediction="eps"):
     """The generalised non-Markovian sampler of Song et al. 2021 (DDIM) on ``steps`` evenly spaced timesteps of the schedule
     (schedule.stride_timesteps) instead of all of them: ``steps`` network evaluations from the same checkpoint.  ``eta`` scales
     the noise of every iteration (0: deterministic, 1: the DDPM posterior's variance).  Returns (state, collection (41, ...),
@@ -1064,8 +1072,10 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
     fewer than ``steps`` of them.  Order 2 walks with smd_engine_multistep_step and keeps its graphs in the cache slot
     "multistep", keyed by (iterations, order, spacing) AND the timesteps themselves: on the lambda grid two values of ``steps``
     can snap to the same number of iterations on different timesteps.  Order 1 on the lambda grid keys its "strided" entry the
-    same way; the defaults are the strided walk, and its key, as they were."""
+    same way; the defaults are the strided walk, and its key, as they were.
+    ``prediction`` "x0" / "v": the tables' first two columns are that kind's (section 26); a non-eps kind is part of the cache key."""
     nT = len(betas)
+    pk = () if _sched.prediction_kind(prediction) == 0 else (("prediction", _sched.prediction_kind(prediction)),)
     if order not in (1, 2):
         raise ValueError(f"order={order}: 1 (DDIM) or 2 (DPM-Solver++(2M))")
     if spacing not in ("uniform", "logsnr"):
@@ -1075,35 +1085,37 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
     taus = _sched.stride_timesteps(nT, steps) if spacing == "uniform" else _sched.logsnr_timesteps(nT, steps, betas)
     walk = [int(t) for t in taus]
     kw = dict(collect=True, infill=infill, infill_samples=infill_samples, infill_masks=infill_masks, noises=noises,
-              infill_noises=infill_noises, use_graph=use_graph, sample_offset=sample_offset, global_num_samples=global_num_samples)
+              infill_noises=infill_noises, use_graph=use_graph, sample_offset=sample_offset, global_num_samples=global_num_samples,
+              prediction=prediction)
     if order == 1:                                       # the strided update on either grid; the default key is the one it had
-        coef, plan = _sched.strided_coefficient_table(betas, taus, eta)
+        coef, plan = _sched.strided_coefficient_table(betas, taus, eta, prediction=prediction)
         # on the lambda grid the number of iterations does not name the timesteps (K = 19 and K = 20 both snap to 18): the key
         # carries the walk itself, because a reused entry keeps its device tables
-        key = ("strided", len(walk), float(eta)) + ((spacing, tuple(walk)) if spacing != "uniform" else ())
+        key = ("strided", len(walk), float(eta)) + ((spacing, tuple(walk)) if spacing != "uniform" else ()) + pk
         x, collection, mp = _strided_walk("strided", rng, model, betas, init, walk, coef, plan, key, **kw)
     else:
-        coef, plan = _sched.multistep_coefficient_table(betas, taus, order)
+        coef, plan = _sched.multistep_coefficient_table(betas, taus, order, prediction=prediction)
         x, collection, mp = _strided_walk("multistep", rng, model, betas, init, walk, coef, plan,
-                                          ("multistep", len(walk), int(order), spacing, tuple(walk)), multistep=True, **kw)
+                                          ("multistep", len(walk), int(order), spacing, tuple(walk)) + pk, multistep=True, **kw)
     return x, collection, _walk_ld_metrics(model, betas, taus, mp)
 
 
-def ddim_encode(model: Model, betas, x0, steps, *, use_graph: bool = True):
+def ddim_encode(model: Model, betas, x0, steps, *, use_graph: bool = True, prediction="eps"):
     """The deterministic encoder of the strided sampler: the same update walked UP the ``steps`` timesteps with sigma = 0 (DDIM
     inversion), ``steps - 1`` network evaluations, one chain, no noise and no collection.  Returns the latent at level T - 1,
     which ``strided_dynamics(..., steps, eta=0)`` decodes again up to the discretisation error of the two walks."""
     nT = len(betas)
     taus = _sched.stride_timesteps(nT, steps)
-    coef, plan = _sched.inversion_coefficient_table(betas, taus)
+    coef, plan = _sched.inversion_coefficient_table(betas, taus, prediction=prediction)
     order = sorted(int(t) for t in taus)[:-1]
-    x, _, _ = _strided_walk("encode", PRNGKey(0), model, betas, x0, order, coef, plan, ("encode", len(order)), collect=False,
-                            use_graph=use_graph, one_chain=True)
+    pk = () if _sched.prediction_kind(prediction) == 0 else (("prediction", _sched.prediction_kind(prediction)),)
+    x, _, _ = _strided_walk("encode", PRNGKey(0), model, betas, x0, order, coef, plan, ("encode", len(order)) + pk, collect=False,
+                            use_graph=use_graph, one_chain=True, prediction=prediction)
     return x
 
 
 def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip: float = 1.0, eps_in=None, sample_offset: int = 0,
-                      global_num_samples: Optional[int] = None, use_graph: bool = True) -> dict:
+                      global_num_samples: Optional[int] = None, use_graph: bool = True, prediction="eps") -> dict:
     """The variational bound of Ho et al. 2020 (eq. 5) on the examples ``batch`` (model space), term by term: no reference
     counterpart.  ``steps`` = 0: every timestep, the bound itself; else the terms at
     ``schedule.stride_timesteps(T, steps)`` only -- the curve, no total (no stride estimates the sum honestly).  One eps-net
@@ -1113,7 +1125,9 @@ def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip
     ``normal(split(rng, T)[t], (N_global, ...))``, this rank's window starting at ``sample_offset``: sharded callers get the
     single-process values.  Returns ``timesteps`` (ascending), ``terms`` / ``eps_mse`` [K][N] float64 (nats per example;
     mean squared error of eps_hat), ``prior`` [N], ``total`` [N] or None, ``nats_per_dim`` / ``bits_per_dim`` (means over the
-    examples, or None) and ``var_0``.  The t = 0 term is a DENSITY of continuous latents, so it -- and the total -- is negative."""
+    examples, or None) and ``var_0``.  ``prediction`` "x0" / "v": columns 2 / 3 of the table turn the network's output into x0, so
+    every term is right; the second sum is sum (eps - out)^2, which means nothing for those kinds: ``eps_mse`` is then None and the
+    result carries ``prediction``.  The t = 0 term is a DENSITY of continuous latents, so it -- and the total -- is negative."""
     eng = model.engine
     dev = eng.device
     x0 = torch.as_tensor(batch).to(dev, torch.float32).contiguous()
@@ -1123,7 +1137,8 @@ def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip
     nT = len(betas)
     steps = int(steps)
     ts = np.arange(nT) if steps == 0 else _sched.stride_timesteps(nT, steps)
-    tab = _sched.bound_tables(betas, ts, clip)
+    kind = _sched.prediction_kind(prediction)
+    tab = _sched.bound_tables(betas, ts, clip, prediction=prediction)
     order = [int(t) for t in tab["timesteps"]]
     K = len(order)
     per = int(np.prod(x0.shape[1:]))
@@ -1131,10 +1146,10 @@ def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip
     jax_mode = isinstance(rng, ThreefryKey) and not explicit
     graphed = use_graph and not explicit and K > 1
     n_glob = (B + sample_offset if global_num_samples is None else int(global_num_samples)) * per
-    _ensure_schedule(eng, betas, with_sampler=True)
+    _ensure_schedule(eng, betas, with_sampler=True, prediction=prediction)
     eng.bind(B, training=False)
     sig = ((id(eng), eng.generation), _lib.tuning_epoch())
-    ckey = (tuple(order), float(clip), B, jax_mode, nT, int(sample_offset), int(n_glob), tuple(x0.shape[1:]))
+    ckey = (tuple(order), float(clip), B, jax_mode, nT, int(sample_offset), int(n_glob), tuple(x0.shape[1:])) + ((kind,) if kind else ())
     cache = model.__dict__.setdefault("_sampler_graphs", {})
     entry = cache.get("bound") if graphed else None
     reuse = entry is not None and entry["key"] == ckey and entry["sig"] == sig
@@ -1187,20 +1202,27 @@ def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip
         for _ in order:
             step(entry["chains"][0])
     sums = entry["partial"][torch.tensor(order, device=dev)].double().cpu().numpy()          # [K][B][3] (q, e, n)
-    return _sched.bound_from_sums(tab, sums, per)
+    out = _sched.bound_from_sums(tab, sums, per)
+    out["prediction"] = _sched.PREDICTIONS[kind]
+    if kind != 0:
+        out["eps_mse"] = None
+    return out
 
 
 def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400, sampling="ald", epsilon=1e-3,
            steps=100, denoise=True, *, sample_offset: int = 0, use_graph: bool = True,
            global_num_samples: Optional[int] = None, ddim_steps: int = 0, ddim_eta: float = 0.0, ddim_order: int = 1,
-           ddim_spacing: str = "uniform"):
+           ddim_spacing: str = "uniform", prediction="eps"):
     """train_ncsn.py:499-551.  'ddpm': N(0,1) init + diffusion_dynamics.  'ald' / 'cas': uniform(-sqrt(12)/2, sqrt(12)/2)
     init (:542-547) + annealed / consistent Langevin dynamics with the score network ``scorenet``.  The reference unpacks
     three values from every sampler although consistent_langevin_dynamics returns two (a ValueError upstream); here 'cas'
     returns a two-entry collection [init, final state].  ``ddim_steps`` > 0 ('ddpm' only): the same initialisation, then the
-    strided walk ``strided_dynamics(..., ddim_steps, ddim_eta, order=ddim_order, spacing=ddim_spacing)`` instead of every timestep."""
+    strided walk ``strided_dynamics(..., ddim_steps, ddim_eta, order=ddim_order, spacing=ddim_spacing)`` instead of every timestep.
+    ``prediction`` "x0" / "v" ('ddpm' only): what the network's output means."""
     if sampling not in ("ddpm", "ald", "cas"):
         raise ValueError(f"Unknown sampling algorithm: {sampling}")
+    if sampling != "ddpm" and _sched.prediction_kind(prediction) != 0:
+        raise ValueError(f"prediction={prediction!r} is a DDPM option: the Langevin samplers ('ald', 'cas') take a score network")
     if ddim_steps and sampling != "ddpm":
         raise ValueError("ddim_steps is a DDPM option: sampling must be 'ddpm'")
     init_rng, ld_rng = split(rng)                                                    # :536
@@ -1240,9 +1262,9 @@ def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400
         generated, collection, ld_metrics = strided_dynamics(ld_rng, scorenet, sigmas, init, ddim_steps, ddim_eta,
                                                              sample_offset=sample_offset, use_graph=use_graph,
                                                              global_num_samples=global_num_samples, order=ddim_order,
-                                                             spacing=ddim_spacing)
+                                                             spacing=ddim_spacing, prediction=prediction)
         return generated, collection, collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = diffusion_dynamics(ld_rng, scorenet, sigmas, init, epsilon, steps, denoise,
                                                            False, sample_offset=sample_offset, use_graph=use_graph,
-                                                           global_num_samples=global_num_samples)
+                                                           global_num_samples=global_num_samples, prediction=prediction)
     return generated, collection, collate_sampling_metrics(ld_metrics.cpu().numpy())

@@ -16,6 +16,7 @@ tensors out, launched on torch's current HIP stream; fake-tensor (meta) rules ar
   smd_amd::bound_terms(x0, eps, eps_hat, table, t, clip)   its three per-example sums [B][3]
   smd_amd::timestep_draw(cdf, p, u, label_base)         loss-aware timestep labels and importance weights (DESIGN.md 25)
   smd_amd::weighted_mse(pred, eps, s, iw, gamma, inv)   the weighted DDPM loss and its gradient w.r.t. pred
+  smd_amd::param_mse(pred, eps, x0, s, iw, gamma, kind, inv)   the same for an x0- / v-predicting network (DESIGN.md 26)
 
 ``engine`` is the integer id of a live ``smd_amd.engine.Engine`` (``register_engine``); custom-op schemas carry tensors
 and scalars only.
@@ -288,6 +289,42 @@ def weighted_mse(pred: torch.Tensor, eps: torch.Tensor, noise_level: torch.Tenso
 
 @weighted_mse.register_fake
 def _(pred, eps, noise_level, iw, min_snr_gamma, inv_global_count):
+    B = pred.shape[0]
+    rows = B if pred.dim() == 2 else B * pred.shape[1]
+    return (pred.new_empty((B,), dtype=torch.float32), pred.new_empty((B,), dtype=torch.float32),
+            pred.new_empty((rows, pred.shape[-1]), dtype=torch.bfloat16))
+
+
+# ---- x0- / v-parameterised training
+@torch.library.custom_op("smd_amd::param_mse", mutates_args=())
+def param_mse(pred: torch.Tensor, eps: torch.Tensor, x0: torch.Tensor, noise_level: torch.Tensor, iw: torch.Tensor,
+              min_snr_gamma: float, kind: int, inv_global_count: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(loss_per_sample [B] unweighted, weight_per_sample [B], dpred bf16 [B*S][C]) of the weighted DDPM loss of a network that
+    predicts eps (kind 0), x0 (1) or v = s eps - sqrt(1 - s^2) x0 (2): dpred = 2 w (pred - target) inv_global_count with the
+    targets and weights of include/smd_hip.h smd_engine_set_loss_weights (smd_param_mse_fwd_bwd)."""
+    _need_gpu(pred, eps, x0, noise_level, iw)
+    if pred.dtype != torch.float32 or eps.dtype != torch.float32 or x0.dtype != torch.float32 or eps.shape != pred.shape \
+            or x0.shape != pred.shape or pred.dim() not in (2, 3):
+        raise ValueError("param_mse: pred, eps, x0 fp32 (B, S, C) or (B, C) tensors of one shape")
+    if int(kind) not in (0, 1, 2):
+        raise ValueError(f"param_mse: kind={kind} (0 eps, 1 x0, 2 v)")
+    B, S, Cn = _bsc(pred)
+    if noise_level.dtype != torch.float32 or iw.dtype != torch.float32 or noise_level.numel() != B or iw.numel() != B:
+        raise ValueError("param_mse: noise_level, iw fp32 [B]")
+    pred, eps, x0, noise_level, iw = pred.contiguous(), eps.contiguous(), x0.contiguous(), noise_level.contiguous(), iw.contiguous()
+    loss = torch.empty((B,), dtype=torch.float32, device=pred.device)
+    w = torch.empty_like(loss)
+    dpred = torch.empty((B * S, Cn), dtype=torch.bfloat16, device=pred.device)
+    with torch.cuda.device(pred.device):
+        _lib.check(_lib.get_lib().smd_param_mse_fwd_bwd(pred.data_ptr(), eps.data_ptr(), x0.data_ptr(), noise_level.data_ptr(),
+                                                        iw.data_ptr(), float(min_snr_gamma), int(kind), B, S, Cn, Cn,
+                                                        float(inv_global_count), loss.data_ptr(), w.data_ptr(), dpred.data_ptr(),
+                                                        _stream()), "param_mse")
+    return loss, w, dpred
+
+
+@param_mse.register_fake
+def _(pred, eps, x0, noise_level, iw, min_snr_gamma, kind, inv_global_count):
     B = pred.shape[0]
     rows = B if pred.dim() == 2 else B * pred.shape[1]
     return (pred.new_empty((B,), dtype=torch.float32), pred.new_empty((B,), dtype=torch.float32),

@@ -34,23 +34,67 @@ def alphas_cumprod(betas: np.ndarray) -> np.ndarray:
     return np.cumprod((np.float32(1.0) - betas).astype(np.float32), dtype=np.float32)
 
 
-def min_snr_weight(alphas_prod_like, gamma: float) -> np.ndarray:
-    """Min-SNR-gamma loss weight of an eps-prediction loss (Hang et al. 2023), float64: min(SNR, gamma) / SNR with
+PREDICTIONS = ("eps", "x0", "v")     # what the network's output means; the index is the engine's kind
+
+
+def prediction_kind(prediction) -> int:
+    """0 / 1 / 2 for "eps" / "x0" / "v" (or the integer itself): the value of the engine option "prediction"."""
+    if isinstance(prediction, (int, np.integer)) and not isinstance(prediction, bool) and 0 <= int(prediction) < len(PREDICTIONS):
+        return int(prediction)
+    if prediction in PREDICTIONS:
+        return PREDICTIONS.index(prediction)
+    raise ValueError(f"prediction must be one of {PREDICTIONS}, got {prediction!r}")
+
+
+def x0_coefficients(alphas_prod_like, prediction="eps"):
+    """float64 (c0, c1) of x0 = c0 x_t - c1 out for a network whose output ``out`` is eps (c0 = sqrt(1/ap), c1 = sqrt(1/ap - 1)),
+    x0 (c0 = 0, c1 = -1) or v = sqrt(ap) eps - sqrt(1 - ap) x0 (c0 = sqrt(ap), c1 = sqrt(1 - ap)): the first two columns of every
+    sampler table, which is all the sampler kernels know about the parameterisation."""
+    ap = np.asarray(alphas_prod_like, dtype=np.float64)
+    kind = prediction_kind(prediction)
+    if kind == 0:          # sqrt(1/ap - 1) as sqrt(1 - ap) / sqrt(ap): 1/ap - 1 cancels near ap = 1, 1 - ap is exact there
+        return 1.0 / np.sqrt(ap), np.sqrt(1.0 - ap) / np.sqrt(ap)
+    if kind == 1:
+        return np.zeros_like(ap), -np.ones_like(ap)
+    return np.sqrt(ap), np.sqrt(1.0 - ap)
+
+
+def _x0_columns(betas, prediction):
+    """float32 [T][2] (c0, c1) for a non-eps kind: float64 from the float32 ``alphas_cumprod``, rounded once; None for eps (the
+    tables then keep the float32 expressions of the reference, bit for bit)."""
+    if prediction_kind(prediction) == 0:
+        return None
+    c0, c1 = x0_coefficients(alphas_cumprod(betas).astype(np.float64), prediction)
+    return np.stack([c0, c1], axis=1).astype(np.float32)
+
+
+def min_snr_weight(alphas_prod_like, gamma: float, prediction="eps") -> np.ndarray:
+    """Min-SNR-gamma loss weight (Hang et al. 2023), float64.  ``prediction`` "eps" (the default): min(SNR, gamma) / SNR with
     SNR = ap / (1 - ap), i.e. min(1, gamma (1 - ap) / ap) -- 1 where SNR <= gamma, gamma / SNR above.  ``gamma`` <= 0 or +inf: no
     weighting (all ones).  ap = 1 (SNR = inf) gives 0 and ap = 0 gives 1, never a NaN.  The weighted loss kernel evaluates the
-    same expression per sample from the squared noise level q-sample stored."""
+    same expression per sample from the squared noise level q-sample stored.
+    ``prediction`` "x0": min(SNR, gamma) -- gamma at ap = 1, 0 at ap = 0; "v": min(SNR, gamma) / (SNR + 1) = min(ap, gamma (1 - ap))
+    -- 0 at both ends (section 26).  Where finite, w_v (SNR + 1) = w_x0 = w_eps SNR."""
     ap = np.asarray(alphas_prod_like, dtype=np.float64)
     gamma = float(gamma)
+    kind = prediction_kind(prediction)
     if not (gamma > 0.0) or np.isinf(gamma):
         return np.ones_like(ap)
+    if kind == 1:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            snr = np.where(ap < 1.0, ap / (1.0 - ap), np.inf)
+        return np.minimum(snr, gamma)
+    if kind == 2:
+        return np.minimum(ap, gamma * (1.0 - ap))
     with np.errstate(divide="ignore", invalid="ignore"):
         f = gamma * (1.0 - ap) / ap
     return np.minimum(1.0, np.where(ap > 0.0, f, np.inf))
 
 
-def reverse_coefficient_table(betas: np.ndarray) -> np.ndarray:
+def reverse_coefficient_table(betas: np.ndarray, prediction="eps") -> np.ndarray:
     """[T][8] float32: sqrt(1/ap), sqrt(1-ap)*sqrt(1/ap), mu1, mu2, sigma, ap, sqrt(ap), sqrt(1-ap)
-    (utils/ebm_utils.py:332-358, sigma = exp(0.5*log(max(var,1e-20))) as at :356-364)."""
+    (utils/ebm_utils.py:332-358, sigma = exp(0.5*log(max(var,1e-20))) as at :356-364).  ``prediction`` "x0" / "v": the first two
+    columns are that kind's (c0, c1) of ``x0_coefficients``; nothing else changes."""
     f = np.float32
     betas = np.asarray(betas, dtype=np.float32)
     alphas = (f(1) - betas).astype(np.float32)
@@ -65,7 +109,11 @@ def reverse_coefficient_table(betas: np.ndarray) -> np.ndarray:
     sigma = np.exp(f(0.5) * np.log(var_c, dtype=np.float32), dtype=np.float32)
     out = np.stack([sqrt_recip, sqrt_m1, mu1, mu2, sigma, ap, np.sqrt(ap, dtype=np.float32),
                     np.sqrt(f(1) - ap, dtype=np.float32)], axis=1)
-    return np.ascontiguousarray(out.astype(np.float32))
+    out = np.ascontiguousarray(out.astype(np.float32))
+    cols = _x0_columns(betas, prediction)
+    if cols is not None:
+        out[:, :2] = cols
+    return out
 
 
 def collection_index_table(T: int) -> np.ndarray:
@@ -111,9 +159,9 @@ def strided_coefficients(betas: np.ndarray, taus, eta: float) -> dict:
     return dict(a=np.sqrt(ap_s) - c * np.sqrt(ap_t), b=c, sigma=sigma, sqrt_as=np.sqrt(ap_s), sqrt_1m_as=np.sqrt(1 - ap_s))
 
 
-def _walk_tables(betas, order, co, next_t, slots, clip):
+def _walk_tables(betas, order, co, next_t, slots, clip, prediction="eps"):
     T = len(betas)
-    base = reverse_coefficient_table(betas)
+    base = reverse_coefficient_table(betas, prediction)
     coef = np.zeros((T, 8), dtype=np.float32)
     plan = np.zeros((T, 4), dtype=np.int32)
     plan[:, :3] = -1                                       # not on the walk: no next timestep, no iteration, no slot
@@ -123,20 +171,20 @@ def _walk_tables(betas, order, co, next_t, slots, clip):
     return coef, plan
 
 
-def strided_coefficient_table(betas: np.ndarray, taus, eta: float, clip: float = 1.0):
+def strided_coefficient_table(betas: np.ndarray, taus, eta: float, clip: float = 1.0, prediction="eps"):
     """Tables of the strided sampler for the descending timesteps ``taus``: float32 [T][8] (sqrt_recip, sqrt_m1, a, b, sigma,
     clip, sqrt_as, sqrt_1m_as) and int32 [T][4] (next_t, iteration, slot, 0).  Columns 0 / 1 are those of
-    ``reverse_coefficient_table``.  Timesteps that are not in ``taus`` have a zero row and (-1, -1, -1, 0); next_t is -1
+    ``reverse_coefficient_table`` (of the kind ``prediction``).  Timesteps that are not in ``taus`` have a zero row and (-1, -1, -1, 0); next_t is -1
     after the last iteration.  The slots are the reference's collection bookkeeping (``collection_slot_table``) applied to a
     walk of K = len(taus) iterations, so the collection keeps its 41 rows."""
     taus = [int(t) for t in taus]
     K = len(taus)
     slot_k = collection_slot_table(K)
     return _walk_tables(betas, taus, strided_coefficients(betas, taus, eta), taus[1:] + [-1],
-                        [int(slot_k[K - 1 - j]) for j in range(K)], clip)
+                        [int(slot_k[K - 1 - j]) for j in range(K)], clip, prediction)
 
 
-def inversion_coefficient_table(betas: np.ndarray, taus):
+def inversion_coefficient_table(betas: np.ndarray, taus, prediction="eps"):
     """The same walk ascending with sigma = 0 (DDIM inversion): taus_asc[j] -> taus_asc[j + 1], no clamp (clip = +inf), nothing
     collected.  len(taus) - 1 steps are executed; the last of them has next_t = T, which is out of range, so the walk stops by
     itself and no step is executed at T - 1."""
@@ -147,7 +195,7 @@ def inversion_coefficient_table(betas: np.ndarray, taus):
     co = dict(a=np.sqrt(ap[s_]) - c * np.sqrt(ap[t_]), b=c, sigma=np.zeros(len(t_)), sqrt_as=np.sqrt(ap[s_]),
               sqrt_1m_as=np.sqrt(1 - ap[s_]))
     n = len(t_)
-    return _walk_tables(betas, asc[:-1], co, asc[1:-1] + [len(betas)], [-1] * n, np.inf)
+    return _walk_tables(betas, asc[:-1], co, asc[1:-1] + [len(betas)], [-1] * n, np.inf, prediction)
 
 
 # ------------------------------------------------------------------ second-order multistep walks
@@ -197,14 +245,14 @@ def multistep_coefficients(betas: np.ndarray, taus, order: int) -> dict:
 MULTISTEP_COLUMNS = 12    # floats per row of the multistep coefficient table: rows stay 16-byte aligned
 
 
-def multistep_coefficient_table(betas: np.ndarray, taus, order: int, clip: float = 1.0):
+def multistep_coefficient_table(betas: np.ndarray, taus, order: int, clip: float = 1.0, prediction="eps"):
     """Tables of the multistep sampler for the descending timesteps ``taus``: float32 [T][12] -- the eight columns of
     ``strided_coefficient_table`` at eta = 0 with a0 in place of a (sqrt_recip, sqrt_m1, a0, b, 0, clip, sqrt_as, sqrt_1m_as),
     then a1 and three zeros -- and that function's int32 [T][4] plan unchanged.  At order 1 the first eight columns ARE the
     strided table, bit for bit."""
     taus = [int(t) for t in taus]
     co = multistep_coefficients(betas, taus, order)
-    base, plan = strided_coefficient_table(betas, taus, 0.0, clip)
+    base, plan = strided_coefficient_table(betas, taus, 0.0, clip, prediction)
     coef = np.zeros((len(betas), MULTISTEP_COLUMNS), dtype=np.float32)
     coef[:, :8] = base
     coef[taus, 2] = co["a0"]
@@ -213,7 +261,7 @@ def multistep_coefficient_table(betas: np.ndarray, taus, order: int, clip: float
 
 
 # ------------------------------------------------------------------ variational bound
-def bound_tables(betas: np.ndarray, timesteps, clip: float = 1.0) -> dict:
+def bound_tables(betas: np.ndarray, timesteps, clip: float = 1.0, prediction="eps") -> dict:
     """Everything the per-timestep variational bound (Ho et al. 2020, eq. 5) needs from the schedule, for the timesteps
     ``timesteps`` -- all of [0, T), or ``stride_timesteps(T, K)`` -- in any order; they are walked ascending.  Built in float64
     from the float32 ``alphas_cumprod`` (as the strided tables are), with ap_prev[0] = 1, and rounded once:
@@ -222,7 +270,8 @@ def bound_tables(betas: np.ndarray, timesteps, clip: float = 1.0) -> dict:
       var_0                  the decoder's variance, bt_1 (the reference's posterior variance at t = 0 is 0)
       decoder_const          (D / 2) log(2 pi var_0) per DIMENSION, i.e. 0.5 log(2 pi var_0): multiply by D
       prior_a, prior_c       L_T = 0.5 (prior_a * sum x0^2 + D * prior_c), prior_a = ap_{T-1}, prior_c = -ap_{T-1} - log(1 - ap_{T-1})
-      table [T][4] float32   (sqrt(ap), sqrt(1-ap), sqrt(1/ap), sqrt(1/ap - 1)): the kernels' rows
+      table [T][4] float32   (sqrt(ap), sqrt(1-ap), sqrt(1/ap), sqrt(1/ap - 1)): the kernels' rows; columns 2 and 3 are the
+                             (c0, c1) of ``x0_coefficients`` for the kind ``prediction``
       next_t [T] int32       the ascending walk: next_t[t] = the next timestep, -1 after the last and for timesteps off the walk
       timesteps              the walk, ascending (int64);  clip is passed through
     """
@@ -242,6 +291,8 @@ def bound_tables(betas: np.ndarray, timesteps, clip: float = 1.0) -> dict:
     w[1:] = mu1[1:] ** 2 / (2 * bt[1:])
     w[0] = 1.0 / (2 * var_0)
     table = np.stack([np.sqrt(ap), np.sqrt(1 - ap), np.sqrt(1 / ap), np.sqrt(1 / ap - 1)], axis=1)
+    if prediction_kind(prediction) != 0:
+        table[:, 2], table[:, 3] = x0_coefficients(ap, prediction)
     next_t = np.full((T,), -1, dtype=np.int32)
     next_t[ts[:-1]] = ts[1:]
     return dict(w=w, var_0=var_0, decoder_const=0.5 * np.log(2 * np.pi * var_0), prior_a=float(ap[-1]),

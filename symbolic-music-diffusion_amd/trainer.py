@@ -69,20 +69,30 @@ class LazyMetrics(dict):
 
 
 LOSS_WEIGHTINGS = ("none", "min_snr")
+PREDICTIONS = ("eps", "x0", "v")           # schedule.PREDICTIONS: what the network's output means
 TIMESTEP_SAMPLERS = ("uniform", "loss_second_moment")
 
 
 def validate_training_options(loss: str = "ddpm", loss_weighting: str = "none", timestep_sampler: str = "uniform",
-                              world_size: int = 1) -> None:
-    """The combinations of --loss / --loss_weighting / --timestep_sampler this engine trains; anything else
-    raises a ValueError that says what is refused.  train_ncsn.py calls this before it touches a device."""
+                              world_size: int = 1, prediction: str = "eps", sampling: str = "ddpm") -> None:
+    """The combinations of --loss / --loss_weighting / --timestep_sampler / --prediction / --sampling this engine trains (DESIGN.md
+    sections 25, 26); anything else raises a ValueError that says what is refused.  train_ncsn.py calls this before it touches a
+    device."""
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"--prediction must be one of {PREDICTIONS}, got {prediction!r}")
+    if prediction != "eps" and loss != "ddpm":
+        raise ValueError(f"--prediction={prediction} applies to --loss=ddpm only (got --loss={loss}): x0- and v-prediction are "
+                         "parameterisations of the DDPM network; the score-matching losses (--loss=dsm, --loss=ssm) train a score")
+    if prediction != "eps" and sampling != "ddpm":
+        raise ValueError(f"--prediction={prediction} needs --sampling=ddpm (got --sampling={sampling}): the Langevin samplers "
+                         "(--sampling=ald, --sampling=cas) take the network's output as a score")
     if loss_weighting not in LOSS_WEIGHTINGS:
         raise ValueError(f"--loss_weighting must be one of {LOSS_WEIGHTINGS}, got {loss_weighting!r}")
     if timestep_sampler not in TIMESTEP_SAMPLERS:
         raise ValueError(f"--timestep_sampler must be one of {TIMESTEP_SAMPLERS}, got {timestep_sampler!r}")
     if loss != "ddpm" and (loss_weighting != "none" or timestep_sampler != "uniform"):
         raise ValueError(f"--loss_weighting={loss_weighting} / --timestep_sampler={timestep_sampler} apply to --loss=ddpm only "
-                         f"(got --loss={loss}): the weights are defined for the eps-prediction DDPM loss")
+                         f"(got --loss={loss}): the weights are defined for the DDPM loss (of any --prediction)")
     if timestep_sampler == "loss_second_moment" and world_size > 1:
         raise ValueError(f"--timestep_sampler=loss_second_moment is single-process only (world size {world_size}): every rank "
                          "would need the labels and losses of the whole batch (an all-gather per step) to keep the tables "
@@ -184,12 +194,31 @@ class TimestepSampler:
         self._warmed.copy_((self.counts >= self.DEPTH).all().to(torch.int32).reshape(1))
 
 
+def loss_in_eps_units(loss_per_sample: torch.Tensor, noise_level: torch.Tensor, prediction: str = "eps") -> torch.Tensor:
+    """The batch mean of f_b loss_b: the unweighted per-sample loss of an x0- / v-predicting network in the units of an eps loss,
+    so runs of different kinds can be compared.  With ap = noise_level^2, at fixed x_t:
+    x0_hat - x0 = -(sqrt(1 - ap) / sqrt(ap)) (eps_hat - eps) and v_hat - v = (eps_hat - eps) / sqrt(ap), so f = 1 for eps,
+    ap / (1 - ap) for x0 and ap for v.  Samples with ap = 1 (label 1: x_t is x0 itself, an x0 estimate says nothing about eps) are
+    left out of the x0 mean; a mean over no sample is 0.  Computed on the device in float64 from [B] values: no kernel of its own."""
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"prediction must be one of {PREDICTIONS}, got {prediction!r}")
+    loss = loss_per_sample.double()
+    if prediction == "eps":
+        return loss.mean().float()
+    ap = noise_level.double() ** 2
+    if prediction == "v":
+        return (ap * loss).mean().float()
+    keep = ap < 1.0
+    f = torch.where(keep, ap / torch.where(keep, 1.0 - ap, torch.ones_like(ap)), torch.zeros_like(ap))
+    return ((f * loss).sum() / keep.sum().clamp(min=1)).float()
+
+
 def train_step(objective, batch, optimizer: Optimizer, sigmas, rng: PRNGKey, learning_rate: float, *,
                grad_clip: float = 1.0, mu: float = 0.999, labels=None, eps=None, comm: "Optional[GradComm]" = None,
                lr_gamma: float = 1.0, lr_interval: int = 1, sample_offset: int = 0,
                global_batch: Optional[int] = None, continuous_noise: bool = True, used_alphas=None,
                loss_weighting: str = "none", min_snr_gamma: float = 5.0,
-               timestep_sampler: "Optional[TimestepSampler]" = None, loss_weights=None):
+               timestep_sampler: "Optional[TimestepSampler]" = None, loss_weights=None, prediction: str = "eps"):
     """train_ncsn.py:260-288: value_and_grad(mean diffusion_loss) -> clip_grads -> Adam
     (+ EMA, fused).  ``learning_rate`` is the step's LR as in the reference; pass ``lr_gamma`` /
     ``lr_interval`` instead to let the kernel evaluate the stepped schedule from its own step
@@ -206,7 +235,17 @@ def train_step(objective, batch, optimizer: Optimizer, sigmas, rng: PRNGKey, lea
     sample by min(SNR, min_snr_gamma) / SNR of its noise level, ``timestep_sampler`` (a TimestepSampler) draws the labels from
     its loss-aware table, weights the samples by 1 / (n p) and is fed the step's per-sample losses; ``loss_weights`` ([B]) passes
     importance weights explicitly.  metrics['loss'] is then the weighted objective that is optimised, mean(w loss), and
-    metrics['loss_unweighted'] the plain mean.  With the defaults nothing changes."""
+    metrics['loss_unweighted'] the plain mean.  With the defaults nothing changes.
+
+    ``prediction`` "x0" / "v" (``objective is diffusion_loss`` only): the network's output is compared with
+    x0 / v = s eps - sqrt(1 - s^2) x0 and min_snr weights by min(SNR, gamma) / min(SNR, gamma) / (SNR + 1).  metrics['loss'] and
+    ['loss_unweighted'] are then in that output's space, and metrics['loss_eps'] is the unweighted loss in eps units
+    (``loss_in_eps_units``): what an eps run reports as its unweighted loss, so runs of different kinds can be compared."""
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"train_step: prediction must be one of {PREDICTIONS}, got {prediction!r}")
+    if prediction != "eps" and objective is not diffusion_loss:
+        raise ValueError(f"train_step: prediction={prediction!r} applies to objective=diffusion_loss (the DDPM loss) only, got "
+                         f"{getattr(objective, '__name__', objective)!r}")
     if loss_weighting not in LOSS_WEIGHTINGS:
         raise ValueError(f"train_step: loss_weighting must be one of {LOSS_WEIGHTINGS}, got {loss_weighting!r}")
     weighted = loss_weighting != "none" or timestep_sampler is not None or loss_weights is not None
@@ -223,9 +262,10 @@ def train_step(objective, batch, optimizer: Optimizer, sigmas, rng: PRNGKey, lea
                                    lr_gamma=lr_gamma, lr_interval=lr_interval, continuous_noise=continuous_noise)
     dsm = objective is denoising_score_matching_loss
     if dsm:
+        eng.set_prediction("eps")
         _ensure_any_schedule(eng)
     else:
-        _ensure_schedule(eng, sigmas, with_sampler=False)
+        _ensure_schedule(eng, sigmas, with_sampler=False, prediction=prediction)
     eng.bind(batch.shape[0], training=True)
     lab = None if labels is None else torch.as_tensor(labels).to(eng.device, torch.int32).contiguous()
     e = None if eps is None else torch.as_tensor(eps).to(eng.device, torch.float32).contiguous()
@@ -299,10 +339,13 @@ def train_step(objective, batch, optimizer: Optimizer, sigmas, rng: PRNGKey, lea
     per_sample = eng.loss_per_sample()
     loss = per_sample.mean()
     metrics = LazyMetrics(loss=loss, grad=eng.metrics[1], lr=eng.metrics[2])
-    if weighted:
+    if weighted or prediction != "eps":
         # the objective that was optimised, from the weights the loss kernel wrote; the plain mean stays comparable between runs
+        # (an x0 / v step always runs the weighted kernel: unweighted, every weight is exactly 1)
         metrics["loss"] = (eng.weight_per_sample() * per_sample).mean()
         metrics["loss_unweighted"] = loss
+        if prediction != "eps":        # (an eps run's loss_unweighted -- unweighted: its loss -- is already in eps units)
+            metrics["loss_eps"] = loss_in_eps_units(per_sample, eng.noise_level_per_sample(), prediction)
         if timestep_sampler is not None:
             timestep_sampler.update(lab, per_sample)         # the UNWEIGHTED per-sample losses, in sample order
     return optimizer, metrics

@@ -8,6 +8,7 @@ per GPU, RCCL gradient all-reduce); rank 0 logs / evaluates / saves.
 """
 from __future__ import annotations
 
+import functools
 import logging
 import os
 import re
@@ -95,16 +96,20 @@ def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world
     early_stop = train_utils.EarlyStopping(patience=1)                            # :333
     # weighted training: min-SNR loss weights and / or the loss-aware timestep sampler
     train_options = {"loss_weighting": FLAGS.loss_weighting, "min_snr_gamma": FLAGS.min_snr_gamma,
-                     "timestep_sampler": FLAGS.timestep_sampler}
+                     "timestep_sampler": FLAGS.timestep_sampler, "prediction": FLAGS.prediction}
     sampler = None
     if FLAGS.timestep_sampler == "loss_second_moment":
         from smd_amd.trainer import TimestepSampler
         sampler = TimestepSampler.for_schedule(sigmas, FLAGS.continuous_noise, dev)
     if rank == 0:
-        log.info("loss weighting: %s (min_snr_gamma %g); timestep sampler: %s", FLAGS.loss_weighting, FLAGS.min_snr_gamma,
-                 FLAGS.timestep_sampler)
+        log.info("loss weighting: %s (min_snr_gamma %g); timestep sampler: %s; prediction: %s", FLAGS.loss_weighting,
+                 FLAGS.min_snr_gamma, FLAGS.timestep_sampler, FLAGS.prediction)
     resumed_from = -1
     if FLAGS.resume:
+        try:
+            checkpoint.check_resume_prediction(output_dir, FLAGS.prediction)          # a changed kind is refused
+        except ValueError as e:
+            raise SystemExit(str(e))
         found, restored = checkpoint.restore_checkpoint(output_dir, optimizer.engine)
         if found:
             early_stop = restored
@@ -124,6 +129,8 @@ def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world
 
     # :345-352 (ssm needs a second backward through the network and is a toy-only objective upstream)
     objective = {"ddpm": ncsn.diffusion_loss, "dsm": ncsn.denoising_score_matching_loss}[FLAGS.loss]
+    # the validation loss of an x0- / v-predicting network is that kind's (unweighted, output-space) loss too
+    eval_objective = objective if FLAGS.prediction == "eps" else functools.partial(objective, prediction=FLAGS.prediction)
     sampling_step = resumed_from                    # checkpoints are numbered by this counter: a resumed run goes on counting
     for epoch in range(FLAGS.epochs):
         start_time = time.time()
@@ -138,7 +145,8 @@ def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world
                 grad_clip=FLAGS.grad_clip, mu=FLAGS.mu, comm=comm, lr_gamma=FLAGS.lr_gamma,
                 lr_interval=FLAGS.lr_schedule_interval, sample_offset=rank * FLAGS.batch_size,
                 global_batch=FLAGS.batch_size * world, continuous_noise=FLAGS.continuous_noise,
-                loss_weighting=FLAGS.loss_weighting, min_snr_gamma=FLAGS.min_snr_gamma, timestep_sampler=sampler)
+                loss_weighting=FLAGS.loss_weighting, min_snr_gamma=FLAGS.min_snr_gamma, timestep_sampler=sampler,
+                prediction=FLAGS.prediction)
             if FLAGS.ema:
                 ema = ema.update(optimizer.target)                                # :364-365 (fused: no-op)
 
@@ -154,7 +162,8 @@ def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world
                 sampling_step += 1
                 rng, eval_rng = ncsn.split(rng)
                 if rank == 0:
-                    eval_metrics = evaluate(valid_batches, optimizer.target, sigmas, eval_rng, FLAGS.continuous_noise, objective)
+                    eval_metrics = evaluate(valid_batches, optimizer.target, sigmas, eval_rng, FLAGS.continuous_noise,
+                                            eval_objective)
                     train_utils.log_metrics(eval_metrics, global_step, train_batches.examples * FLAGS.epochs,
                                             summary_writer=eval_writer, verbose=verbose)
                     improved, early_stop = early_stop.update(eval_metrics["loss"])            # :393
@@ -185,7 +194,7 @@ def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world
                         generated, collection, ld_metrics = ncsn.sample(
                             scorenet, sigmas, rng, input_shape, num_samples=FLAGS.eval_samples,
                             sampling=FLAGS.sampling, epsilon=FLAGS.ld_epsilon, steps=FLAGS.ld_steps,
-                            denoise=FLAGS.denoise)
+                            denoise=FLAGS.denoise, prediction=FLAGS.prediction)
                         log_langevin_dynamics(ld_metrics, sampling_step, output_dir)
                         del scorenet
                     train_writer.flush()
@@ -212,7 +221,8 @@ def main(argv):
                          "sample the checkpoint with sample_ncsn.py --dtype=fp32")
     try:
         from smd_amd.trainer import validate_training_options
-        validate_training_options(FLAGS.loss, FLAGS.loss_weighting, FLAGS.timestep_sampler, world)
+        validate_training_options(FLAGS.loss, FLAGS.loss_weighting, FLAGS.timestep_sampler, world,
+                                  prediction=FLAGS.prediction, sampling=FLAGS.sampling)
     except ValueError as e:
         raise SystemExit(str(e))
     if FLAGS.timestep_sampler == "loss_second_moment" and FLAGS.ckpt_format == "flax" and rank == 0:
