@@ -575,6 +575,33 @@ int smd_bound_noise(const float* x0, int B, int S, int C, int Cp, const float* t
                     smd_bf16* xt_bf16, void* stream);
 int smd_bound_terms(const float* x0, const float* eps, const float* eps_hat, int B, int S, int C, const float* table, int T,
                     float clip, int32_t* t_ptr, const int32_t* next_t, uint32_t* arrive, float* partial, void* stream);
+/* The three element-wise kernels of a progressive-distillation step (Salimans & Ho 2022) on explicit
+ * arrays.  Every sample has a walk step of its own: steps [B] int32 in [0, N) picks its row of table [N][16] fp32 (16-byte
+ * aligned; columns c0_t, c1_t, a, b, clip, alpha_t, sigma_t, alpha_m, c0_m, c1_m, w1, w2, weight, 1/sigma_t, 0, 0).  A step outside
+ * [0, N) makes that sample a no-op: none of its outputs is written.  All arrays [B][S][C] fp32, contiguous; when C is a
+ * multiple of 4 they must be 16-byte aligned (anything else is refused before the launch).  Nothing but the outputs named
+ * here is written.
+ * smd_distill_noise: z_t = fmaf(alpha_t, x0, sigma_t * eps), level_out[b] = alpha_t.  draw 0: eps is read; draw != 0: eps is
+ *   WRITTEN with Philox normals, counter (e/4, b + sample_offset, 7, step), step_ptr (device, NULL-able) replacing `step`.
+ * smd_distill_mid: x1 = clamp(c0_t z_t - c1_t out1, -clip, clip) (rounded once, as the strided sampler forms it),
+ *   z_m = fmaf(a, x1, b * z_t), level_out[b] = alpha_m.  z_m has the bits the strided sampler step writes at sigma = 0 from
+ *   the same table entries.
+ * smd_distill_loss: x2 = clamp(c0_m z_m - c1_m out2, -clip, clip), x~ = w1 x1 + w2 x2, the student's target by its kind
+ *   (0 eps: (z_t - alpha_t x~) * (1/sigma_t), 1 x0: x~, 2 v: (alpha_t z_t - x~) * (1/sigma_t), 1/sigma_t the table's column; z_t may
+ *   be NULL for kind 1), evaluated per element in float64 from the fp32 inputs and rounded once: the eps and v targets are a
+ *   cancelling difference over sigma_t, which fp32 arithmetic would carry into pred - target.
+ *   loss_per_sample [B] the UNWEIGHTED mean of (pred - target)^2 (fp32, fixed summation order, no atomics: a sample's value
+ *   depends on its own rows only and two calls agree bitwise), weight_per_sample [B] = iw_b * weight (iw NULL = 1),
+ *   dpred = 2 w_b (pred - target) * inv_global_count in fp32, the layout smd_engine_backward_from takes, and, with
+ *   target_out != NULL, the target itself. */
+int smd_distill_noise(const float* x0, int B, int S, int C, const float* table, int N, const int32_t* steps, float* eps, int draw,
+                      uint32_t seed_lo, uint32_t seed_hi, uint32_t sample_offset, uint32_t step, const uint32_t* step_ptr,
+                      float* z_t, float* level_out, void* stream);
+int smd_distill_mid(const float* z_t, const float* out1, int B, int S, int C, const float* table, int N, const int32_t* steps,
+                    float* x1, float* z_m, float* level_out, void* stream);
+int smd_distill_loss(const float* x1, const float* z_m, const float* out2, const float* z_t, const float* pred, int kind, int B,
+                     int S, int C, const float* table, int N, const int32_t* steps, const float* iw, float inv_global_count,
+                     float* loss_per_sample, float* weight_per_sample, float* dpred, float* target_out, void* stream);
 
 /* ---- reference-precision (fp32) kernels of the engine option "fp32" -----------------------------------------------------
  * smd_gemm_f32: out[m][n] = act(sum_k A[m][k] W[k][n] + bias[n]) + residual[m or m % res_row_mod][n], nn.Dense with A

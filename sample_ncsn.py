@@ -69,7 +69,28 @@ def resolve_prediction_flag(FLAGS) -> str:
     return kind
 
 
-def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sample_offset=0, global_num_samples=None):
+def resolve_distill_walk(FLAGS):
+    """The walk a distilled student's checkpoint records (``distill_timesteps``), or None.  With
+    --sampling=ddpm such a checkpoint is sampled on that walk by the strided sampler: --ddim_steps unset takes its length, another
+    number is refused, --ddim_order / --ddim_eta / --infill / --interpolate go through the same walk.  Before the GPU is touched."""
+    from smd_amd import checkpoint
+    walk = checkpoint.checkpoint_distill_walk(FLAGS.model_dir) if FLAGS.sampling == "ddpm" else None
+    if walk is None:
+        return None
+    where = f"the checkpoint under {FLAGS.model_dir} was distilled to the {len(walk)} timesteps {checkpoint.format_walk(walk)}"
+    if FLAGS.ddim_steps and FLAGS.ddim_steps != len(walk):
+        raise SystemExit(f"--ddim_steps={FLAGS.ddim_steps}: {where}; drop the flag or pass --ddim_steps={len(walk)}")
+    if FLAGS.ddim_spacing != "uniform":
+        raise SystemExit(f"--ddim_spacing={FLAGS.ddim_spacing} chooses the timesteps itself: {where}")
+    if FLAGS.ddim_encode:
+        raise SystemExit(f"--ddim_encode inverts an evenly spaced walk: {where}")
+    if max(walk) >= FLAGS.num_sigmas:
+        raise SystemExit(f"--num_sigmas={FLAGS.num_sigmas}: {where}")
+    FLAGS.ddim_steps = len(walk)
+    return walk
+
+
+def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sample_offset=0, global_num_samples=None, walk=None):
     """sample_ncsn.py:313-365."""
     from smd_amd import ncsn
     rng, sample_rng = ncsn.split(rng)
@@ -78,13 +99,13 @@ def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sampl
         model, sigmas, sample_rng, sample_shape, num_samples=num_samples, sampling=FLAGS.sampling,
         epsilon=FLAGS.ld_epsilon, steps=FLAGS.ld_steps, denoise=FLAGS.denoise, sample_offset=sample_offset,
         use_graph=FLAGS.graph, global_num_samples=global_num_samples, ddim_steps=FLAGS.ddim_steps, ddim_eta=FLAGS.ddim_eta,
-        ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS))
+        ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS), ddim_timesteps=walk)
     torch.cuda.synchronize()
     log.info("Generated samples in %f seconds", time.time() - t0)
     return generated, collection, ld_metrics
 
 
-def infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=0, global_num_samples=None):
+def infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=0, global_num_samples=None, walk=None):
     """sample_ncsn.py:189-242 (init ~ U[0,1) like :228: jax.random.uniform with --rng_impl=threefry, torch's device
     generator otherwise)."""
     from smd_amd import jax_random, ncsn
@@ -107,7 +128,7 @@ def infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=0, g
         generated, collection, ld_metrics = ncsn.strided_dynamics(
             ld_rng, model, sigmas, init, FLAGS.ddim_steps, FLAGS.ddim_eta, True, infill_samples=samples, infill_masks=masks,
             use_graph=FLAGS.graph, sample_offset=sample_offset, global_num_samples=global_num_samples, order=FLAGS.ddim_order,
-            spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS))
+            spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS), timesteps=walk)
         return generated, collection, ncsn.collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = ncsn.diffusion_dynamics(
         ld_rng, model, sigmas, init, FLAGS.ld_epsilon, FLAGS.ld_steps, FLAGS.denoise, True,
@@ -134,7 +155,7 @@ def diffusion_stochastic_encoder(samples, sigmas, rng, device="cuda:0", sample_o
 
 
 def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl, dev, use_graph=True, points=9, ddim_steps=0,
-                        ddim_eta=0.0, ddim_encode=False, ddim_order=1, ddim_spacing="uniform", prediction="eps"):
+                        ddim_eta=0.0, ddim_encode=False, ddim_order=1, ddim_spacing="uniform", prediction="eps", walk=None):
     """sample_ncsn.py:425-435 + diffusion_decoder (:269-310) for this rank's rows [lo, hi): goals = roll(starts, 1); both are
     encoded with the same key (the same noise); every one of the 9 interpolated latents is decoded with the SAME
     ld_rng = split(PRNGKey(sample_seed), 3)[1].  Returns (generated (9, n, ...), collection (9, 41, n, ...), collated metrics).
@@ -158,7 +179,8 @@ def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl,
         z = ((1 - alpha) * zs + alpha * zg).astype(np.float32)
         if ddim_steps:
             g, c, ld = ncsn.strided_dynamics(ld_rng, model, sigmas, z, ddim_steps, ddim_eta, use_graph=use_graph, sample_offset=lo,
-                                             global_num_samples=num, order=ddim_order, spacing=ddim_spacing, prediction=prediction)
+                                             global_num_samples=num, order=ddim_order, spacing=ddim_spacing, prediction=prediction,
+                                             timesteps=walk)
         else:
             g, c, ld = ncsn.diffusion_dynamics(ld_rng, model, sigmas, z, use_graph=use_graph, sample_offset=lo, global_num_samples=num,
                                                prediction=prediction)
@@ -255,14 +277,15 @@ def check_cluster_flags(FLAGS):
                          f"fewer than the {k} clusters of --prd_clusters={FLAGS.prd_clusters} / --ndb_bins={FLAGS.ndb_bins}")
 
 
-def check_ddim_flags(FLAGS):
-    """the refusals of --ddim_steps / --ddim_eta / --ddim_encode / --ddim_order / --ddim_spacing, before the GPU is touched"""
+def check_ddim_flags(FLAGS, walk=None):
+    """the refusals of --ddim_steps / --ddim_eta / --ddim_encode / --ddim_order / --ddim_spacing, before the GPU is touched;
+    ``walk``: the recorded walk of a distilled checkpoint (resolve_distill_walk), whose length --ddim_steps then is"""
     used = [f"--{n}" for n in ("ddim_steps", "ddim_eta", "ddim_encode") if FLAGS.is_present(n) and getattr(FLAGS, n)]
     used += [f"--{n}" for n, off in (("ddim_order", 1), ("ddim_spacing", "uniform")) if FLAGS.is_present(n) and getattr(FLAGS, n) != off]
     if used and FLAGS.sampling != "ddpm":
         raise SystemExit(f"{', '.join(used)}: the strided sampler walks a DDPM schedule, it needs --sampling=ddpm (got --sampling={FLAGS.sampling})")
     steps = FLAGS.ddim_steps
-    if steps is None or not (steps == 0 or 2 <= steps <= FLAGS.num_sigmas):
+    if walk is None and (steps is None or not (steps == 0 or 2 <= steps <= FLAGS.num_sigmas)):
         raise SystemExit(f"--ddim_steps={steps}: 0 (every timestep) or from 2 to --num_sigmas={FLAGS.num_sigmas} timesteps")
     if FLAGS.ddim_eta < 0:
         raise SystemExit(f"--ddim_eta={FLAGS.ddim_eta}: the noise scale is >= 0")
@@ -425,7 +448,10 @@ def main(argv):
         raise SystemExit(f"--nn_k={FLAGS.nn_k}: the radius is the distance to the k-th neighbour for k from 1 to 8")
     if FLAGS.cluster_metrics:
         check_cluster_flags(FLAGS)
-    check_ddim_flags(FLAGS)
+    walk = resolve_distill_walk(FLAGS)
+    if walk is not None and rank == 0:
+        log.info("distilled checkpoint: sampling on its walk of %d timesteps %s", len(walk), walk)
+    check_ddim_flags(FLAGS, walk)
     check_bound_flags(FLAGS)
     check_copy_flags(FLAGS)
     try:
@@ -487,16 +513,16 @@ def main(argv):
             samples[:, infilled_idx, :] = 0
             masks[:, fixed_idx, :] = 1
         generated, collection, ld_metrics = infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=lo,
-                                                           global_num_samples=num)
+                                                           global_num_samples=num, walk=walk)
     elif FLAGS.interpolate:                                                 # :425-435
         generated, collection, ld_metrics = interpolate_samples(model, sigmas, real, lo, hi, rng, FLAGS.sample_seed, FLAGS.rng_impl,
                                                                 dev, FLAGS.graph, ddim_steps=FLAGS.ddim_steps,
                                                                 ddim_eta=FLAGS.ddim_eta, ddim_encode=FLAGS.ddim_encode,
                                                                 ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing,
-                                                                prediction=FLAGS.prediction)
+                                                                prediction=FLAGS.prediction, walk=walk)
     else:                                                                   # :437-439
         generated, collection, ld_metrics = generate_samples(FLAGS, model, rng, shape, hi - lo, sigmas, sample_offset=lo,
-                                                             global_num_samples=num)
+                                                             global_num_samples=num, walk=walk)
 
     # evaluate() reads the device collection where there is one (a single rank); the shards of several ranks are gathered
     # on the host below

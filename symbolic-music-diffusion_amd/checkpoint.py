@@ -16,7 +16,7 @@ import glob
 import json
 import os
 import re
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np  # noqa: F401  (type names in annotations)
 import torch
@@ -187,6 +187,31 @@ def check_resume_prediction(ckpt_dir: str, prediction: str) -> None:
     if recorded != prediction:
         raise ValueError(f"--resume: {path} was trained with --prediction={recorded}, this run asks for --prediction={prediction}; "
                          f"resume with --prediction={recorded} or start a new --model_dir")
+
+
+def format_walk(walk) -> str:
+    """a walk as the metadata string "15,11,6,2" ("" for no walk)"""
+    return ",".join(str(int(t)) for t in walk) if walk is not None else ""
+
+
+def checkpoint_distill_walk(ckpt_dir: str) -> Optional[List[int]]:
+    """The walk a distilled student was trained on (``distill_timesteps`` of its train_options), or None:
+    a network that was not distilled, a flax-format file, no checkpoint."""
+    text = checkpoint_train_options(ckpt_dir).get("distill_timesteps") or ""
+    return [int(t) for t in text.split(",")] if text else None
+
+
+def check_resume_distill(ckpt_dir: str, walk) -> None:
+    """--resume with another student walk than the checkpoint records is refused (ValueError): that includes resuming a
+    distillation run without --distill_from and a plain run with it.  No checkpoint or a flax-format file: nothing to check."""
+    path = ckpt_dir if os.path.isfile(ckpt_dir) else latest_checkpoint(ckpt_dir)
+    if path is None or flax_io.is_flax_file(path):
+        return
+    recorded, mine = format_walk(checkpoint_distill_walk(path)), format_walk(walk)
+    if recorded != mine:
+        say = lambda w: f"the distillation walk {w}" if w else "no distillation walk"
+        raise ValueError(f"--resume: {path} was trained on {say(recorded)}, this run asks for {say(mine)}; resume with the "
+                         "--distill_from / --distill_steps it was started with or start a new --model_dir")
 
 
 def load_ema_params(ckpt_dir: str, engine) -> bool:

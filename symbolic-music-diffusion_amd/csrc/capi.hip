@@ -549,6 +549,31 @@ int smd_bound_terms(const float* x0, const float* eps, const float* eps_hat, int
   return launch_bound_terms(a, S(stream));
 }
 
+int smd_distill_noise(const float* x0, int Bn, int Sn, int C, const float* table, int N, const int32_t* steps, float* eps, int draw,
+                      uint32_t lo, uint32_t hi, uint32_t off, uint32_t step, const uint32_t* step_ptr, float* z_t, float* level_out,
+                      void* stream) {
+  DistillNoiseArgs a;
+  a.x0 = x0; a.eps = eps; a.draw = draw ? 1 : 0; a.B = Bn; a.S = Sn; a.C = C; a.N = N; a.table = table; a.steps = steps;
+  a.key = RngKey{lo, hi}; a.sample_offset = off; a.step = step; a.step_ptr = step_ptr; a.z_t = z_t; a.level_out = level_out;
+  return launch_distill_noise(a, S(stream));
+}
+int smd_distill_mid(const float* z_t, const float* out1, int Bn, int Sn, int C, const float* table, int N, const int32_t* steps,
+                    float* x1, float* z_m, float* level_out, void* stream) {
+  DistillMidArgs a;
+  a.z_t = z_t; a.out1 = out1; a.B = Bn; a.S = Sn; a.C = C; a.N = N; a.table = table; a.steps = steps; a.x1 = x1; a.z_m = z_m;
+  a.level_out = level_out;
+  return launch_distill_mid(a, S(stream));
+}
+int smd_distill_loss(const float* x1, const float* z_m, const float* out2, const float* z_t, const float* pred, int kind, int Bn,
+                     int Sn, int C, const float* table, int N, const int32_t* steps, const float* iw, float inv_global_count,
+                     float* loss_per_sample, float* weight_per_sample, float* dpred, float* target_out, void* stream) {
+  DistillLossArgs a;
+  a.x1 = x1; a.z_m = z_m; a.out2 = out2; a.z_t = z_t; a.pred = pred; a.kind = kind; a.B = Bn; a.S = Sn; a.C = C; a.N = N;
+  a.table = table; a.steps = steps; a.iw = iw; a.inv_global_count = inv_global_count; a.loss_per_sample = loss_per_sample;
+  a.weight_per_sample = weight_per_sample; a.dpred = dpred; a.target_out = target_out;
+  return launch_distill_loss(a, S(stream));
+}
+
 int smd_probe_tr_read(const smd_bf16* image, smd_bf16* out, void* stream) { return launch_probe_tr_read(B(image), B(out), S(stream)); }
 
 // ---- lab entry: launch_gemm_tn_grouped / launch_gemm_tn256_multi on a caller's problem list (include/smd_hip_lab.h).  Everything

@@ -18,7 +18,8 @@ enum : uint32_t {
   SMD_STREAM_INIT = 3,      // initial state           (train_ncsn.py:540)
   SMD_STREAM_INFILL = 4,    // infill template noise   (utils/ebm_utils.py:342-345)
   SMD_STREAM_BOUND = 5,     // forward noise of the variational bound (bound.hip; no reference counterpart)
-  SMD_STREAM_TIMESTEP = 6   // loss-aware timestep draw (timestep.hip; no reference counterpart)
+  SMD_STREAM_TIMESTEP = 6,  // loss-aware timestep draw (timestep.hip; no reference counterpart)
+  SMD_STREAM_DISTILL = 7    // forward noise of a distillation step (distill.hip; no reference counterpart)
 };
 
 __host__ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {

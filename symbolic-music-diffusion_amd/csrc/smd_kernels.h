@@ -412,6 +412,58 @@ struct BoundTermsArgs {
 };
 int launch_bound_terms(const BoundTermsArgs& a, hipStream_t st);
 
+// ------------------------------------------------------------------ progressive distillation (distill.hip)
+// Three element-wise kernels with a walk step PER SAMPLE: steps [B] int32 in [0, N) picks the sample's row of table [N][16]
+// float32 (64-byte rows, 16-byte aligned): c0_t, c1_t, a, b, clip, alpha_t, sigma_t, alpha_m, c0_m, c1_m, w1, w2, weight,
+// 1/sigma_t, 0, 0 (schedule.distill_tables).  A step outside [0, N) makes the sample a no-op that writes nothing.
+#define SMD_DISTILL_COLUMNS 16
+struct DistillNoiseArgs {
+  const float* x0 = nullptr;          // [B][S][C] examples
+  float* eps = nullptr;               // [B][S][C]: read (draw == 0) or written (draw == 1)
+  int draw = 0;                       // 1: Philox normals keyed by (key, b + sample_offset, step) on SMD_STREAM_DISTILL
+  int B = 0, S = 0, C = 0, N = 0;
+  const float* table = nullptr;
+  const int* steps = nullptr;         // [B]
+  RngKey key{0, 0};
+  uint32_t sample_offset = 0;
+  uint32_t step = 0;                  // the draw's fourth counter word
+  const uint32_t* step_ptr = nullptr; // device (nullable): replaces `step`, as in q-sample
+  float* z_t = nullptr;               // [B][S][C] alpha_t x0 + sigma_t eps
+  float* level_out = nullptr;         // [B] alpha_t: the teacher's and the student's noise level
+};
+int launch_distill_noise(const DistillNoiseArgs& a, hipStream_t st);
+
+struct DistillMidArgs {
+  const float* z_t = nullptr;         // [B][S][C]
+  const float* out1 = nullptr;        // [B][S][C] teacher(z_t, alpha_t)
+  int B = 0, S = 0, C = 0, N = 0;
+  const float* table = nullptr;
+  const int* steps = nullptr;
+  float* x1 = nullptr;                // [B][S][C] the clamped x0 estimate at t
+  float* z_m = nullptr;               // [B][S][C] a x1 + b z_t: the strided step's state at sigma = 0, bit for bit
+  float* level_out = nullptr;         // [B] alpha_m
+};
+int launch_distill_mid(const DistillMidArgs& a, hipStream_t st);
+
+struct DistillLossArgs {
+  const float* x1 = nullptr;          // [B][S][C]
+  const float* z_m = nullptr;
+  const float* out2 = nullptr;        // teacher(z_m, alpha_m)
+  const float* z_t = nullptr;         // read for the eps and v targets only
+  const float* pred = nullptr;        // student(z_t, alpha_t)
+  int kind = 0;                       // the STUDENT's output: 0 eps, 1 x0, 2 v
+  int B = 0, S = 0, C = 0, N = 0;
+  const float* table = nullptr;
+  const int* steps = nullptr;
+  const float* iw = nullptr;          // [B] or null (1)
+  float inv_global_count = 0.f;       // 1 / (Bglobal S C)
+  float* loss_per_sample = nullptr;   // [B] the UNWEIGHTED mean of (pred - target)^2
+  float* weight_per_sample = nullptr; // [B] iw_b * weight[k_b]
+  float* dpred = nullptr;             // [B][S][C] fp32: 2 w_b (pred - target) inv_global_count
+  float* target_out = nullptr;        // [B][S][C] or null
+};
+int launch_distill_loss(const DistillLossArgs& a, hipStream_t st);
+
 // Langevin update of annealed_langevin_dynamics / consistent_langevin_dynamics (utils/ebm_utils.py:131-164, 231-253)
 struct LangevinStepArgs {
   float* x = nullptr;                 // [B][S][C] state, updated in place

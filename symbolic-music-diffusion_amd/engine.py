@@ -546,3 +546,73 @@ class Engine:
     @property
     def slot_table(self) -> torch.Tensor:
         return self._sched_tensors["slot"]
+
+
+# ------------------------------------------------------------------ progressive distillation
+# Engine-free wrappers of the three element-wise kernels (include/smd_hip.h smd_distill_*): device tensors in, device tensors
+# out, launched on torch's current stream.  ``table`` is the float32 [N][16] table of schedule.distill_tables on the device,
+# ``steps`` int32 [B] in [0, N).  A sample whose step is out of range is a no-op: its rows of the outputs are not written.
+def _distill_args(x: torch.Tensor, table: torch.Tensor, steps: torch.Tensor, *more: Optional[torch.Tensor]):
+    if not x.is_cuda:
+        raise RuntimeError("the distillation kernels need a ROCm GPU: the HIP path has no CPU fallback")
+    if x.dtype != torch.float32 or x.dim() not in (2, 3) or not x.is_contiguous():
+        raise ValueError("distill: fp32 contiguous (B, S, C) or (B, C) tensors")
+    B, S, Cn = (x.shape[0], 1, x.shape[1]) if x.dim() == 2 else tuple(x.shape)
+    for t in more:
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != tuple(x.shape) or not t.is_contiguous()
+                              or t.device != x.device):
+            raise ValueError(f"distill: every array must be fp32, contiguous and of shape {tuple(x.shape)} on {x.device}")
+    if (table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != _sched.DISTILL_COLUMNS or not table.is_contiguous()
+            or table.device != x.device):
+        raise ValueError(f"distill: table fp32 [N][{_sched.DISTILL_COLUMNS}] on {x.device}")
+    if steps.dtype != torch.int32 or steps.numel() != B or not steps.is_contiguous() or steps.device != x.device:
+        raise ValueError(f"distill: steps int32 [{B}] on {x.device}")
+    return B, S, Cn, int(table.shape[0])
+
+
+def distill_noise(x0: torch.Tensor, table: torch.Tensor, steps: torch.Tensor, eps: Optional[torch.Tensor] = None, *, seed: int = 0,
+                  sample_offset: int = 0, step: int = 0, step_ptr: Optional[torch.Tensor] = None):
+    """(z_t, level [B], eps): z_t = alpha_t x0 + sigma_t eps at every sample's own step.  ``eps`` None: Philox normals keyed by
+    (seed, b + sample_offset, step), ``step_ptr`` (a device counter) replacing ``step``; they are returned."""
+    B, S, Cn, N = _distill_args(x0, table, steps, eps)
+    draw = eps is None
+    eps = torch.empty_like(x0) if draw else eps
+    z_t, level = torch.empty_like(x0), torch.empty(B, dtype=torch.float32, device=x0.device)
+    with torch.cuda.device(x0.device):
+        _lib.check(_lib.get_lib().smd_distill_noise(_ptr(x0), B, S, Cn, _ptr(table), N, _ptr(steps), _ptr(eps), int(draw),
+                                                    seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, int(sample_offset),
+                                                    int(step) & 0xFFFFFFFF, _ptr(step_ptr), _ptr(z_t), _ptr(level), _stream()),
+                   "distill_noise")
+    return z_t, level, eps
+
+
+def distill_mid(z_t: torch.Tensor, out1: torch.Tensor, table: torch.Tensor, steps: torch.Tensor):
+    """(x1, z_m, level [B]): the teacher's first strided step t -> m from its output ``out1`` at z_t."""
+    B, S, Cn, N = _distill_args(z_t, table, steps, out1)
+    x1, z_m = torch.empty_like(z_t), torch.empty_like(z_t)
+    level = torch.empty(B, dtype=torch.float32, device=z_t.device)
+    with torch.cuda.device(z_t.device):
+        _lib.check(_lib.get_lib().smd_distill_mid(_ptr(z_t), _ptr(out1), B, S, Cn, _ptr(table), N, _ptr(steps), _ptr(x1), _ptr(z_m),
+                                                  _ptr(level), _stream()), "distill_mid")
+    return x1, z_m, level
+
+
+def distill_loss(x1: torch.Tensor, z_m: torch.Tensor, out2: torch.Tensor, z_t: torch.Tensor, pred: torch.Tensor, table: torch.Tensor,
+                 steps: torch.Tensor, prediction, inv_global_count: float, iw: Optional[torch.Tensor] = None,
+                 want_target: bool = False):
+    """(loss_per_sample [B], weight_per_sample [B], dpred, target or None) of a student of kind ``prediction`` whose output at
+    z_t is ``pred``: the target is x~ = w1 x1 + w2 x2 in the student's output space, x2 the teacher's estimate from ``out2`` at
+    z_m; the loss is the unweighted mean, dpred carries the weight and ``inv_global_count`` = 1 / (global batch * S * C)."""
+    B, S, Cn, N = _distill_args(x1, table, steps, z_m, out2, z_t, pred)
+    kind = _sched.prediction_kind(prediction)
+    if iw is not None and (iw.dtype != torch.float32 or iw.numel() != B or not iw.is_contiguous() or iw.device != x1.device):
+        raise ValueError(f"distill_loss: iw fp32 [{B}] on {x1.device}")
+    loss = torch.empty(B, dtype=torch.float32, device=x1.device)
+    weight = torch.empty(B, dtype=torch.float32, device=x1.device)
+    dpred = torch.empty_like(x1)
+    target = torch.empty_like(x1) if want_target else None
+    with torch.cuda.device(x1.device):
+        _lib.check(_lib.get_lib().smd_distill_loss(_ptr(x1), _ptr(z_m), _ptr(out2), _ptr(z_t), _ptr(pred), kind, B, S, Cn, _ptr(table),
+                                                   N, _ptr(steps), _ptr(iw), float(inv_global_count), _ptr(loss), _ptr(weight),
+                                                   _ptr(dpred), _ptr(target), _stream()), "distill_loss")
+    return loss, weight, dpred, target

@@ -285,6 +285,15 @@ ENGINE_FLAGS: List[FlagDef] = [
     _D("timestep_sampler", "enum", "uniform", "train_ncsn --loss=ddpm: how training timesteps are drawn, uniform (the reference) "
        "or loss_second_moment = p_t ~ sqrt(E[L_t^2]) from a ten-deep loss history with the loss re-weighted by 1 / (n p_t) "
        "(Nichol & Dhariwal 2021; single process only; DESIGN.md section 25).", ("uniform", "loss_second_moment")),
+    _D("distill_from", "string", "", "train_ncsn --loss=ddpm: progressive distillation (Salimans & Ho 2022; DESIGN.md section 27).  A "
+       "safetensors checkpoint file, or a directory whose newest checkpoint is taken: the frozen teacher.  The student starts from "
+       "its parameters and is trained so that one strided step lands where two of the teacher's land; its walk of --distill_steps "
+       "timesteps is recorded in the checkpoint and sample_ncsn.py walks it.  The teacher's kind and walk come from its metadata; "
+       "--prediction is the student's kind.  Single process, bf16, uniform timestep draw, --loss_weighting=none."),
+    _D("distill_steps", "int", 0, "--distill_from: N, the student's number of sampler steps.  The teacher's walk must have 2N "
+       "timesteps: evenly spaced ones for a teacher that was not distilled itself, else the walk its checkpoint records."),
+    _D("distill_weighting", "enum", "truncated_snr", "--distill_from: loss weight of a student step, truncated_snr = max(SNR, 1) on "
+       "the x-space error written in the student's output space, or none.", ("truncated_snr", "none")),
     _D("resume", "bool", False, "train_ncsn: start from the newest checkpoint under --model_dir (parameters, optimiser state, EMA, "
        "early stopping and, from a safetensors checkpoint, the timestep sampler's tables) instead of a fresh initialisation."),
     _D("ckpt_format", "enum", "safetensors", "Checkpoint file format written by train_ncsn: safetensors, or the "

@@ -160,6 +160,11 @@ _SIGS = {
                                   c_void, c_u32, c_void, c_void, c_void]),
     "smd_bound_terms": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_float, c_void, c_void,
                                   c_void, c_void, c_void]),
+    "smd_distill_noise": (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, C.c_int, c_u32, c_u32, c_u32,
+                                    c_u32, c_void, c_void, c_void, c_void]),
+    "smd_distill_mid": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, c_void, c_void, c_void]),
+    "smd_distill_loss": (C.c_int, [c_void, c_void, c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void,
+                                   c_void, C.c_float, c_void, c_void, c_void, c_void, c_void]),
     "smd_set_tuning": (C.c_int, [C.c_char_p, C.c_int]),
     "smd_set_timestep": (C.c_int, [c_void, c_i32, c_void]),
     "smd_gemm_bf16_nt": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_int,

@@ -1058,7 +1058,7 @@ def _walk_ld_metrics(model: Model, betas, taus, mp):
 def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, infill=False, infill_samples=None,
                      infill_masks=None, *, noises: Optional[Callable] = None, infill_noises: Optional[Callable] = None,
                      use_graph: bool = True, sample_offset: int = 0, global_num_samples: Optional[int] = None, order: int = 1,
-                     spacing: str = "uniform", prediction="eps"):
+                     spacing: str = "uniform", prediction="eps", timesteps=None):
     """The generalised non-Markovian sampler of Song et al. 2021 (DDIM) on ``steps`` evenly spaced timesteps of the schedule
     (schedule.stride_timesteps) instead of all of them: ``steps`` network evaluations from the same checkpoint.  ``eta`` scales
     the noise of every iteration (0: deterministic, 1: the DDPM posterior's variance).  Returns (state, collection (41, ...),
@@ -1073,7 +1073,10 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
     "multistep", keyed by (iterations, order, spacing) AND the timesteps themselves: on the lambda grid two values of ``steps``
     can snap to the same number of iterations on different timesteps.  Order 1 on the lambda grid keys its "strided" entry the
     same way; the defaults are the strided walk, and its key, as they were.
-    ``prediction`` "x0" / "v": the tables' first two columns are that kind's (section 26); a non-eps kind is part of the cache key."""
+    ``prediction`` "x0" / "v": the tables' first two columns are that kind's (section 26); a non-eps kind is part of the cache key.
+    ``timesteps``: an explicit strictly descending walk within [0, T), e.g. the walk a distilled student was trained on
+    (``schedule.distill_walk``; section 27), instead of the ``steps`` evenly spaced ones; ``steps`` must then be None, 0 or
+    the walk's length.  The walk is part of the cache key, as the lambda grid's is; without it every key is as it was."""
     nT = len(betas)
     pk = () if _sched.prediction_kind(prediction) == 0 else (("prediction", _sched.prediction_kind(prediction)),)
     if order not in (1, 2):
@@ -1082,8 +1085,19 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
         raise ValueError(f"spacing={spacing!r}: 'uniform' (in t) or 'logsnr' (in lambda)")
     if order == 2 and float(eta) != 0.0:
         raise ValueError(f"order=2 is a deterministic solver: eta must be 0, got {eta}")
-    taus = _sched.stride_timesteps(nT, steps) if spacing == "uniform" else _sched.logsnr_timesteps(nT, steps, betas)
+    if timesteps is not None:
+        taus = np.asarray([int(t) for t in timesteps], dtype=np.int64)
+        if len(taus) == 0 or taus[0] >= nT or taus[-1] < 0 or np.any(np.diff(taus) >= 0):
+            raise ValueError(f"timesteps: a walk is strictly descending within [0, {nT}), got {[int(t) for t in taus]}")
+        if steps not in (None, 0) and int(steps) != len(taus):
+            raise ValueError(f"steps={steps} contradicts the explicit walk of {len(taus)} timesteps")
+        if spacing != "uniform":
+            raise ValueError(f"spacing={spacing!r} chooses the timesteps itself: it cannot be combined with an explicit walk")
+    else:
+        taus = _sched.stride_timesteps(nT, steps) if spacing == "uniform" else _sched.logsnr_timesteps(nT, steps, betas)
     walk = [int(t) for t in taus]
+    # an explicit walk that IS the evenly spaced one shares that walk's graphs and device tables
+    explicit = timesteps is not None and not (2 <= len(walk) <= nT and walk == [int(t) for t in _sched.stride_timesteps(nT, len(walk))])
     kw = dict(collect=True, infill=infill, infill_samples=infill_samples, infill_masks=infill_masks, noises=noises,
               infill_noises=infill_noises, use_graph=use_graph, sample_offset=sample_offset, global_num_samples=global_num_samples,
               prediction=prediction)
@@ -1091,12 +1105,14 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
         coef, plan = _sched.strided_coefficient_table(betas, taus, eta, prediction=prediction)
         # on the lambda grid the number of iterations does not name the timesteps (K = 19 and K = 20 both snap to 18): the key
         # carries the walk itself, because a reused entry keeps its device tables
-        key = ("strided", len(walk), float(eta)) + ((spacing, tuple(walk)) if spacing != "uniform" else ()) + pk
+        key = (("strided", len(walk), float(eta)) + ((spacing, tuple(walk)) if spacing != "uniform" else ())
+               + (("walk", tuple(walk)) if explicit else ()) + pk)
         x, collection, mp = _strided_walk("strided", rng, model, betas, init, walk, coef, plan, key, **kw)
     else:
         coef, plan = _sched.multistep_coefficient_table(betas, taus, order, prediction=prediction)
         x, collection, mp = _strided_walk("multistep", rng, model, betas, init, walk, coef, plan,
-                                          ("multistep", len(walk), int(order), spacing, tuple(walk)) + pk, multistep=True, **kw)
+                                          ("multistep", len(walk), int(order), spacing, tuple(walk)) + pk,
+                                          multistep=True, **kw)
     return x, collection, _walk_ld_metrics(model, betas, taus, mp)
 
 
@@ -1212,13 +1228,16 @@ def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip
 def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400, sampling="ald", epsilon=1e-3,
            steps=100, denoise=True, *, sample_offset: int = 0, use_graph: bool = True,
            global_num_samples: Optional[int] = None, ddim_steps: int = 0, ddim_eta: float = 0.0, ddim_order: int = 1,
-           ddim_spacing: str = "uniform", prediction="eps"):
+           ddim_spacing: str = "uniform", prediction="eps", ddim_timesteps=None):
     """train_ncsn.py:499-551.  'ddpm': N(0,1) init + diffusion_dynamics.  'ald' / 'cas': uniform(-sqrt(12)/2, sqrt(12)/2)
     init (:542-547) + annealed / consistent Langevin dynamics with the score network ``scorenet``.  The reference unpacks
     three values from every sampler although consistent_langevin_dynamics returns two (a ValueError upstream); here 'cas'
     returns a two-entry collection [init, final state].  ``ddim_steps`` > 0 ('ddpm' only): the same initialisation, then the
     strided walk ``strided_dynamics(..., ddim_steps, ddim_eta, order=ddim_order, spacing=ddim_spacing)`` instead of every timestep.
-    ``prediction`` "x0" / "v" ('ddpm' only): what the network's output means."""
+    ``prediction`` "x0" / "v" ('ddpm' only): what the network's output means.  ``ddim_timesteps``: an
+    explicit descending walk for the strided sampler (a distilled student's, section 27) instead of ``ddim_steps`` evenly spaced ones."""
+    if ddim_timesteps is not None and not ddim_steps:
+        ddim_steps = len(ddim_timesteps)
     if sampling not in ("ddpm", "ald", "cas"):
         raise ValueError(f"Unknown sampling algorithm: {sampling}")
     if sampling != "ddpm" and _sched.prediction_kind(prediction) != 0:
@@ -1262,7 +1281,7 @@ def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400
         generated, collection, ld_metrics = strided_dynamics(ld_rng, scorenet, sigmas, init, ddim_steps, ddim_eta,
                                                              sample_offset=sample_offset, use_graph=use_graph,
                                                              global_num_samples=global_num_samples, order=ddim_order,
-                                                             spacing=ddim_spacing, prediction=prediction)
+                                                             spacing=ddim_spacing, prediction=prediction, timesteps=ddim_timesteps)
         return generated, collection, collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = diffusion_dynamics(ld_rng, scorenet, sigmas, init, epsilon, steps, denoise,
                                                            False, sample_offset=sample_offset, use_graph=use_graph,

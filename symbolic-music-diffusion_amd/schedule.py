@@ -260,6 +260,97 @@ def multistep_coefficient_table(betas: np.ndarray, taus, order: int, clip: float
     return coef, plan
 
 
+# ------------------------------------------------------------------ progressive distillation
+DISTILL_COLUMNS = 16      # floats per row of the distillation table: one 64-byte row per student step
+DISTILL_WEIGHTINGS = ("truncated_snr", "none")
+DISTILL_COLUMN_NAMES = ("c0_t", "c1_t", "a", "b", "clip", "alpha_t", "sigma_t", "alpha_m", "c0_m", "c1_m", "w1", "w2", "weight",
+                        "inv_sigma_t")
+
+
+def _check_walk(T: int, walk, what: str) -> np.ndarray:
+    w = np.asarray(walk, dtype=np.int64).reshape(-1)
+    if len(w) == 0 or w[0] >= T or w[-1] < 0 or np.any(np.diff(w) >= 0):
+        raise ValueError(f"{what}: a walk is strictly descending within [0, {T}), got {[int(t) for t in w]}")
+    return w
+
+
+def distill_walk(T: int, N: int, teacher_walk=None):
+    """(teacher_walk, student_walk) of one round of progressive distillation (Salimans & Ho 2022) to a student of ``N`` steps: the
+    teacher's descending walk of 2N timesteps -- ``stride_timesteps(T, 2N)`` in the first round, the walk its checkpoint
+    records later -- and every second entry of it, ``teacher_walk[0::2]``.  Both end at the clean level, which is not listed."""
+    T, N = int(T), int(N)
+    if N < 1:
+        raise ValueError(f"distill_walk: a student takes N >= 1 steps, got {N}")
+    if teacher_walk is None:
+        if 2 * N > T:
+            raise ValueError(f"distill_walk: a student of {N} steps needs a teacher walk of {2 * N} timesteps, the schedule has {T}")
+        tw = np.asarray(stride_timesteps(T, 2 * N), dtype=np.int64)
+    else:
+        tw = _check_walk(T, teacher_walk, "distill_walk")
+    if len(tw) != 2 * N:
+        raise ValueError(f"distill_walk: a student of {N} steps needs a teacher walk of {2 * N} timesteps, got {len(tw)}")
+    return tw.copy(), tw[0::2].copy()
+
+
+def distill_weights(ap, walk, kind, weighting: str = "truncated_snr") -> np.ndarray:
+    """float64 loss weight of every step of the student walk ``walk`` (timesteps into the cumulative alphas ``ap``), for a
+    student whose output is ``kind``.  "none": 1.  "truncated_snr" (Salimans & Ho 2022, section 4): max(SNR, 1) on the error in
+    x space, written in the student's output space -- x0: max(SNR, 1); eps: max(1, 1 / SNR), since eps_hat - eps =
+    -sqrt(SNR) (x_hat - x); v: max(SNR, 1) / (SNR + 1), since v_hat - v = -sqrt(SNR + 1) (x_hat - x).  SNR = ap / (1 - ap)."""
+    if weighting not in DISTILL_WEIGHTINGS:
+        raise ValueError(f"distill_weights: weighting must be one of {DISTILL_WEIGHTINGS}, got {weighting!r}")
+    k = prediction_kind(kind)
+    ap_t = np.asarray(ap, dtype=np.float64)[np.asarray(walk, dtype=np.int64)]
+    if weighting == "none":
+        return np.ones_like(ap_t)
+    snr = ap_t / (1.0 - ap_t)
+    if k == 1:
+        return np.maximum(snr, 1.0)
+    if k == 0:
+        return np.maximum(1.0, 1.0 / snr)
+    return np.maximum(snr, 1.0) / (snr + 1.0)
+
+
+def distill_tables(betas: np.ndarray, teacher_walk, teacher_prediction="eps", student_prediction="v",
+                   weighting: str = "truncated_snr", clip: float = 1.0):
+    """The table of the distillation kernels for the teacher walk ``teacher_walk`` (2N timesteps, descending) and a dict of its
+    float64 originals.  Student step k has the levels t = walk[2k], m = walk[2k + 1] and u = walk[2k + 2] (clean, ap = 1, after
+    the last).  float32 [N][16], rounded once from float64:
+
+      c0_t, c1_t, a, b, clip, alpha_t, sigma_t, alpha_m, c0_m, c1_m, w1, w2, weight, 1 / sigma_t, 0, 0
+
+    (c0, c1) are ``x0_coefficients`` of the TEACHER's kind at t and at m, (a, b) ``strided_coefficients`` at eta = 0 for t -> m,
+    alpha = sqrt(ap), sigma = sqrt(1 - ap), weight = ``distill_weights`` of the STUDENT's kind.  (w1, w2) is the convex form of
+    the target of Salimans & Ho: with (a', b') the coefficients of m -> u and r = sigma_u / sigma_t = b' b,
+    x~ = (z_u - r z_t) / (alpha_u - r alpha_t) = w1 x1 + w2 x2, w2 = a' / D, w1 = a b' / D, D = alpha_u - r alpha_t = a' + a b'.
+    D is formed as that sum, so w1 + w2 = 1 to rounding however fine the walk; the last step has b' = 0: (w1, w2) = (0, 1)."""
+    tw = _check_walk(len(betas), teacher_walk, "distill_tables")
+    if len(tw) % 2:
+        raise ValueError(f"distill_tables: a teacher walk has an even number of timesteps, got {len(tw)}")
+    if not float(clip) > 0:
+        raise ValueError(f"distill_tables: clip={clip} must be positive (inf: no clamp)")
+    ap = alphas_cumprod(betas).astype(np.float64)
+    co = strided_coefficients(betas, tw, 0.0)
+    t, m = tw[0::2], tw[1::2]
+    a, b, a2, b2 = co["a"][0::2], co["b"][0::2], co["a"][1::2], co["b"][1::2]
+    ap_u = np.concatenate([ap[tw[2::2]], np.ones(1)])
+    alpha_t, sigma_t = np.sqrt(ap[t]), np.sqrt(1.0 - ap[t])
+    alpha_u, sigma_u = np.sqrt(ap_u), np.sqrt(1.0 - ap_u)
+    c0_t, c1_t = x0_coefficients(ap[t], teacher_prediction)
+    c0_m, c1_m = x0_coefficients(ap[m], teacher_prediction)
+    n1, n2 = a * b2, a2
+    D = n1 + n2
+    ref = dict(c0_t=c0_t, c1_t=c1_t, a=a, b=b, clip=np.full(len(t), float(clip)), alpha_t=alpha_t, sigma_t=sigma_t,
+               alpha_m=np.sqrt(ap[m]), c0_m=c0_m, c1_m=c1_m, w1=n1 / D, w2=n2 / D,
+               weight=distill_weights(ap, t, student_prediction, weighting), inv_sigma_t=1.0 / sigma_t)
+    table = np.zeros((len(t), DISTILL_COLUMNS), dtype=np.float32)
+    for j, name in enumerate(DISTILL_COLUMN_NAMES):
+        table[:, j] = ref[name]
+    ref.update(a2=a2, b2=b2, D=D, r=sigma_u / sigma_t, alpha_u=alpha_u, sigma_u=sigma_u, sigma_m=np.sqrt(1.0 - ap[m]),
+               t=t.copy(), m=m.copy(), u=np.concatenate([tw[2::2], -np.ones(1, dtype=np.int64)]))
+    return np.ascontiguousarray(table), ref
+
+
 # ------------------------------------------------------------------ variational bound (DESIGN.md section 17)
 def bound_tables(betas: np.ndarray, timesteps, clip: float = 1.0, prediction="eps") -> dict:
     """Everything the per-timestep variational bound (Ho et al. 2020, eq. 5) needs from the schedule, for the timesteps

@@ -387,6 +387,123 @@ def _train_step_generic(objective, batch, optimizer: Optimizer, sigmas, rng, lea
     return optimizer, LazyMetrics(loss=loss.detach(), grad=eng.metrics[1], lr=eng.metrics[2])
 
 
+# ------------------------------------------------------------------ progressive distillation
+from .schedule import DISTILL_WEIGHTINGS  # noqa: E402  (one list: the flag's enum, the tables' check)
+
+
+def validate_distill_options(loss: str = "ddpm", loss_weighting: str = "none", timestep_sampler: str = "uniform",
+                             world_size: int = 1, dtype: str = "bf16", ckpt_format: str = "safetensors",
+                             distill_weighting: str = "truncated_snr", distill_steps: int = 0) -> None:
+    """The combinations --distill_from is trained with; anything else raises a ValueError that says what is refused.
+    train_ncsn.py calls this before it touches a device."""
+    if loss != "ddpm":
+        raise ValueError(f"--distill_from applies to --loss=ddpm only (got --loss={loss}): the teacher's two strided steps are "
+                         "steps of the DDPM sampler")
+    if timestep_sampler != "uniform":
+        raise ValueError(f"--distill_from draws the student's steps uniformly: --timestep_sampler={timestep_sampler} is refused")
+    if loss_weighting != "none":
+        raise ValueError(f"--distill_from takes its loss weight from --distill_weighting: --loss_weighting={loss_weighting} is "
+                         "refused")
+    if ckpt_format == "flax":
+        raise ValueError("--distill_from needs --ckpt_format=safetensors: the student's walk is recorded in the safetensors "
+                         "metadata, which a flax checkpoint does not have")
+    if world_size > 1:
+        raise ValueError(f"--distill_from is single-process only (world size {world_size}): the distillation step has no "
+                         "gradient all-reduce")
+    if dtype != "bf16":
+        raise ValueError(f"--distill_from trains the student in bf16 (got --dtype={dtype})")
+    if distill_weighting not in DISTILL_WEIGHTINGS:
+        raise ValueError(f"--distill_weighting must be one of {DISTILL_WEIGHTINGS}, got {distill_weighting!r}")
+    if int(distill_steps) < 1:
+        raise ValueError(f"--distill_from needs --distill_steps=N with N >= 1 (the student's number of sampler steps), got "
+                         f"{distill_steps}")
+
+
+class DistillTables:
+    """What one round of progressive distillation needs from the schedule, on the device: the [N][16] table of
+    ``schedule.distill_tables`` and a uniform (p, cdf) over the student's N steps for ``smd_timestep_draw``.  ``teacher_walk``
+    (2N timesteps) and ``student_walk`` (N) are the host lists; ``ref`` holds the table's float64 originals."""
+
+    def __init__(self, betas, teacher_walk, teacher_prediction: str, student_prediction: str, weighting: str = "truncated_snr",
+                 device="cuda:0", clip: float = 1.0):
+        from . import schedule as _sched
+        self.betas = np.asarray(betas, dtype=np.float32)
+        if len(teacher_walk) % 2:
+            raise ValueError(f"DistillTables: a teacher walk has an even number of timesteps, got {len(teacher_walk)}")
+        tw, sw = _sched.distill_walk(len(self.betas), len(teacher_walk) // 2, teacher_walk)
+        self.teacher_walk, self.student_walk = [int(t) for t in tw], [int(t) for t in sw]
+        self.teacher_prediction = _sched.PREDICTIONS[_sched.prediction_kind(teacher_prediction)]
+        self.student_prediction = _sched.PREDICTIONS[_sched.prediction_kind(student_prediction)]
+        self.weighting = weighting
+        self.host, self.ref = _sched.distill_tables(self.betas, tw, self.teacher_prediction, self.student_prediction, weighting, clip)
+        self.N = len(sw)
+        self.device = torch.device(device)
+        self.table = torch.from_numpy(self.host).to(self.device)
+        self.p = torch.full((self.N,), 1.0 / self.N, dtype=torch.float32, device=self.device)
+        self.cdf = torch.cumsum(self.p.double(), 0).float()
+
+    def draw(self, B: int, seed: int, sample_offset: int = 0, step_ptr: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [B] steps in [0, N), uniform: Philox keyed by (seed, b + sample_offset, *step_ptr) on the timestep stream"""
+        from . import lib as _lib
+        steps = torch.empty(B, dtype=torch.int32, device=self.device)
+        if getattr(self, "_iw", None) is None or self._iw.numel() != B:       # the entry point always writes the weights: all 1 here
+            self._iw = torch.empty(B, dtype=torch.float32, device=self.device)
+        iw = self._iw
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.get_lib().smd_timestep_draw(
+                self.cdf.data_ptr(), self.p.data_ptr(), self.N, 0, B, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                int(sample_offset), 0, None if step_ptr is None else step_ptr.data_ptr(), None, steps.data_ptr(), iw.data_ptr(),
+                torch.cuda.current_stream().cuda_stream), "timestep_draw")
+        return steps
+
+
+def distill_step(batch, optimizer: Optimizer, teacher: Model, tables: DistillTables, rng: PRNGKey, learning_rate: float, *,
+                 steps=None, eps=None, loss_weights=None, prediction: Optional[str] = None, grad_clip: float = 1.0,
+                 mu: float = 0.999, lr_gamma: float = 1.0, lr_interval: int = 1):
+    """One optimisation step of progressive distillation (Salimans & Ho 2022): the student
+    (``optimizer.target``) is trained so that ONE strided step from z_t at level t = walk[2k] lands where the frozen ``teacher``'s
+    TWO strided steps t -> m -> u land.  On one stream: draw the steps k (unless ``steps`` int32 [B] is given), noise the batch to
+    z_t (``eps`` given or Philox), teacher(z_t), the teacher's first step, teacher(z_m), student(z_t) in the training workspace,
+    target + loss + d loss / d pred, the student's backward pass, the fused clip + Adam (+ EMA) sweep.  ``teacher`` is an inference
+    model with parameters of its own; it is read only.  ``prediction`` is the student's kind (default: the tables').
+    ``loss_weights`` [B] multiplies the tables' per-step weight.  Returns (optimizer, metrics {'loss' (weighted),
+    'loss_unweighted', 'grad', 'lr'}) as LazyMetrics: nothing synchronises with the host."""
+    from . import engine as _eng
+    from . import schedule as _sched
+    eng = optimizer.engine
+    kind = tables.student_prediction if prediction is None else _sched.PREDICTIONS[_sched.prediction_kind(prediction)]
+    if kind != tables.student_prediction:
+        raise ValueError(f"distill_step: prediction={kind!r}, but the tables carry the loss weights of a {tables.student_prediction!r} "
+                         "student")
+    if eng.cfg.dtype != "bf16":
+        raise ValueError(f"distill_step: the student trains in bf16, got dtype={eng.cfg.dtype!r}")
+    if teacher.engine.params.data_ptr() == eng.params.data_ptr():
+        raise ValueError("distill_step: the teacher shares the student's parameter buffer; it needs a frozen copy of its own")
+    if tuple(teacher.cfg.sample_shape) != tuple(eng.cfg.sample_shape):
+        raise ValueError(f"distill_step: teacher samples {teacher.cfg.sample_shape}, student samples {eng.cfg.sample_shape}")
+    batch = torch.as_tensor(batch).to(eng.device, torch.float32).contiguous()
+    B = batch.shape[0]
+    eng.set_prediction(kind)
+    eng.set_opt_overlap(0)
+    if steps is None:
+        k = tables.draw(B, int(rng.seed), step_ptr=eng.step_counter)
+    else:
+        k = torch.as_tensor(steps).to(eng.device, torch.int32).contiguous()
+    e = None if eps is None else torch.as_tensor(eps).to(eng.device, torch.float32).contiguous()
+    iw = None if loss_weights is None else torch.as_tensor(loss_weights).to(eng.device, torch.float32).contiguous()
+    z_t, level_t, _ = _eng.distill_noise(batch, tables.table, k, e, seed=int(rng.seed), step_ptr=eng.step_counter)
+    out1 = teacher.engine.forward(z_t, level_t)
+    x1, z_m, level_m = _eng.distill_mid(z_t, out1, tables.table, k)
+    out2 = teacher.engine.forward(z_m, level_m)
+    pred = eng.forward_train(z_t, level_t)
+    inv = 1.0 / (B * float(np.prod(eng.cfg.sample_shape)))
+    per_sample, weight, dpred, _ = _eng.distill_loss(x1, z_m, out2, z_t, pred, tables.table, k, kind, inv, iw)
+    eng.backward_from(dpred)
+    eng.optimizer_step(learning_rate, lr_gamma, lr_interval, grad_clip, mu, 1.0)
+    return optimizer, LazyMetrics(loss=(weight * per_sample).mean(), loss_unweighted=per_sample.mean(), grad=eng.metrics[1],
+                                  lr=eng.metrics[2])
+
+
 def eval_step(objective, batch, model: Model, sigmas, rng: PRNGKey, continuous_noise: bool = True):
     """train_ncsn.py:206-221: summed loss of one batch."""
     return objective(batch, model, sigmas, rng, continuous_noise, "sum")

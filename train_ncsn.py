@@ -64,8 +64,43 @@ def model_shape(FLAGS, slice_idx):
     return tuple(shape)
 
 
-def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world=1, verbose=True):
-    """train_ncsn.py:291-496."""
+def resolve_distillation(FLAGS, world=1):
+    """--distill_from / --distill_steps / --distill_weighting settled before a device is touched: None without --distill_from,
+    else dict(path, teacher_prediction, teacher_walk, student_walk, weighting).  The teacher's kind and walk come from its
+    safetensors metadata; every refusal is a SystemExit of one sentence."""
+    from smd_amd import checkpoint, flax_io
+    from smd_amd.trainer import validate_distill_options
+    if not FLAGS.distill_from:
+        given = [f"--{n}" for n in ("distill_steps", "distill_weighting") if FLAGS.is_present(n)]
+        if given:
+            raise SystemExit(f"{', '.join(given)}: options of progressive distillation, give --distill_from")
+        return None
+    try:
+        validate_distill_options(FLAGS.loss, FLAGS.loss_weighting, FLAGS.timestep_sampler, world, FLAGS.dtype, FLAGS.ckpt_format,
+                                 FLAGS.distill_weighting, FLAGS.distill_steps)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    src = os.path.expanduser(FLAGS.distill_from)
+    path = src if os.path.isfile(src) else checkpoint.latest_checkpoint(src)
+    if path is None:
+        raise SystemExit(f"--distill_from={FLAGS.distill_from}: no checkpoint there")
+    if flax_io.is_flax_file(path):
+        raise SystemExit(f"--distill_from={FLAGS.distill_from}: {path} is a flax-format file; the teacher is loaded from a safetensors "
+                         "checkpoint, whose metadata names its kind and walk")
+    teacher_prediction = checkpoint.checkpoint_prediction(path) or "eps"
+    recorded = checkpoint.checkpoint_distill_walk(path)
+    try:
+        teacher_walk, student_walk = schedule.distill_walk(FLAGS.num_sigmas, FLAGS.distill_steps, recorded)
+    except ValueError as e:
+        where = f"{path} records a walk of {len(recorded)} timesteps" if recorded else f"{path} records no walk (evenly spaced timesteps)"
+        raise SystemExit(f"--distill_steps={FLAGS.distill_steps}: {e} ({where})")
+    return dict(path=path, teacher_prediction=teacher_prediction, teacher_walk=[int(t) for t in teacher_walk],
+                student_walk=[int(t) for t in student_walk], weighting=FLAGS.distill_weighting)
+
+
+def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world=1, verbose=True, distill=None):
+    """train_ncsn.py:291-496.  ``distill`` (resolve_distillation): the train step is trainer.distill_step against the frozen
+    teacher; everything around it -- logging, evaluation, snapshots, the LR schedule -- is the loop's own."""
     from smd_amd import checkpoint, ncsn, train_utils
     from smd_amd.trainer import GradComm, create_optimizer, evaluate, train_step
 
@@ -97,6 +132,25 @@ def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world
     # weighted training: min-SNR loss weights and / or the loss-aware timestep sampler
     train_options = {"loss_weighting": FLAGS.loss_weighting, "min_snr_gamma": FLAGS.min_snr_gamma,
                      "timestep_sampler": FLAGS.timestep_sampler, "prediction": FLAGS.prediction}
+    teacher = tables = None
+    if distill is not None:
+        from smd_amd.trainer import DistillTables
+        teacher = ncsn.create_model(model_rng, input_shape, model_kwargs, FLAGS.batch_size, architecture=FLAGS.architecture,
+                                    num_timesteps=len(sigmas), device=dev, dtype=FLAGS.dtype, init=False)
+        if not checkpoint.restore_checkpoint(distill["path"], teacher.engine, load_optimizer_state=False)[0]:
+            raise SystemExit(f"--distill_from: no checkpoint at {distill['path']}")
+        model.engine.params.copy_(teacher.engine.params)                    # the student starts as the teacher (--resume overrides)
+        model.engine.refresh_weights()
+        if optimizer.engine.ema is not None:
+            optimizer.engine.ema.copy_(model.params)
+        tables = DistillTables(sigmas, distill["teacher_walk"], distill["teacher_prediction"], FLAGS.prediction, distill["weighting"],
+                               device=dev)
+        train_options.update(distill_timesteps=checkpoint.format_walk(distill["student_walk"]),
+                             distill_teacher_steps=len(distill["teacher_walk"]))
+        if rank == 0:
+            log.info("distillation: teacher %s (%s, walk of %d timesteps) -> student of %d steps on %s (%s, weighting %s)",
+                     distill["path"], distill["teacher_prediction"], len(distill["teacher_walk"]), len(distill["student_walk"]),
+                     checkpoint.format_walk(distill["student_walk"]), FLAGS.prediction, distill["weighting"])
     sampler = None
     if FLAGS.timestep_sampler == "loss_second_moment":
         from smd_amd.trainer import TimestepSampler
@@ -140,13 +194,19 @@ def train(FLAGS, train_batches, valid_batches, sigmas, output_dir, rank=0, world
             rng, train_rng = ncsn.split(rng)                                      # :358
             global_step = step + epoch * train_batches.examples                   # :359
             # the stepped LR schedule (:340-342) is evaluated on the device from the update counter
-            optimizer, train_metrics = train_step(
-                objective, batch, optimizer, sigmas, train_rng, FLAGS.learning_rate,
-                grad_clip=FLAGS.grad_clip, mu=FLAGS.mu, comm=comm, lr_gamma=FLAGS.lr_gamma,
-                lr_interval=FLAGS.lr_schedule_interval, sample_offset=rank * FLAGS.batch_size,
-                global_batch=FLAGS.batch_size * world, continuous_noise=FLAGS.continuous_noise,
-                loss_weighting=FLAGS.loss_weighting, min_snr_gamma=FLAGS.min_snr_gamma, timestep_sampler=sampler,
-                prediction=FLAGS.prediction)
+            if distill is not None:
+                from smd_amd.trainer import distill_step
+                optimizer, train_metrics = distill_step(
+                    batch, optimizer, teacher, tables, train_rng, FLAGS.learning_rate, prediction=FLAGS.prediction,
+                    grad_clip=FLAGS.grad_clip, mu=FLAGS.mu, lr_gamma=FLAGS.lr_gamma, lr_interval=FLAGS.lr_schedule_interval)
+            else:
+                optimizer, train_metrics = train_step(
+                    objective, batch, optimizer, sigmas, train_rng, FLAGS.learning_rate,
+                    grad_clip=FLAGS.grad_clip, mu=FLAGS.mu, comm=comm, lr_gamma=FLAGS.lr_gamma,
+                    lr_interval=FLAGS.lr_schedule_interval, sample_offset=rank * FLAGS.batch_size,
+                    global_batch=FLAGS.batch_size * world, continuous_noise=FLAGS.continuous_noise,
+                    loss_weighting=FLAGS.loss_weighting, min_snr_gamma=FLAGS.min_snr_gamma, timestep_sampler=sampler,
+                    prediction=FLAGS.prediction)
             if FLAGS.ema:
                 ema = ema.update(optimizer.target)                                # :364-365 (fused: no-op)
 
@@ -225,6 +285,13 @@ def main(argv):
                                   prediction=FLAGS.prediction, sampling=FLAGS.sampling)
     except ValueError as e:
         raise SystemExit(str(e))
+    distill = resolve_distillation(FLAGS, world)
+    if FLAGS.resume:
+        from smd_amd import checkpoint
+        try:
+            checkpoint.check_resume_distill(FLAGS.model_dir, None if distill is None else distill["student_walk"])
+        except ValueError as e:
+            raise SystemExit(str(e))
     if FLAGS.timestep_sampler == "loss_second_moment" and FLAGS.ckpt_format == "flax" and rank == 0:
         log.info("--ckpt_format=flax has no place for the timestep sampler's tables: they are not saved, a resumed run restarts "
                  "its warm-up")
@@ -239,7 +306,7 @@ def main(argv):
     train_ds, eval_ds, _, _ = build_datasets(FLAGS, shape, f"cuda:{local_rank}", rank, world)
     noise_schedule = schedule.create_noise_schedule(FLAGS.sigma_begin, FLAGS.sigma_end, FLAGS.num_sigmas,
                                                     schedule=FLAGS.schedule_type)               # :574-577
-    train(FLAGS, train_ds, eval_ds, noise_schedule, FLAGS.model_dir, rank, world, verbose=FLAGS.verbose)
+    train(FLAGS, train_ds, eval_ds, noise_schedule, FLAGS.model_dir, rank, world, verbose=FLAGS.verbose, distill=distill)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
