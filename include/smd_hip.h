@@ -313,6 +313,54 @@ typedef struct smd_bound_io {
 } smd_bound_io;
 int smd_engine_bound_step(smd_engine* e, const smd_bound_io* io, void* stream);
 
+/* One iteration of the walk that estimates the statistic of the analytic (optimal) reverse variance of Bao et al. 2022
+ * (Analytic-DPM; no counterpart in the reference) on examples.  At t = *t_ptr:
+ *   smd_bound_noise    x_t = sqrt(ap_t) x0 + sqrt(1-ap_t) eps  -> x_t (fp32) and the engine's bf16 network input, as above
+ *   eps-net            out = model(x_t, sqrt(ap_t)), FiLM-table row t
+ *   smd_score_moments  sums[t][s][c] = sum over the batch of (A_t x_t + B_t out)^2, (A_t, B_t) = moment_table[t][0..1]: the
+ *                      network's output in eps units for any prediction kind; the last workgroup stores next_t[t] to *t_ptr
+ * eps_source, the key fields, the no-op for t outside [0, T) and the requirements (FiLM tables, an inference workspace, both
+ * architectures, options "fp8" and "fp32", T the engine's num_timesteps, 16-byte alignment of the table rows and, for
+ * data_channels % 4 == 0, of every fp32 array) are those of smd_engine_bound_step.  Row t of sums is WRITTEN, every element of
+ * it, never accumulated: the host adds batches and draws in float64.  partial is a workspace of
+ * ceil(B / SMD_MOMENT_CHUNK) * S * C floats. */
+#define SMD_MOMENT_CHUNK 8
+typedef struct smd_moment_io {
+  const float* x0;                 /* [B][S][C] examples (model space) */
+  float* x_t;                      /* [B][S][C] scratch: the noised examples of the current timestep */
+  float* eps;                      /* [B][S][C] the draw (read or written, see eps_source) */
+  int32_t* t_ptr;                  /* device timestep; replaced by next_t[t] */
+  const float* noise_table;        /* [T][4] (sqrt(ap), sqrt(1-ap), sqrt(1/ap), sqrt(1/ap - 1)): smd_bound_io's table */
+  const float* moment_table;       /* [T][4] (A, B, 0, 0) */
+  const int32_t* next_t;           /* [T] the walk: next timestep after t, -1 ends it */
+  int32_t T;
+  int32_t eps_source;              /* 0 explicit, 1 jax.random (threefry), 2 Philox */
+  uint32_t seed_lo, seed_hi, sample_offset;
+  const uint32_t* key_ptr;         /* Philox key in device memory ([2] words) or NULL = seed_lo / seed_hi */
+  const uint32_t* tf_keys;         /* eps_source 1: [T][2] key table */
+  int64_t tf_n_total;
+  float* partial;                  /* [ceil(B / SMD_MOMENT_CHUNK)][S][C] workspace */
+  float* sums;                     /* [T][S][C] */
+} smd_moment_io;
+int smd_engine_moment_step(smd_engine* e, const smd_moment_io* io, void* stream);
+
+/* smd_engine_strided_step with a PER-ELEMENT noise scale (the diagonal form of the analytic variance):
+ *   x' = a x0 + b x + coef4 * sig[iteration][s][c] * z
+ * coef and plan are smd_stride_plan's tables; column 4 of coef is now a 0/1 switch, and z is read / drawn (and sig read) only
+ * where it is not 0.  sig is one float32 [K][S][C] table shared by every sample, indexed by the plan's `iteration`; a row whose
+ * iteration is outside [0, K) is off the walk (a no-op).  z * sig is rounded once and a zero sig contributes +0, so a table
+ * filled with one constant sigma and coef4 = 1 gives the bits of smd_engine_strided_step with that sigma in column 4.  The
+ * draws (z_in, else tf_noise_keys row `iteration`, else Philox keyed by t), the infill blend, the bf16 network input, the
+ * collection row, metrics_partial[t], the last workgroup's store of next_t, the no-op for t outside [0, T) or off the walk,
+ * `part` and its refusal under option "fp32" are as for smd_engine_strided_step.  plan->T must be the engine's num_timesteps;
+ * the plan rows, and for data_channels % 4 == 0 every fp32 array, sig included, 16-byte aligned. */
+typedef struct smd_sigma_table {
+  const float* sig;                /* [K][S][C] */
+  int32_t K;
+} smd_sigma_table;
+int smd_engine_analytic_step(smd_engine* e, const smd_sample_io* io, const smd_stride_plan* plan, const smd_sigma_table* sig, int part,
+                             void* stream);
+
 /* One Langevin update of annealed_langevin_dynamics / consistent_langevin_dynamics (utils/ebm_utils.py:131-164, 231-253):
  *   next = x + alpha * grad + noise_coef * z;  with infill: next = next (1 - mask) + (infill_samples + infill_sigma * zi) mask.
  * grad = model(state, sigma) comes from smd_engine_forward.  z / zi: explicit arrays, else jax.random.normal(step_rng) /
@@ -575,6 +623,15 @@ int smd_bound_noise(const float* x0, int B, int S, int C, int Cp, const float* t
                     smd_bf16* xt_bf16, void* stream);
 int smd_bound_terms(const float* x0, const float* eps, const float* eps_hat, int B, int S, int C, const float* table, int T,
                     float clip, int32_t* t_ptr, const int32_t* next_t, uint32_t* arrive, float* partial, void* stream);
+/* The reduction of smd_engine_moment_step on explicit arrays: sums[t][s][c] = sum over b of (A x_t[b][s][c] + B out[b][s][c])^2
+ * with (A, B) = table[t][0..1] (table [T][4] fp32, 16-byte aligned), one FMA for eps_hat and one for its square, fp32.  The
+ * batch is summed in chunks of SMD_MOMENT_CHUNK rows into partial [ceil(B / SMD_MOMENT_CHUNK)][S][C] and a second launch
+ * adds the chunks in chunk order: no atomics on floats, two calls agree bitwise.  Only row t of sums [T][S][C] is written,
+ * every element of it; x_t and out are contiguous [B][S][C] (no padding columns are read); *t_ptr outside [0, T) makes the
+ * call a no-op that writes nothing.  next_t != NULL: the second launch's last workgroup stores next_t[t] to *t_ptr (arrive:
+ * one zeroed uint32, reset by the kernel).  For C % 4 == 0 all four arrays must be 16-byte aligned. */
+int smd_score_moments(const float* x_t, const float* out, int B, int S, int C, const float* table, int T, int32_t* t_ptr,
+                      const int32_t* next_t, uint32_t* arrive, float* partial, float* sums, void* stream);
 /* The three element-wise kernels of a progressive-distillation step (Salimans & Ho 2022) on explicit
  * arrays.  Every sample has a walk step of its own: steps [B] int32 in [0, N) picks its row of table [N][16] fp32 (16-byte
  * aligned; columns c0_t, c1_t, a, b, clip, alpha_t, sigma_t, alpha_m, c0_m, c1_m, w1, w2, weight, 1/sigma_t, 0, 0).  A step outside

@@ -90,7 +90,8 @@ def resolve_distill_walk(FLAGS):
     return walk
 
 
-def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sample_offset=0, global_num_samples=None, walk=None):
+def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sample_offset=0, global_num_samples=None, walk=None,
+                     analytic=None):
     """sample_ncsn.py:313-365."""
     from smd_amd import ncsn
     rng, sample_rng = ncsn.split(rng)
@@ -99,13 +100,14 @@ def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sampl
         model, sigmas, sample_rng, sample_shape, num_samples=num_samples, sampling=FLAGS.sampling,
         epsilon=FLAGS.ld_epsilon, steps=FLAGS.ld_steps, denoise=FLAGS.denoise, sample_offset=sample_offset,
         use_graph=FLAGS.graph, global_num_samples=global_num_samples, ddim_steps=FLAGS.ddim_steps, ddim_eta=FLAGS.ddim_eta,
-        ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS), ddim_timesteps=walk)
+        ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS), ddim_timesteps=walk,
+        analytic=analytic)
     torch.cuda.synchronize()
     log.info("Generated samples in %f seconds", time.time() - t0)
     return generated, collection, ld_metrics
 
 
-def infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=0, global_num_samples=None, walk=None):
+def infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=0, global_num_samples=None, walk=None, analytic=None):
     """sample_ncsn.py:189-242 (init ~ U[0,1) like :228: jax.random.uniform with --rng_impl=threefry, torch's device
     generator otherwise)."""
     from smd_amd import jax_random, ncsn
@@ -128,7 +130,7 @@ def infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=0, g
         generated, collection, ld_metrics = ncsn.strided_dynamics(
             ld_rng, model, sigmas, init, FLAGS.ddim_steps, FLAGS.ddim_eta, True, infill_samples=samples, infill_masks=masks,
             use_graph=FLAGS.graph, sample_offset=sample_offset, global_num_samples=global_num_samples, order=FLAGS.ddim_order,
-            spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS), timesteps=walk)
+            spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS), timesteps=walk, analytic=analytic)
         return generated, collection, ncsn.collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = ncsn.diffusion_dynamics(
         ld_rng, model, sigmas, init, FLAGS.ld_epsilon, FLAGS.ld_steps, FLAGS.denoise, True,
@@ -155,7 +157,8 @@ def diffusion_stochastic_encoder(samples, sigmas, rng, device="cuda:0", sample_o
 
 
 def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl, dev, use_graph=True, points=9, ddim_steps=0,
-                        ddim_eta=0.0, ddim_encode=False, ddim_order=1, ddim_spacing="uniform", prediction="eps", walk=None):
+                        ddim_eta=0.0, ddim_encode=False, ddim_order=1, ddim_spacing="uniform", prediction="eps", walk=None,
+                        analytic=None):
     """sample_ncsn.py:425-435 + diffusion_decoder (:269-310) for this rank's rows [lo, hi): goals = roll(starts, 1); both are
     encoded with the same key (the same noise); every one of the 9 interpolated latents is decoded with the SAME
     ld_rng = split(PRNGKey(sample_seed), 3)[1].  Returns (generated (9, n, ...), collection (9, 41, n, ...), collated metrics).
@@ -180,7 +183,7 @@ def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl,
         if ddim_steps:
             g, c, ld = ncsn.strided_dynamics(ld_rng, model, sigmas, z, ddim_steps, ddim_eta, use_graph=use_graph, sample_offset=lo,
                                              global_num_samples=num, order=ddim_order, spacing=ddim_spacing, prediction=prediction,
-                                             timesteps=walk)
+                                             timesteps=walk, analytic=analytic)
         else:
             g, c, ld = ncsn.diffusion_dynamics(ld_rng, model, sigmas, z, use_graph=use_graph, sample_offset=lo, global_num_samples=num,
                                                prediction=prediction)
@@ -325,6 +328,68 @@ def check_bound_flags(FLAGS):
         raise SystemExit(f"--bound_steps={steps}: 0 (every timestep) or from 2 to --num_sigmas={FLAGS.num_sigmas} timesteps")
 
 
+def check_analytic_flags(FLAGS, world=1):
+    """the refusals of --analytic_variance / --analytic_examples / --analytic_draws / --analytic_moments, before the GPU is touched
+    (after resolve_distill_walk: a recorded walk has set --ddim_steps)"""
+    if FLAGS.analytic_variance == "none":
+        used = [f"--{n}" for n in ("analytic_examples", "analytic_draws", "analytic_moments") if FLAGS.is_present(n)]
+        if used:
+            raise SystemExit(f"{', '.join(used)}: options of the analytic variance, give --analytic_variance=scalar or element")
+        return
+    flag = f"--analytic_variance={FLAGS.analytic_variance}"
+    if FLAGS.sampling != "ddpm":
+        raise SystemExit(f"{flag}: the optimal variance is that of a DDPM schedule, it needs --sampling=ddpm (got --sampling={FLAGS.sampling})")
+    if not FLAGS.ddim_steps:
+        raise SystemExit(f"{flag} belongs to the strided sampler: give --ddim_steps (or a distilled checkpoint, which records its "
+                         "walk); the every-timestep walk is --ddim_steps=--num_sigmas")
+    if FLAGS.ddim_order == 2:
+        raise SystemExit(f"{flag} with --ddim_order=2: the second-order solver is deterministic, it has no noise term to give a variance to")
+    if world > 1:
+        raise SystemExit(f"{flag} runs in a single process (the estimate is not sharded): got WORLD_SIZE={world}")
+    if FLAGS.analytic_variance == "element" and FLAGS.compute_bound:
+        raise SystemExit(f"{flag} with --compute_bound: the bound takes the scalar form only (per-element variances would need "
+                         "per-element sums); use --analytic_variance=scalar")
+    if FLAGS.analytic_examples is None or FLAGS.analytic_examples < 1:
+        raise SystemExit(f"--analytic_examples={FLAGS.analytic_examples}: {flag} estimates on at least one example")
+    if FLAGS.analytic_draws is None or FLAGS.analytic_draws < 1:
+        raise SystemExit(f"--analytic_draws={FLAGS.analytic_draws}: {flag} takes at least one draw per example")
+    if FLAGS.analytic_moments and not os.path.isfile(os.path.expanduser(FLAGS.analytic_moments)):
+        raise SystemExit(f"--analytic_moments={FLAGS.analytic_moments}: no such file")
+
+
+def analytic_moments(FLAGS, model, sigmas, walk, examples, bound_timesteps=None):
+    """--analytic_variance: the statistic g for every timestep the run needs -- the sampling walk and, with --compute_bound, the
+    bound's timesteps -- loaded from --analytic_moments or estimated on ``examples`` (a callable returning them, model space)
+    and written to {sampling_dir}/ncsn/analytic_moments.safetensors.  Returns (g [K][...], timesteps [K] ascending)."""
+    from smd_amd import analytic as A
+    from smd_amd import ncsn
+    want = A.run_metadata(FLAGS, _prediction(FLAGS), model.engine)
+    taus = A.resolve_walk(FLAGS, sigmas, walk)
+    need = np.unique(np.concatenate([taus] + ([np.asarray(bound_timesteps, dtype=np.int64)] if bound_timesteps is not None else [])))
+    shape = tuple(model.engine.cfg.sample_shape)
+    if FLAGS.analytic_moments:
+        path = os.path.expanduser(FLAGS.analytic_moments)
+        try:
+            g, ts, count, meta = A.load_moments(path)
+            A.check_moments(path, g, ts, meta, want, need, shape)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        log.info("analytic variance: loaded E[eps_hat^2] at %d timesteps (%d example-draws) from %s", len(ts), count, path)
+        return g, ts
+    t0 = time.time()
+    x0 = np.ascontiguousarray(examples(), dtype=np.float32)
+    rng = ncsn.split(ncsn.make_key(FLAGS.sample_seed, "philox"), num=5)[4]
+    g, count = ncsn.estimate_score_moments(model, sigmas, x0, need, draws=FLAGS.analytic_draws, rng=rng,
+                                           batch=min(256, len(x0)), prediction=_prediction(FLAGS), use_graph=FLAGS.graph)
+    model.drop_sampler_cache()
+    A.save_moments(os.path.join(FLAGS.sampling_dir, "ncsn", A.MOMENTS_FILE), g, need, count,
+                   dict(want, examples=str(len(x0)), draws=str(FLAGS.analytic_draws),
+                        example_source="synthetic" if FLAGS.synthetic else "dataset"))
+    log.info("analytic variance: E[eps_hat^2] at %d timesteps from %d examples x %d draws in %.1f s (mean %.4f)", len(need), len(x0),
+             FLAGS.analytic_draws, time.time() - t0, float(np.clip(g, 0, 1).mean()))
+    return g, need
+
+
 def check_copy_flags(FLAGS):
     """the refusals of --copy_metrics / --copy_k / --copy_train_examples, before the GPU is touched"""
     if not FLAGS.copy_metrics:
@@ -378,7 +443,7 @@ def copy_metrics_report(FLAGS, train, real, generated, dev):
              len(train), k, time.time() - t0)
 
 
-def compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world):
+def compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world, analytic_g=None):
     """The variational bound over this rank's rows [lo, hi) of the eval set; rank 0 gathers and writes
     {sampling_dir}/ncsn/bound.json (scalars, per-timestep means) and bound_terms.pkl (the per-example arrays)."""
     import json
@@ -388,7 +453,7 @@ def compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world):
     t0 = time.time()
     out = ncsn.variational_bound(rng, model, sigmas, np.ascontiguousarray(real[lo:hi], dtype=np.float32), FLAGS.bound_steps,
                                  sample_offset=lo, global_num_samples=len(real), use_graph=FLAGS.graph,
-                                 prediction=_prediction(FLAGS))
+                                 prediction=_prediction(FLAGS), analytic=analytic_g)
     model.drop_sampler_cache()
     parts = [out]
     if world > 1:
@@ -412,6 +477,10 @@ def compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world):
                    var_0=float(out["var_0"]), exact=bool(exact))
     if out.get("prediction", "eps") != "eps":               # an x0 / v model says so (and has eps_mse: null); eps files are as ever
         summary["prediction"] = out["prediction"]
+    if analytic_g is not None:                              # single process (check_analytic_flags): out is the whole eval set
+        summary.update(analytic_terms=[float(v) for v in out["analytic_terms"].mean(axis=1)],
+                       analytic_total=float(out["analytic_total"].mean()), analytic_bits_per_dim=float(out["analytic_bits_per_dim"]),
+                       sigma2_ratio=[float(v) for v in out["sigma2_ratio"]])
     log_dir = FLAGS.sampling_dir
     os.makedirs(os.path.join(log_dir, "ncsn"), exist_ok=True)
     with open(os.path.join(log_dir, "ncsn/bound.json"), "w") as f:
@@ -454,6 +523,7 @@ def main(argv):
     check_ddim_flags(FLAGS, walk)
     check_bound_flags(FLAGS)
     check_copy_flags(FLAGS)
+    check_analytic_flags(FLAGS, world)
     try:
         FLAGS.prediction = resolve_prediction_flag(FLAGS)
     except ValueError as e:
@@ -493,8 +563,27 @@ def main(argv):
     lo, hi = shard_bounds(num, world, rank)
     model, rng = load_model(FLAGS, shape, dev)
 
+    analytic = None
+    bound_g = None
+    if FLAGS.analytic_variance != "none":
+        def analytic_examples():                        # the training split as --copy_metrics reads it, else the eval examples
+            n = FLAGS.analytic_examples
+            if FLAGS.synthetic:
+                return data.SyntheticLatents(shape, n, n, COPY_SYNTHETIC_SEED).take_examples(n)
+            src = train_ds if len(getattr(train_ds, "array", ())) else eval_ds
+            return src.take_examples(min(n, len(src.array)))
+        bound_ts = None
+        if FLAGS.compute_bound:
+            bound_ts = np.arange(FLAGS.num_sigmas) if FLAGS.bound_steps == 0 else schedule.stride_timesteps(FLAGS.num_sigmas, FLAGS.bound_steps)
+        from smd_amd import analytic as A
+        g_all, g_ts = analytic_moments(FLAGS, model, sigmas, walk, analytic_examples, bound_ts)
+        taus = A.resolve_walk(FLAGS, sigmas, walk)
+        analytic = (FLAGS.analytic_variance, g_all[np.searchsorted(g_ts, taus)])
+        if bound_ts is not None:
+            bound_g = g_all[np.searchsorted(g_ts, np.unique(bound_ts))]
+
     if FLAGS.compute_bound:
-        compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world)
+        compute_bound(FLAGS, model, real, lo, hi, sigmas, rank, world, analytic_g=bound_g)
         if FLAGS.bound_only:
             if world > 1:
                 import torch.distributed as dist
@@ -513,16 +602,16 @@ def main(argv):
             samples[:, infilled_idx, :] = 0
             masks[:, fixed_idx, :] = 1
         generated, collection, ld_metrics = infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=lo,
-                                                           global_num_samples=num, walk=walk)
+                                                           global_num_samples=num, walk=walk, analytic=analytic)
     elif FLAGS.interpolate:                                                 # :425-435
         generated, collection, ld_metrics = interpolate_samples(model, sigmas, real, lo, hi, rng, FLAGS.sample_seed, FLAGS.rng_impl,
                                                                 dev, FLAGS.graph, ddim_steps=FLAGS.ddim_steps,
                                                                 ddim_eta=FLAGS.ddim_eta, ddim_encode=FLAGS.ddim_encode,
                                                                 ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing,
-                                                                prediction=FLAGS.prediction, walk=walk)
+                                                                prediction=FLAGS.prediction, walk=walk, analytic=analytic)
     else:                                                                   # :437-439
         generated, collection, ld_metrics = generate_samples(FLAGS, model, rng, shape, hi - lo, sigmas, sample_offset=lo,
-                                                             global_num_samples=num, walk=walk)
+                                                             global_num_samples=num, walk=walk, analytic=analytic)
 
     # evaluate() reads the device collection where there is one (a single rank); the shards of several ranks are gathered
     # on the host below

@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libsmd_hip.so")
-SOURCES = ["tuning.hip", "gemm_nt.hip", "gemm_nt256.hip", "gemm_tn.hip", "gemm_tn256.hip", "norm.hip", "ln128.hip", "attention.hip", "encoder_fused.hip", "diffusion.hip", "timestep.hip", "bound.hip", "distill.hip", "rng_jax.hip", "optim.hip",
+SOURCES = ["tuning.hip", "gemm_nt.hip", "gemm_nt256.hip", "gemm_tn.hip", "gemm_tn256.hip", "norm.hip", "ln128.hip", "attention.hip", "encoder_fused.hip", "diffusion.hip", "timestep.hip", "bound.hip", "analytic.hip", "distill.hip", "rng_jax.hip", "optim.hip",
            "metrics.hip", "nn_metrics.hip", "nn_search.hip", "kmeans.hip", "gemm_f32.hip", "net_f32.hip", "engine.hip", "capi.hip"]
 HEADERS = ["smd_common.h", "smd_kernels.h", "gemm_plan.h", "gemm_tile.h", "gram_tile.h", "gram_walk.h", "step_walk.h", "f32_kernels.h", "gemm_epilogue.h", "engine.h", "rng.h", "rng_threefry.h",
            os.path.join("..", "..", "include", "smd_hip.h"), os.path.join("..", "..", "include", "smd_hip_lab.h")]
@@ -45,7 +45,7 @@ EXTRA_FLAGS = {"encoder_fused.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
 # encoder_fused.hip keeps the default: its workgroups take 136-160 KiB of LDS, no GEMM workgroup can join them on a CU, and
 # its GELU phases are 3 % faster with the packed forms.
 if os.environ.get("SMD_SLP") != "1":
-    for _f in ("norm.hip", "ln128.hip", "diffusion.hip", "timestep.hip", "bound.hip", "distill.hip", "optim.hip", "attention.hip", "net_f32.hip"):
+    for _f in ("norm.hip", "ln128.hip", "diffusion.hip", "timestep.hip", "bound.hip", "analytic.hip", "distill.hip", "optim.hip", "attention.hip", "net_f32.hip"):
         EXTRA_FLAGS.setdefault(_f, []).append("-fno-slp-vectorize")
 
 

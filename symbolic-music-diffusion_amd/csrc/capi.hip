@@ -263,6 +263,31 @@ int smd_engine_bound_step(smd_engine* e, const smd_bound_io* io, void* stream) {
   b.partial = io->partial;
   return e->impl.bound_step(b, S(stream));
 }
+int smd_engine_moment_step(smd_engine* e, const smd_moment_io* io, void* stream) {
+  NEED(e);
+  SMD_ARG_CHECK(io, "moment_step: null io");
+  MomentStepIO m;
+  m.x0 = io->x0; m.x_t = io->x_t; m.eps = io->eps; m.t_ptr = io->t_ptr; m.noise_table = io->noise_table;
+  m.moment_table = io->moment_table; m.next_t = io->next_t; m.T = io->T; m.eps_source = io->eps_source; m.seed_lo = io->seed_lo;
+  m.seed_hi = io->seed_hi; m.sample_offset = io->sample_offset; m.key_ptr = io->key_ptr; m.tf_keys = io->tf_keys;
+  m.tf_n_total = io->tf_n_total; m.partial = io->partial; m.sums = io->sums;
+  return e->impl.moment_step(m, S(stream));
+}
+int smd_engine_analytic_step(smd_engine* e, const smd_sample_io* io, const smd_stride_plan* plan, const smd_sigma_table* sig, int part,
+                             void* stream) {
+  NEED(e);
+  SMD_ARG_CHECK(io && plan && sig, "analytic_step: null io / plan / sig");
+  StridePlan p;
+  p.coef = plan->coef; p.plan = plan->plan; p.T = plan->T;
+  return e->impl.analytic_step(sample_io(io), p, sig->sig, sig->K, S(stream), part);
+}
+int smd_score_moments(const float* x_t, const float* out, int B, int S_, int C, const float* table, int T, int32_t* t_ptr,
+                      const int32_t* next_t, uint32_t* arrive, float* partial, float* sums, void* stream) {
+  ScoreMomentsArgs a;
+  a.x_t = x_t; a.out = out; a.B = B; a.S = S_; a.C = C; a.T = T; a.table = table; a.t_ptr = t_ptr; a.next_t = next_t;
+  a.arrive = arrive; a.partial = partial; a.sums = sums;
+  return launch_score_moments(a, S(stream));
+}
 
 // ------------------------------------------------------------------ single kernels
 int smd_set_tuning(const char* key, int value) { return smd_tuning_set(key, value); }

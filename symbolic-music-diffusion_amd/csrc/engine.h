@@ -87,6 +87,24 @@ struct BoundStepIO {                   // include/smd_hip.h smd_bound_io
   float* partial = nullptr;           // [T][B][3]
 };
 
+struct MomentStepIO {                  // include/smd_hip.h smd_moment_io
+  const float* x0 = nullptr;
+  float* x_t = nullptr;
+  float* eps = nullptr;
+  int* t_ptr = nullptr;
+  const float* noise_table = nullptr; // [T][4], see BoundNoiseArgs
+  const float* moment_table = nullptr;// [T][4] (A, B, 0, 0), see ScoreMomentsArgs
+  const int32_t* next_t = nullptr;    // [T]
+  int T = 0;
+  int eps_source = 0;                 // 0 explicit, 1 jax.random (threefry), 2 Philox
+  uint32_t seed_lo = 0, seed_hi = 0, sample_offset = 0;
+  const uint32_t* key_ptr = nullptr;
+  const uint32_t* tf_keys = nullptr;  // [T][2]
+  int64_t tf_n_total = 0;
+  float* partial = nullptr;           // [ceil(B / SMD_MOMENT_CHUNK)][S][C]
+  float* sums = nullptr;              // [T][S][C]
+};
+
 struct MultistepPlan {
   const float* coef = nullptr;        // [T][12], see MultistepStepArgs
   const int32_t* plan = nullptr;      // [T][4]
@@ -161,6 +179,11 @@ class SmdEngine {
   int multistep_step(const SampleStepIO& io, const MultistepPlan& plan, float* x0_prev, hipStream_t st, int part = 0);
   // one iteration of the variational-bound walk: noise an example to level t, eps-net forward at table row t, the three sums
   int bound_step(const BoundStepIO& io, hipStream_t st);
+  // one iteration of the analytic-variance estimator walk: noise an example to level t, eps-net forward at table row t, the
+  // batch sums of eps_hat^2 per element
+  int moment_step(const MomentStepIO& io, hipStream_t st);
+  // eps-net forward + fused strided step with the per-element noise scale sig [n_iter][S][C]
+  int analytic_step(const SampleStepIO& io, const StridePlan& plan, const float* sig, int n_iter, hipStream_t st, int part = 0);
   int init_state(float* x, uint32_t seed_lo, uint32_t seed_hi, uint32_t sample_offset, hipStream_t st);
   int load_state(const float* x, hipStream_t st);            // explicit state -> bf16 network input
   // device pointers of a few internals (tests / metrics)

@@ -1446,6 +1446,57 @@ int SmdEngine::bound_step(const BoundStepIO& io, hipStream_t st) {
   return launch_bound_terms(a, st);
 }
 
+int SmdEngine::moment_step(const MomentStepIO& io, hipStream_t st) {
+  SMD_ARG_CHECK(io.x0 && io.x_t && io.eps && io.t_ptr && io.partial && io.sums, "moment_step: null example / scratch / t pointer / partial / sums");
+  SMD_ARG_CHECK(io.noise_table && io.moment_table && io.next_t, "moment_step: null table / next_t");
+  SMD_ARG_CHECK(io.T == d_.num_timesteps, "moment_step: the tables have T=%d rows, the engine %d timesteps", io.T, d_.num_timesteps);
+  SMD_ARG_CHECK(!training_ && batch_ > 0 && film_tables_, "moment_step: bind an inference workspace and the schedule tables first");
+  SMD_ARG_CHECK(io.eps_source >= 0 && io.eps_source <= 2, "moment_step: eps_source=%d (0 explicit, 1 threefry, 2 Philox)", io.eps_source);
+  const int S = d_.seq_len, C = d_.data_channels;
+  if (io.eps_source == 1) {
+    const int64_t per = (int64_t)S * C;
+    SMD_ARG_CHECK(io.tf_keys, "moment_step: eps_source 1 needs the key table");
+    SMD_ARG_CHECK(io.tf_n_total >= ((int64_t)io.sample_offset + batch_) * per && io.tf_n_total <= (1ll << 32),
+                  "moment_step: tf_n_total=%lld must cover this rank's window and be <= 2^32", (long long)io.tf_n_total);
+    RC(launch_threefry_normal(io.eps, io.tf_n_total, (int64_t)io.sample_offset * per, (int64_t)batch_ * per, 0u, 0u, io.tf_keys,
+                              io.t_ptr, 1, 0, st));
+  }
+  BoundNoiseArgs n;
+  n.x0 = io.x0; n.eps = io.eps; n.draw = io.eps_source == 2; n.B = batch_; n.S = S; n.C = C; n.Cp = Cp_; n.T = io.T;
+  n.table = io.noise_table; n.t_ptr = io.t_ptr; n.key = RngKey{io.seed_lo, io.seed_hi}; n.key_ptr = io.key_ptr;
+  n.sample_offset = io.sample_offset; n.x_t = io.x_t;
+  n.xt_bf16 = fp32 ? nullptr : W.x_bf16;      // reference precision reads the fp32 x_t itself
+  RC(launch_bound_noise(n, st));
+  RC(run_network(io.t_ptr, st, 0, io.x_t));
+  ScoreMomentsArgs a;
+  a.x_t = io.x_t; a.out = W.pred; a.B = batch_; a.S = S; a.C = C; a.T = io.T; a.table = io.moment_table;
+  a.t_ptr = io.t_ptr; a.next_t = io.next_t; a.arrive = W.step_arrive; a.partial = io.partial; a.sums = io.sums;
+  return launch_score_moments(a, st);
+}
+
+int SmdEngine::analytic_step(const SampleStepIO& io, const StridePlan& plan, const float* sig, int n_iter, hipStream_t st, int part) {
+  SMD_ARG_CHECK(io.x && io.t_ptr, "analytic_step: null state / t pointer");
+  SMD_ARG_CHECK(plan.coef && plan.plan && sig, "analytic_step: null coefficient table / plan / sig table");
+  SMD_ARG_CHECK(plan.T == d_.num_timesteps, "analytic_step: the plan has T=%d rows, the engine %d timesteps", plan.T, d_.num_timesteps);
+  SMD_ARG_CHECK(!training_ && coef_ && film_tables_, "analytic_step: bind an inference workspace and the schedule tables first");
+  SMD_ARG_CHECK(part >= 0 && part <= 2, "analytic_step: part=%d (0 whole step, 1 stem, 2 output stage + analytic update)", part);
+  SMD_ARG_CHECK(!(fp32 && part != 0), "analytic_step: part=%d is not available under fp32 (no two-chain pipeline): walk one chain with part 0", part);
+  RC(run_network(io.t_ptr, st, part, io.x));
+  if (part == 1) return 0;
+  AnalyticStepArgs a;
+  a.x = io.x; a.eps_hat = W.pred;
+  a.B = batch_; a.S = d_.seq_len; a.C = d_.data_channels; a.Cp = Cp_; a.T = plan.T;
+  a.coef = plan.coef; a.plan = plan.plan; a.t_ptr = io.t_ptr; a.z_in = io.z_in; a.key = RngKey{io.seed_lo, io.seed_hi};
+  a.sample_offset = io.sample_offset;
+  a.infill_samples = io.infill_samples; a.infill_masks = io.infill_masks; a.infill_z_in = io.infill_z_in;
+  a.tf_noise_keys = io.tf_noise_keys; a.tf_infill_keys = io.tf_infill_keys; a.tf_n_total = io.tf_n_total;
+  a.key_ptr = io.key_ptr;
+  a.x_bf16 = W.x_bf16; a.metrics_partial = io.metrics_partial; a.collection = io.collection;
+  a.t_advance = io.t_ptr; a.arrive = W.step_arrive;      // *t_ptr = plan[t].next_t by the step's last workgroup
+  a.sig = sig; a.n_iter = n_iter;
+  return launch_analytic_step(a, st);
+}
+
 int SmdEngine::multistep_step(const SampleStepIO& io, const MultistepPlan& plan, float* x0_prev, hipStream_t st, int part) {
   SMD_ARG_CHECK(io.x && io.t_ptr, "multistep_step: null state / t pointer");
   SMD_ARG_CHECK(plan.coef && plan.plan, "multistep_step: null coefficient table / plan");

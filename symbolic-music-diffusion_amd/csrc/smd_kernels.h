@@ -412,6 +412,31 @@ struct BoundTermsArgs {
 };
 int launch_bound_terms(const BoundTermsArgs& a, hipStream_t st);
 
+// ------------------------------------------------------------------ analytic reverse variance (analytic.hip)
+// sums[t][s][c] = sum over b of (A_t x_t + B_t out)^2: table [T][4] float32 rows (A, B, 0, 0), 16-byte aligned.  The batch is
+// reduced in chunks of SMD_MOMENT_CHUNK rows (partial) that a second launch adds in chunk order.  The chunk size is part of
+// the public contract (the caller sizes `partial` by it): its one definition is the public header's.
+#include "../../include/smd_hip.h"
+struct ScoreMomentsArgs {
+  const float* x_t = nullptr;         // [B][S][C] the network's input
+  const float* out = nullptr;         // [B][S][C] the network's output (eps, x0 or v: the table row says which)
+  int B = 0, S = 0, C = 0, T = 0;
+  const float* table = nullptr;
+  int* t_ptr = nullptr;               // device timestep; t outside [0, T) makes both launches no-ops
+  const int32_t* next_t = nullptr;    // [T] or null: the last workgroup stores next_t[t] to *t_ptr (-1 ends a walk)
+  unsigned* arrive = nullptr;         // arrival counter for that store: zero before the first launch, reset by the kernel
+  float* partial = nullptr;           // [ceil(B / SMD_MOMENT_CHUNK)][S][C] workspace, every element of the used rows written
+  float* sums = nullptr;              // [T][S][C]: row t is written (never accumulated)
+};
+int launch_score_moments(const ScoreMomentsArgs& a, hipStream_t st);
+
+// the strided step with a per-element noise scale: coef column 4 is a 0/1 switch, sigma comes from sig[plan[t].iteration][s][c]
+struct AnalyticStepArgs : StridedStepArgs {
+  const float* sig = nullptr;         // [n_iter][S][C] float32, the same rows for every sample
+  int n_iter = 0;                     // rows of sig; an iteration outside [0, n_iter) is a no-op
+};
+int launch_analytic_step(const AnalyticStepArgs& a, hipStream_t st);
+
 // ------------------------------------------------------------------ progressive distillation (distill.hip)
 // Three element-wise kernels with a walk step PER SAMPLE: steps [B] int32 in [0, N) picks the sample's row of table [N][16]
 // float32 (64-byte rows, 16-byte aligned): c0_t, c1_t, a, b, clip, alpha_t, sigma_t, alpha_m, c0_m, c1_m, w1, w2, weight,

@@ -543,6 +543,23 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.L.smd_engine_bound_step(self.h, C.byref(io), _stream()), "bound_step")
 
+    def moment_step(self, io: "_lib.MomentIO") -> None:
+        """One iteration of the analytic-variance estimator walk: noise the examples to the level of the device timestep,
+        eps-net forward at that table row, the batch sums of eps_hat^2 (include/smd_hip.h smd_engine_moment_step)."""
+        self._sync_fp8_weights()
+        self._join_pending()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.smd_engine_moment_step(self.h, C.byref(io), _stream()), "moment_step")
+
+    def analytic_step(self, io: "_lib.SampleIO", plan: "_lib.StridePlan", sig: "_lib.SigmaTable", part: int = 0) -> None:
+        """One iteration of a strided walk with the per-element noise scale ``sig`` ([K][S][C] float32 on the device;
+        include/smd_hip.h smd_engine_analytic_step); ``part`` as in sample_step."""
+        self._sync_fp8_weights()
+        self._join_pending()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.smd_engine_analytic_step(self.h, C.byref(io), C.byref(plan), C.byref(sig), int(part), _stream()),
+                       "analytic_step")
+
     @property
     def slot_table(self) -> torch.Tensor:
         return self._sched_tensors["slot"]

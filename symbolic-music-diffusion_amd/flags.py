@@ -278,6 +278,16 @@ ENGINE_FLAGS: List[FlagDef] = [
        "update DPM-Solver++(2M) of Lu et al. 2022 (deterministic: --ddim_eta=0; DESIGN.md section 18)."),
     _D("ddim_spacing", "enum", "uniform", "--ddim_steps: the timesteps are evenly spaced in t (uniform) or in "
        "lambda = log(sqrt(ap) / sqrt(1 - ap)) snapped to timesteps (logsnr: at most --ddim_steps of them).", ("uniform", "logsnr")),
+    _D("analytic_variance", "enum", "none", "sample_ncsn --ddim_steps: give the noise of every iteration the optimal reverse variance of "
+       "Bao et al. 2022 (Analytic-DPM) instead of sigma_eta^2, from an estimate of E[eps_hat^2] per timestep: none, scalar (one "
+       "variance per iteration) or element (one per latent element; DESIGN.md section 28).  With --compute_bound (scalar only) "
+       "bound.json gains the bound of the K-step chain.  Single process, --sampling=ddpm, --ddim_order=1.", ("none", "scalar", "element")),
+    _D("analytic_examples", "int", 256, "--analytic_variance: examples the statistic is estimated on (the training split, else the eval "
+       "examples; --synthetic: synthetic ones)."),
+    _D("analytic_draws", "int", 1, "--analytic_variance: noise draws per example and timestep."),
+    _D("analytic_moments", "string", "", "--analytic_variance: load the estimate from this file (a "
+       "{sampling_dir}/ncsn/analytic_moments.safetensors of an earlier run) instead of estimating; a file whose metadata "
+       "contradicts the run or whose timesteps do not cover the walk is refused."),
     _D("loss_weighting", "enum", "none", "train_ncsn --loss=ddpm: weight of every timestep in the loss, none (the reference) or "
        "min_snr = min(SNR, --min_snr_gamma) / SNR (Hang et al. 2023; DESIGN.md section 25).  Works on any number of ranks.",
        ("none", "min_snr")),

@@ -88,6 +88,20 @@ class BoundIO(C.Structure):
                 ("sample_offset", c_u32), ("key_ptr", c_void), ("tf_keys", c_void), ("tf_n_total", c_i64), ("partial", c_void)]
 
 
+class MomentIO(C.Structure):
+    _fields_ = [("x0", c_void), ("x_t", c_void), ("eps", c_void), ("t_ptr", c_void), ("noise_table", c_void),
+                ("moment_table", c_void), ("next_t", c_void), ("T", c_i32), ("eps_source", c_i32), ("seed_lo", c_u32),
+                ("seed_hi", c_u32), ("sample_offset", c_u32), ("key_ptr", c_void), ("tf_keys", c_void), ("tf_n_total", c_i64),
+                ("partial", c_void), ("sums", c_void)]
+
+
+class SigmaTable(C.Structure):
+    _fields_ = [("sig", c_void), ("K", c_i32)]
+
+
+MOMENT_CHUNK = 8         # SMD_MOMENT_CHUNK of include/smd_hip.h: batch rows per partial of smd_score_moments
+
+
 class MultistepPlan(C.Structure):
     _fields_ = [("coef", c_void), ("plan", c_void), ("T", c_i32)]
 
@@ -156,6 +170,10 @@ _SIGS = {
     "smd_engine_strided_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(StridePlan), C.c_int, c_void]),
     "smd_engine_multistep_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(MultistepPlan), c_void, C.c_int, c_void]),
     "smd_engine_bound_step": (C.c_int, [c_void, C.POINTER(BoundIO), c_void]),
+    "smd_engine_moment_step": (C.c_int, [c_void, C.POINTER(MomentIO), c_void]),
+    "smd_engine_analytic_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(StridePlan), C.POINTER(SigmaTable), C.c_int, c_void]),
+    "smd_score_moments": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, c_void, c_void,
+                                    c_void, c_void]),
     "smd_bound_noise": (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_int, c_void, C.c_int, c_void, c_void, C.c_int, c_u32, c_u32,
                                   c_void, c_u32, c_void, c_void, c_void]),
     "smd_bound_terms": (C.c_int, [c_void, c_void, c_void, C.c_int, C.c_int, C.c_int, c_void, C.c_int, C.c_float, c_void, c_void,

@@ -16,6 +16,7 @@ sequences calls and reproduces the reference's output layouts and quirks.
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import logging
 import math
 import os
@@ -892,13 +893,16 @@ def diffusion_dynamics(rng: PRNGKey, model: Model, betas, init, epsilon=None, T=
 def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], coef: np.ndarray, plan: np.ndarray, walk_key: tuple, *,
                   collect: bool, infill: bool = False, infill_samples=None, infill_masks=None, noises: Optional[Callable] = None,
                   infill_noises: Optional[Callable] = None, use_graph: bool = True, one_chain: bool = False, sample_offset: int = 0,
-                  global_num_samples: Optional[int] = None, multistep: bool = False, prediction="eps"):
+                  global_num_samples: Optional[int] = None, multistep: bool = False, prediction="eps",
+                  sig_table: Optional[np.ndarray] = None):
     """A table-driven walk over the timesteps ``order`` (smd_engine_strided_step) in the arrangement of diffusion_dynamics:
     eager launches with explicit draws, else one graph-replayed chain, else (B >= 128, bf16 / fp8) the pipelined pair.  Its
     cached graphs and persistent buffers live in their own ``slot`` of the model's sampler cache, beside diffusion_dynamics'
     entry, keyed additionally by ``walk_key``.  ``multistep``: ``coef`` is a multistep table ([T][12]), every chain carries one
     history tensor of its state's shape and steps with smd_engine_multistep_step; the first iteration does not read the
-    history, so a reused buffer needs no reset.  Returns (state, collection or None, metrics_partial (T, B, 3) indexed by t)."""
+    history, so a reused buffer needs no reset.  ``sig_table``: float32 [iterations][...sample shape], the per-element noise scale
+    of smd_engine_analytic_step, which then takes the step (column 4 of ``coef`` is its 0/1 switch); the table lives with the
+    entry's device tables, so ``walk_key`` must name its contents.  Returns (state, collection or None, metrics_partial (T, B, 3) indexed by t)."""
     eng = model.engine
     dev = eng.device
     init = torch.as_tensor(init).to(dev, torch.float32).contiguous()
@@ -966,6 +970,13 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
         if graphed:
             cache.pop(slot, None)
         entry = dict(key=ckey, sig=sig, x=x, nk_d=nk_d, ik_d=ik_d, inf_s=inf_s, inf_m=inf_m, coef_d=coef_d, plan_d=plan_d, plan=sp)
+        if sig_table is not None:
+            if multistep or tuple(sig_table.shape) != (len(order), *init.shape[1:]) or sig_table.dtype != np.float32:
+                raise ValueError(f"sig_table: float32 {(len(order), *init.shape[1:])} for the strided step, got {sig_table.dtype} {sig_table.shape}")
+            entry["sig_d"] = torch.from_numpy(np.ascontiguousarray(sig_table)).to(dev)
+            st_ = _lib.SigmaTable()
+            st_.sig, st_.K = entry["sig_d"].data_ptr(), len(order)
+            entry["sig_table"] = st_
         chains = []
     sp = entry["plan"]
     key_words = torch.tensor([rng.seed & 0xFFFFFFFF, (rng.seed >> 32) & 0xFFFFFFFF], dtype=torch.int64).to(torch.int32)
@@ -1009,6 +1020,9 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
 
     if multistep:
         step = lambda ch, part=0: ch["eng"].multistep_step(ch["io"], sp, ch["hist"], part)
+    elif sig_table is not None:
+        sgt = entry["sig_table"]
+        step = lambda ch, part=0: ch["eng"].analytic_step(ch["io"], sp, sgt, part)
     else:
         step = lambda ch, part=0: ch["eng"].strided_step(ch["io"], sp, part)
     if explicit:
@@ -1058,7 +1072,7 @@ def _walk_ld_metrics(model: Model, betas, taus, mp):
 def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, infill=False, infill_samples=None,
                      infill_masks=None, *, noises: Optional[Callable] = None, infill_noises: Optional[Callable] = None,
                      use_graph: bool = True, sample_offset: int = 0, global_num_samples: Optional[int] = None, order: int = 1,
-                     spacing: str = "uniform", prediction="eps", timesteps=None):
+                     spacing: str = "uniform", prediction="eps", timesteps=None, analytic=None):
     """The generalised non-Markovian sampler of Song et al. 2021 (DDIM) on ``steps`` evenly spaced timesteps of the schedule
     (schedule.stride_timesteps) instead of all of them: ``steps`` network evaluations from the same checkpoint.  ``eta`` scales
     the noise of every iteration (0: deterministic, 1: the DDPM posterior's variance).  Returns (state, collection (41, ...),
@@ -1076,7 +1090,13 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
     ``prediction`` "x0" / "v": the tables' first two columns are that kind's (section 26); a non-eps kind is part of the cache key.
     ``timesteps``: an explicit strictly descending walk within [0, T), e.g. the walk a distilled student was trained on
     (``schedule.distill_walk``; section 27), instead of the ``steps`` evenly spaced ones; ``steps`` must then be None, 0 or
-    the walk's length.  The walk is part of the cache key, as the lambda grid's is; without it every key is as it was."""
+    the walk's length.  The walk is part of the cache key, as the lambda grid's is; without it every key is as it was.
+    ``analytic`` = ("scalar" | "element", g): the noise of every iteration takes the optimal variance of Bao et al. 2022
+    (``schedule.analytic_variance``) instead of sigma_eta^2; the mean is untouched.  g is the statistic
+    E[eps_hat^2] per ITERATION, [K] or [K][...sample shape] (``estimate_score_moments``).  "scalar" uses its mean per iteration:
+    sqrt(sig2) goes into the strided table's sigma column and smd_engine_strided_step walks as ever.  "element" walks with
+    smd_engine_analytic_step on a [K][...] table, in the cache slot "analytic".  Order 1 only.  A digest of the variances is
+    part of the cache key: a reused entry keeps its device tables."""
     nT = len(betas)
     pk = () if _sched.prediction_kind(prediction) == 0 else (("prediction", _sched.prediction_kind(prediction)),)
     if order not in (1, 2):
@@ -1101,7 +1121,31 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
     kw = dict(collect=True, infill=infill, infill_samples=infill_samples, infill_masks=infill_masks, noises=noises,
               infill_noises=infill_noises, use_graph=use_graph, sample_offset=sample_offset, global_num_samples=global_num_samples,
               prediction=prediction)
-    if order == 1:                                       # the strided update on either grid; the default key is the one it had
+    if analytic is not None and analytic[0] != "none":
+        mode, g = analytic
+        if mode not in ("scalar", "element"):
+            raise ValueError(f"analytic: mode {mode!r} is not 'scalar' or 'element'")
+        if order != 1:
+            raise ValueError("analytic: order=2 is a deterministic solver with no noise term to give a variance to")
+        g = np.asarray(g, dtype=np.float64)
+        if g.shape[0] != len(walk):
+            raise ValueError(f"analytic: g has {g.shape[0]} rows for a walk of {len(walk)} iterations")
+        coef, plan = _sched.strided_coefficient_table(betas, taus, eta, prediction=prediction)
+        if mode == "scalar":
+            sg = _sched.analytic_sigma_table(betas, taus, eta, _sched.analytic_scalar_g(g))
+            coef[walk, 4] = sg
+            slot_name, sig_table = "strided", None
+        else:
+            shape = tuple(model.engine.cfg.sample_shape)
+            if tuple(g.shape[1:]) != shape:
+                raise ValueError(f"analytic: element mode takes g of shape (K, {shape}), got {g.shape}")
+            sg = _sched.analytic_sigma_table(betas, taus, eta, g)
+            coef[walk, 4] = (sg.reshape(len(walk), -1) != 0).any(axis=1).astype(np.float32)      # the switch
+            slot_name, sig_table = "analytic", sg
+        key = (("strided", len(walk), float(eta)) + ((spacing, tuple(walk)) if spacing != "uniform" else ())
+               + (("walk", tuple(walk)) if explicit else ()) + pk + (("analytic", mode, hashlib.sha1(sg.tobytes()).hexdigest()),))
+        x, collection, mp = _strided_walk(slot_name, rng, model, betas, init, walk, coef, plan, key, sig_table=sig_table, **kw)
+    elif order == 1:                                     # the strided update on either grid; the default key is the one it had
         coef, plan = _sched.strided_coefficient_table(betas, taus, eta, prediction=prediction)
         # on the lambda grid the number of iterations does not name the timesteps (K = 19 and K = 20 both snap to 18): the key
         # carries the walk itself, because a reused entry keeps its device tables
@@ -1131,7 +1175,7 @@ def ddim_encode(model: Model, betas, x0, steps, *, use_graph: bool = True, predi
 
 
 def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip: float = 1.0, eps_in=None, sample_offset: int = 0,
-                      global_num_samples: Optional[int] = None, use_graph: bool = True, prediction="eps") -> dict:
+                      global_num_samples: Optional[int] = None, use_graph: bool = True, prediction="eps", analytic=None) -> dict:
     """The variational bound of Ho et al. 2020 (eq. 5) on the examples ``batch`` (model space), term by term: no reference
     counterpart.  ``steps`` = 0: every timestep, the bound itself; else the terms at
     ``schedule.stride_timesteps(T, steps)`` only -- the curve, no total (no stride estimates the sum honestly).  One eps-net
@@ -1143,7 +1187,10 @@ def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip
     mean squared error of eps_hat), ``prior`` [N], ``total`` [N] or None, ``nats_per_dim`` / ``bits_per_dim`` (means over the
     examples, or None) and ``var_0``.  ``prediction`` "x0" / "v": columns 2 / 3 of the table turn the network's output into x0, so
     every term is right; the second sum is sum (eps - out)^2, which means nothing for those kinds: ``eps_mse`` is then None and the
-    result carries ``prediction``.  The t = 0 term is a DENSITY of continuous latents, so it -- and the total -- is negative."""
+    result carries ``prediction``.  The t = 0 term is a DENSITY of continuous latents, so it -- and the total -- is negative.
+    ``analytic`` = g [K] (scalar mode, rows ASCENDING in t like ``timesteps``): the result also carries ``analytic_terms`` /
+    ``analytic_total`` / ``analytic_bits_per_dim`` / ``sigma2_ratio`` of ``schedule.analytic_bound_from_sums``, the bound of the K-step
+    chain with the optimal variances -- a number for every ``steps`` (section 28)."""
     eng = model.engine
     dev = eng.device
     x0 = torch.as_tensor(batch).to(dev, torch.float32).contiguous()
@@ -1222,13 +1269,116 @@ def variational_bound(rng: PRNGKey, model: Model, betas, batch, steps=0, *, clip
     out["prediction"] = _sched.PREDICTIONS[kind]
     if kind != 0:
         out["eps_mse"] = None
+    if analytic is not None:
+        g = _sched.analytic_scalar_g(analytic)
+        ab = _sched.analytic_bound_from_sums(tab, sums, per, g[::-1], np.asarray(order[::-1]), betas)
+        out.update(analytic_terms=ab["terms"], analytic_total=ab["total"], analytic_bits_per_dim=ab["bits_per_dim"],
+                   analytic_nats_per_dim=ab["nats_per_dim"], sigma2_ratio=ab["sigma2_ratio"])
     return out
+
+
+def estimate_score_moments(model: Model, betas, x0, timesteps, draws: int = 1, rng: Optional[PRNGKey] = None, batch: int = 256, *,
+                           eps_in: Optional[Callable] = None, prediction="eps", use_graph: bool = True):
+    """The statistic of the analytic reverse variance (Bao et al. 2022): g_t[s,c] = the mean over the
+    examples ``x0`` (model space) and ``draws`` noise draws of eps_hat[s,c]^2 at every timestep of ``timesteps``, eps_hat the
+    network's output in eps units whatever its ``prediction`` kind.  Forward passes only: one graph-replayed walk
+    (smd_engine_moment_step) up the timesteps per batch of ``batch`` examples and per draw; each walk's fp32 sums [K][...] are
+    added here in float64.  Draws: Philox keyed by (the draw's key, example index, t) -- ``rng`` itself for one draw,
+    ``split(rng, draws)`` for more -- or, explicitly, ``eps_in(r, t)`` -> [N][...] (eager launches).  Returns (g [K][...sample
+    shape] float64, rows ASCENDING in t like ``numpy.unique(timesteps)``, not clipped; count = N * draws)."""
+    eng = model.engine
+    dev = eng.device
+    x0 = torch.as_tensor(x0).to(dev, torch.float32).contiguous()
+    N = x0.shape[0]
+    shape = tuple(x0.shape[1:])
+    if shape != tuple(eng.cfg.sample_shape) or N < 1:
+        raise ValueError(f"x0 shape {tuple(x0.shape)} != (N >= 1, {eng.cfg.sample_shape})")
+    draws, batch = int(draws), int(batch)
+    if draws < 1 or batch < 1:
+        raise ValueError(f"estimate_score_moments: draws={draws}, batch={batch} must be positive")
+    nT = len(betas)
+    kind = _sched.prediction_kind(prediction)
+    mtab, next_t = _sched.analytic_moment_tables(betas, timesteps, prediction)
+    ntab = _sched.bound_tables(betas, timesteps, prediction=prediction)
+    order = [int(t) for t in ntab["timesteps"]]
+    K = len(order)
+    explicit = eps_in is not None
+    if rng is None:
+        rng = PRNGKey(0)
+    if isinstance(rng, ThreefryKey) and not explicit:
+        raise ValueError("estimate_score_moments: the estimate draws with Philox; pass a Philox key (make_key(seed)) or eps_in")
+    keys = [rng] if draws == 1 else list(split(rng, draws))
+    graphed = use_graph and not explicit and K > 1
+    per = int(np.prod(shape))
+    _ensure_schedule(eng, betas, with_sampler=True, prediction=prediction)
+    cache = model.__dict__.setdefault("_sampler_graphs", {})
+    total = np.zeros((K, *shape), dtype=np.float64)
+    idx = torch.tensor(order, device=dev)
+    for lo in range(0, N, batch):
+        hi = min(N, lo + batch)
+        B = hi - lo
+        eng.bind(B, training=False)
+        sig = ((id(eng), eng.generation), _lib.tuning_epoch())
+        ckey = (tuple(order), B, nT, shape) + ((kind,) if kind else ())
+        entry = cache.get("moments") if graphed else None
+        reuse = entry is not None and entry["key"] == ckey and entry["sig"] == sig
+        if not reuse:
+            if graphed:
+                cache.pop("moments", None)
+            chunks = (B + _lib.MOMENT_CHUNK - 1) // _lib.MOMENT_CHUNK
+            entry = dict(key=ckey, sig=sig, x0=torch.zeros((B, *shape), dtype=torch.float32, device=dev),
+                         x_t=torch.zeros((B, *shape), dtype=torch.float32, device=dev),
+                         eps=torch.zeros((B, *shape), dtype=torch.float32, device=dev),
+                         partial=torch.zeros((chunks, *shape), dtype=torch.float32, device=dev),
+                         sums=torch.zeros((nT, *shape), dtype=torch.float32, device=dev),
+                         t_ptr=torch.tensor([order[0]], dtype=torch.int32, device=dev), pkey=torch.zeros(2, dtype=torch.int32, device=dev),
+                         ntab=torch.from_numpy(ntab["table"]).to(dev), mtab=torch.from_numpy(mtab).to(dev),
+                         next_t=torch.from_numpy(next_t).to(dev))
+            io = _lib.MomentIO()
+            io.x0, io.x_t, io.eps = entry["x0"].data_ptr(), entry["x_t"].data_ptr(), entry["eps"].data_ptr()
+            io.t_ptr, io.next_t = entry["t_ptr"].data_ptr(), entry["next_t"].data_ptr()
+            io.noise_table, io.moment_table = entry["ntab"].data_ptr(), entry["mtab"].data_ptr()
+            io.T = nT
+            io.eps_source = 0 if explicit else 2
+            io.key_ptr = entry["pkey"].data_ptr()
+            io.partial, io.sums = entry["partial"].data_ptr(), entry["sums"].data_ptr()
+            entry["io"] = io
+            entry["chains"] = [dict(eng=eng)]
+        io = entry["io"]
+        entry["x0"].copy_(x0[lo:hi])
+        eng.refresh_weights()
+        eng.prepare_sampler()
+        eng.load_state(entry["x0"])            # zeroes the padding columns of the bf16 network input; the walk writes the rest
+        step = lambda ch, part=0: ch["eng"].moment_step(io)
+        for r in range(draws):
+            # the example index is folded into the KEY (the captured sample_offset is the batch-local one): the draw's key
+            # mixed with the batch's first example, so no two batches share a stream
+            kr = keys[r]
+            seed = _splitmix64((kr.seed ^ _splitmix64(lo + 1)) & 0xFFFFFFFFFFFFFFFF) if lo else kr.seed
+            entry["pkey"].copy_(torch.tensor([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=torch.int64).to(torch.int32))
+            entry["t_ptr"].fill_(order[0])
+            if explicit:
+                for t in order:
+                    e = torch.as_tensor(eps_in(r, t)).to(dev, torch.float32).reshape(N, *shape)
+                    entry["eps"].copy_(e[lo:hi])
+                    step(entry["chains"][0])
+            elif graphed:
+                _graph_walk(model, dev, entry["chains"], K - 1, 0, reuse, step)
+                if not reuse:
+                    cache["moments"] = entry
+                    reuse = True
+            else:
+                for _ in order:
+                    step(entry["chains"][0])
+            total += entry["sums"][idx].double().cpu().numpy()
+    count = N * draws
+    return total / count, count
 
 
 def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400, sampling="ald", epsilon=1e-3,
            steps=100, denoise=True, *, sample_offset: int = 0, use_graph: bool = True,
            global_num_samples: Optional[int] = None, ddim_steps: int = 0, ddim_eta: float = 0.0, ddim_order: int = 1,
-           ddim_spacing: str = "uniform", prediction="eps", ddim_timesteps=None):
+           ddim_spacing: str = "uniform", prediction="eps", ddim_timesteps=None, analytic=None):
     """train_ncsn.py:499-551.  'ddpm': N(0,1) init + diffusion_dynamics.  'ald' / 'cas': uniform(-sqrt(12)/2, sqrt(12)/2)
     init (:542-547) + annealed / consistent Langevin dynamics with the score network ``scorenet``.  The reference unpacks
     three values from every sampler although consistent_langevin_dynamics returns two (a ValueError upstream); here 'cas'
@@ -1281,7 +1431,8 @@ def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400
         generated, collection, ld_metrics = strided_dynamics(ld_rng, scorenet, sigmas, init, ddim_steps, ddim_eta,
                                                              sample_offset=sample_offset, use_graph=use_graph,
                                                              global_num_samples=global_num_samples, order=ddim_order,
-                                                             spacing=ddim_spacing, prediction=prediction, timesteps=ddim_timesteps)
+                                                             spacing=ddim_spacing, prediction=prediction, timesteps=ddim_timesteps,
+                                                             analytic=analytic)
         return generated, collection, collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = diffusion_dynamics(ld_rng, scorenet, sigmas, init, epsilon, steps, denoise,
                                                            False, sample_offset=sample_offset, use_graph=use_graph,

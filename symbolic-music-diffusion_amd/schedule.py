@@ -408,3 +408,137 @@ def bound_from_sums(tab: dict, sums: np.ndarray, D: int) -> dict:
     return dict(timesteps=ts, terms=terms, eps_mse=sums[:, :, 1] / D, prior=prior, total=total,
                 nats_per_dim=None if total is None else float(total.mean() / D),
                 bits_per_dim=None if total is None else float(total.mean() / (D * np.log(2.0))), var_0=tab["var_0"])
+
+
+# ------------------------------------------------------------------ analytic (optimal) reverse variance
+ANALYTIC_MODES = ("none", "scalar", "element")
+
+
+def analytic_moment_tables(betas: np.ndarray, timesteps, prediction="eps"):
+    """Tables of the walk that estimates g_t = E[eps_hat^2] (Bao et al. 2022) at ``timesteps`` (any order; walked ascending):
+    float32 [T][4] rows (A, B, 0, 0) with eps_hat = A x_t + B out, the network's output ``out`` in eps units, and int32
+    ``next_t`` [T] (-1 after the last timestep and off the walk).  With x0 = c0 x_t - c1 out (``x0_coefficients``),
+    A = (1 - sqrt(ap) c0) / sqrt(1 - ap) and B = sqrt(ap) c1 / sqrt(1 - ap), taken from their closed forms per kind -- eps
+    (0, 1) exactly, x0 (1 / sqrt(1 - ap), -sqrt(ap) / sqrt(1 - ap)), v (sqrt(1 - ap), sqrt(ap)) -- in float64 from the float32
+    ``alphas_cumprod``, rounded once: 1 - sqrt(ap) c0 is a cancellation that the rounded table columns would not survive."""
+    T = len(betas)
+    ts = np.unique(np.asarray(timesteps, dtype=np.int64))
+    if len(ts) == 0 or ts[0] < 0 or ts[-1] >= T:
+        raise ValueError(f"analytic_moment_tables: timesteps must lie in [0, {T})")
+    ap = alphas_cumprod(betas).astype(np.float64)
+    bb = 1.0 - ap
+    kind = prediction_kind(prediction)
+    if kind == 0:
+        A, B = np.zeros(T), np.ones(T)
+    elif kind == 1:
+        A, B = 1.0 / np.sqrt(bb), -np.sqrt(ap) / np.sqrt(bb)
+    else:
+        A, B = np.sqrt(bb), np.sqrt(ap)
+    table = np.zeros((T, 4), dtype=np.float32)
+    table[:, 0], table[:, 1] = A, B
+    next_t = np.full((T,), -1, dtype=np.int32)
+    next_t[ts[:-1]] = ts[1:]
+    return np.ascontiguousarray(table), next_t
+
+
+def _analytic_parts(betas, taus, eta):
+    """float64 per iteration of the descending walk ``taus``: lam2 = sigma_eta^2, h (the coefficient of -eps_hat in the step's
+    mean), a (the coefficient of x0_hat), and the levels; ap_s := 1 on the last iteration."""
+    taus = np.asarray(taus, dtype=np.int64)
+    ap = alphas_cumprod(betas).astype(np.float64)
+    co = strided_coefficients(betas, taus, eta)
+    ap_t = ap[taus]
+    ap_s = np.concatenate([ap[taus[1:]], np.ones(1)])
+    bb_t, bb_s = 1.0 - ap_t, 1.0 - ap_s
+    lam2 = co["sigma"] ** 2
+    h = np.sqrt(bb_t * ap_s / ap_t) - np.sqrt(np.maximum(bb_s - lam2, 0.0))
+    return dict(lam2=lam2, h=h, a=co["a"], ap_t=ap_t, ap_s=ap_s, bb_t=bb_t, bb_s=bb_s)
+
+
+def analytic_variance(betas: np.ndarray, taus, eta: float, g, clip: float = 1.0) -> np.ndarray:
+    """The optimal state-independent reverse variance of Bao et al. 2022 (Analytic-DPM, Theorem 1 in the notation of
+    ``strided_coefficients``), float64, one entry per iteration of the descending walk ``taus``:
+
+      sig2 = lam^2 + h^2 (1 - g),  lam = sigma_eta,  h = sqrt(bb_t ap_s / ap_t) - sqrt(max(bb_s - lam^2, 0))
+
+    ``g`` [K] (scalar mode: one variance per iteration) or [K][...] (element mode: one per element), row j the statistic
+    E[eps_hat^2] at taus[j], clipped here to [0, 1] (Theorem 2).  A finite ``clip`` (data in [-clip, clip]) also caps the result
+    at lam^2 + a^2 clip^2, a = sqrt(ap_s) - sqrt(max(bb_s - lam^2, 0)) sqrt(ap_t / bb_t).  The last iteration keeps 0, as
+    every walk here ends without noise.  The mean of the step is not touched."""
+    p = _analytic_parts(betas, taus, eta)
+    K = len(p["lam2"])
+    g = np.clip(np.asarray(g, dtype=np.float64), 0.0, 1.0)
+    if g.ndim < 1 or g.shape[0] != K:
+        raise ValueError(f"analytic_variance: g of shape {g.shape} for a walk of {K} iterations")
+    if not float(clip) > 0:
+        raise ValueError(f"analytic_variance: clip={clip} must be positive (inf: no cap)")
+    ex = (slice(None),) + (None,) * (g.ndim - 1)
+    lam2, h, a = p["lam2"][ex], p["h"][ex], p["a"][ex]
+    sig2 = lam2 + h ** 2 * (1.0 - g)
+    if np.isfinite(clip):
+        sig2 = np.minimum(sig2, lam2 + a ** 2 * float(clip) ** 2)
+    sig2[-1] = 0.0
+    return sig2
+
+
+def analytic_sigma_table(betas: np.ndarray, taus, eta: float, g, clip: float = 1.0) -> np.ndarray:
+    """float32 sqrt(``analytic_variance``) of the same arguments: for ``g`` [K][S][C] the [K][S][C] table of
+    smd_engine_analytic_step (row = the plan's iteration), for ``g`` [K] the [K] values of the strided table's sigma column."""
+    return np.ascontiguousarray(np.sqrt(analytic_variance(betas, taus, eta, g, clip)).astype(np.float32))
+
+
+def analytic_scalar_g(g) -> np.ndarray:
+    """Scalar mode's statistic: the mean of g [K][...] over everything but the iteration axis."""
+    g = np.asarray(g, dtype=np.float64)
+    return g.reshape(g.shape[0], -1).mean(axis=1) if g.ndim > 1 else g
+
+
+def analytic_bound_from_sums(tab: dict, sums: np.ndarray, D: int, g, taus, betas) -> dict:
+    """The bound of the chain that walks ``taus`` (descending, ending at timestep 0) at eta = 1 with the SCALAR optimal variance:
+    ``tab`` = ``bound_tables(betas, ...)`` of the same timesteps and schedule, ``sums`` [K][N][3] as for ``bound_from_sums`` (rows ascending in t),
+    ``g`` [K] in the order of ``taus``.  Every transition t -> s with t >= 1 is the KL divergence of two Gaussians of variance
+    lam^2 (the posterior) and sig2 (the model):
+
+      L_(t->s) = a^2 q_t / (2 sig2) + (D / 2) (log(sig2 / lam^2) + lam^2 / sig2 - 1)
+
+    a, lam of ``strided_coefficients(betas, taus, 1)``, q_t = sum (x0 - x0_hat)^2; the decoder term L_0 (variance var_0 = bt_1)
+    and the prior keep the conventions of ``bound_from_sums``.  This is a bound of the K-step chain itself, so ``total`` is a number for every
+    K (for K = T it is the every-timestep bound with the optimal variances: a = mu1, lam^2 = bt).  g = 1 gives sig2 = lam^2 and
+    the terms of ``bound_from_sums``.  No clip cap is applied (``clip`` = inf): the cap belongs to the sampler."""
+    ts = np.asarray(tab["timesteps"], dtype=np.int64)
+    taus = np.asarray(taus, dtype=np.int64)
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.ndim != 3 or sums.shape[0] != len(ts) or sums.shape[2] != 3:
+        raise ValueError(f"analytic_bound_from_sums: sums of shape {sums.shape} for {len(ts)} timesteps")
+    if len(taus) != len(ts) or np.any(taus[::-1] != ts) or ts[0] != 0 or ts[-1] != len(tab["w"]) - 1:
+        raise ValueError("analytic_bound_from_sums: taus must be the table's timesteps, descending from T - 1 to 0")
+    g = np.asarray(g, dtype=np.float64)
+    if g.shape != (len(taus),):
+        raise ValueError(f"analytic_bound_from_sums: g of shape {g.shape} (scalar mode: one value per iteration) for {len(taus)} iterations")
+    if len(betas) != len(tab["w"]):
+        raise ValueError(f"analytic_bound_from_sums: {len(betas)} betas for tables of {len(tab['w'])} timesteps")
+    K = len(ts)
+    if K == len(tab["w"]):
+        # every timestep: a = mu1 and lam^2 = bt as bound_tables forms them, from the float32 betas (the ratios of the float32
+        # cumulative product are those betas only to 1e-7 / beta), and h^2 = beta^2 / (alpha bb), the same identity
+        b64 = np.asarray(betas, dtype=np.float32).astype(np.float64)[taus]
+        ap = alphas_cumprod(betas).astype(np.float64)
+        ap_t, ap_s = ap[taus], np.concatenate([ap[taus[1:]], np.ones(1)])
+        lam2 = b64 * (1 - ap_s) / (1 - ap_t)
+        p = dict(lam2=lam2, a=b64 * np.sqrt(ap_s) / (1 - ap_t))
+        sig2 = lam2 + b64 ** 2 / ((1 - b64) * (1 - ap_t)) * (1.0 - np.clip(g, 0.0, 1.0))
+    else:
+        p = _analytic_parts(betas, taus, 1.0)
+        sig2 = analytic_variance(betas, taus, 1.0, g, clip=np.inf)
+    terms = np.empty((K, sums.shape[1]), dtype=np.float64)
+    ratio = np.ones(K)
+    for j in range(K - 1):                      # iteration j: taus[j] -> taus[j + 1], taus[j] >= 1; row of sums K - 1 - j
+        r = K - 1 - j
+        lam2, s2 = p["lam2"][j], sig2[j]
+        ratio[r] = s2 / lam2
+        terms[r] = p["a"][j] ** 2 * sums[r, :, 0] / (2 * s2) + 0.5 * D * (np.log(s2 / lam2) + lam2 / s2 - 1.0)
+    terms[0] = sums[0, :, 0] / (2 * tab["var_0"]) + D * tab["decoder_const"]
+    prior = 0.5 * (tab["prior_a"] * sums[0, :, 2] + D * tab["prior_c"])
+    total = prior + terms.sum(axis=0)
+    return dict(timesteps=ts, terms=terms, prior=prior, total=total, sigma2_ratio=ratio,
+                nats_per_dim=float(total.mean() / D), bits_per_dim=float(total.mean() / (D * np.log(2.0))), var_0=tab["var_0"])
