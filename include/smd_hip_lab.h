@@ -122,6 +122,13 @@ typedef struct smd_gemm_epilogue {
 } smd_gemm_epilogue;
 int smd_gemm_nt_lab(const smd_bf16* A, int lda, const smd_bf16* Bt, int ldb, int M, int N, int K, const smd_gemm_epilogue* ep,
                     int min_tiles, int32_t* plan_out, void* stream);
+/* lab entry: launch_gemm_nt256_fp8, the launcher of the e4m3 DenseResBlock layers and dgrads, with the same full epilogue
+ * (tests/test_gpu_e4m3_regimes.py): smd_gemm_e4m3_nt (smd_hip.h) reaches bias / fp32 residual / fp32 and bf16 outputs only, the
+ * engine also runs bf16 residual -> bf16 output.  Operands and shape rules are those of smd_gemm_e4m3_nt (M, N, K multiples of 256,
+ * lda / ldb multiples of 16 and >= K); the epilogue checks are those of smd_gemm_nt_lab; alpha must be 1 and accumulate 0.  No
+ * arithmetic of its own.  Errors return < 0 with smd_last_error() set and launch nothing. */
+int smd_gemm_e4m3_nt_lab(const uint8_t* A8, int lda, const uint32_t* scale_a, const uint8_t* Bt8, int ldb, const uint32_t* scale_b,
+                         int M, int N, int K, const smd_gemm_epilogue* ep, void* stream);
 
 /* lab entry: launch_layernorm_fwd with the sampler's table-driven FiLM row (tests/test_gpu_ln_regimes.py).  It is
  * smd_layernorm_fwd_stats (smd_hip.h) plus the two LnArgs fields that only the engine's sampler steps set: with t_ptr != NULL every

@@ -641,24 +641,29 @@ int smd_wgrad_lab_launch(const smd_wgrad_problem* probs, int n, int kind, const 
 
 // ---- lab entry: launch_gemm_nt with every field of GemmEpilogue (include/smd_hip_lab.h).  The checks the launcher cannot make (it
 // trusts the engine's leading dimensions) come first; the plan is the launcher's own, written only behind a launch.
+static int lab_epilogue(const char* who, const smd_gemm_epilogue* e, int N, GemmEpilogue& ep) {
+  SMD_ARG_CHECK(e, "%s: null epilogue", who);
+  SMD_ARG_CHECK(e->act >= 0 && e->act <= 2 && e->aux_mode >= 0 && e->aux_mode <= 2, "%s: act=%d aux_mode=%d must be 0..2", who,
+                e->act, e->aux_mode);
+  SMD_ARG_CHECK(e->aux_mode == SMD_AUX_NONE || e->aux, "%s: aux_mode without aux", who);
+  SMD_ARG_CHECK(e->res_row_mod >= 0, "%s: res_row_mod=%d must be >= 0", who, e->res_row_mod);
+  SMD_ARG_CHECK((!e->pre_bf16 || e->ld_pre >= N) && (!e->aux || e->ld_aux >= N) && (!e->res_f32 || e->ld_res >= N) &&
+                    (!e->res_bf16 || e->ld_resb >= N) && (!e->out_f32 || e->ld_out >= N) && (!e->out_bf16 || e->ld_outb >= N),
+                "%s: a leading dimension is below N=%d (ld_pre=%d ld_aux=%d ld_res=%d ld_resb=%d ld_out=%d ld_outb=%d)", who, N,
+                e->ld_pre, e->ld_aux, e->ld_res, e->ld_resb, e->ld_out, e->ld_outb);
+  ep.alpha = e->alpha; ep.bias = e->bias; ep.act = e->act; ep.pre_bf16 = B(e->pre_bf16); ep.ld_pre = e->ld_pre;
+  ep.aux = B(e->aux); ep.ld_aux = e->ld_aux; ep.aux_mode = e->aux_mode; ep.res_f32 = e->res_f32; ep.ld_res = e->ld_res;
+  ep.res_row_mod = e->res_row_mod; ep.res_bf16 = B(e->res_bf16); ep.ld_resb = e->ld_resb; ep.out_f32 = e->out_f32; ep.ld_out = e->ld_out;
+  ep.accumulate = e->accumulate; ep.out_bf16 = B(e->out_bf16); ep.ld_outb = e->ld_outb;
+  return 0;
+}
 int smd_gemm_nt_lab(const smd_bf16* A, int lda, const smd_bf16* Bt, int ldb, int M, int N, int K, const smd_gemm_epilogue* e,
                     int min_tiles, int32_t* plan_out, void* stream) {
   SMD_ARG_CHECK(e, "smd_gemm_nt_lab: null epilogue");
   SMD_ARG_CHECK(A && Bt && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt) & 15) == 0,
                 "smd_gemm_nt_lab: A / Bt must be non-null and 16-byte aligned");
-  SMD_ARG_CHECK(e->act >= 0 && e->act <= 2 && e->aux_mode >= 0 && e->aux_mode <= 2, "smd_gemm_nt_lab: act=%d aux_mode=%d must be 0..2",
-                e->act, e->aux_mode);
-  SMD_ARG_CHECK(e->aux_mode == SMD_AUX_NONE || e->aux, "smd_gemm_nt_lab: aux_mode without aux");
-  SMD_ARG_CHECK(e->res_row_mod >= 0, "smd_gemm_nt_lab: res_row_mod=%d must be >= 0", e->res_row_mod);
-  SMD_ARG_CHECK((!e->pre_bf16 || e->ld_pre >= N) && (!e->aux || e->ld_aux >= N) && (!e->res_f32 || e->ld_res >= N) &&
-                    (!e->res_bf16 || e->ld_resb >= N) && (!e->out_f32 || e->ld_out >= N) && (!e->out_bf16 || e->ld_outb >= N),
-                "smd_gemm_nt_lab: a leading dimension is below N=%d (ld_pre=%d ld_aux=%d ld_res=%d ld_resb=%d ld_out=%d ld_outb=%d)", N,
-                e->ld_pre, e->ld_aux, e->ld_res, e->ld_resb, e->ld_out, e->ld_outb);
   GemmEpilogue ep;
-  ep.alpha = e->alpha; ep.bias = e->bias; ep.act = e->act; ep.pre_bf16 = B(e->pre_bf16); ep.ld_pre = e->ld_pre;
-  ep.aux = B(e->aux); ep.ld_aux = e->ld_aux; ep.aux_mode = e->aux_mode; ep.res_f32 = e->res_f32; ep.ld_res = e->ld_res;
-  ep.res_row_mod = e->res_row_mod; ep.res_bf16 = B(e->res_bf16); ep.ld_resb = e->ld_resb; ep.out_f32 = e->out_f32; ep.ld_out = e->ld_out;
-  ep.accumulate = e->accumulate; ep.out_bf16 = B(e->out_bf16); ep.ld_outb = e->ld_outb;
+  if (lab_epilogue("smd_gemm_nt_lab", e, N, ep) != 0) return -1;
   smd_plan::NtPlan p = {};
   const int rc = launch_gemm_nt(B(A), lda, B(Bt), ldb, M, N, K, ep, S(stream), min_tiles > 0 ? min_tiles : smd_plan::NT256_MIN_TILES, &p);
   if (rc == 0 && plan_out) {
@@ -666,6 +671,17 @@ int smd_gemm_nt_lab(const smd_bf16* A, int lda, const smd_bf16* Bt, int ldb, int
     for (int i = 0; i < 8; ++i) plan_out[i] = v[i];
   }
   return rc;
+}
+
+// ---- lab entry: launch_gemm_nt256_fp8 with every field of GemmEpilogue (the forms the engine's e4m3 layers and dgrads run)
+int smd_gemm_e4m3_nt_lab(const uint8_t* A8, int lda, const uint32_t* scale_a, const uint8_t* Bt8, int ldb, const uint32_t* scale_b,
+                         int M, int N, int K, const smd_gemm_epilogue* e, void* stream) {
+  SMD_ARG_CHECK(e, "smd_gemm_e4m3_nt_lab: null epilogue");
+  SMD_ARG_CHECK(A8 && Bt8 && (reinterpret_cast<uintptr_t>(A8) & 15) == 0 && (reinterpret_cast<uintptr_t>(Bt8) & 15) == 0,
+                "smd_gemm_e4m3_nt_lab: A8 / Bt8 must be non-null and 16-byte aligned");
+  GemmEpilogue ep;
+  if (lab_epilogue("smd_gemm_e4m3_nt_lab", e, N, ep) != 0) return -1;
+  return launch_gemm_nt256_fp8(A8, lda, scale_a, Bt8, ldb, scale_b, M, N, K, ep, S(stream));
 }
 
 // ---- lab entries: the launchers of diffusion.hip with every field of their argument structs (include/smd_hip_lab.h).  What the

@@ -256,6 +256,8 @@ _SIGS = {
                                        C.POINTER(c_i32), c_void]),
     "smd_gemm_nt_lab": (C.c_int, [c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GemmEpilogue), C.c_int,
                                   C.POINTER(c_i32), c_void]),
+    "smd_gemm_e4m3_nt_lab": (C.c_int, [c_void, C.c_int, c_void, c_void, C.c_int, c_void, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(GemmEpilogue), c_void]),
     "smd_reverse_step_lab": (C.c_int, [C.POINTER(ReverseStepLabArgs), C.POINTER(c_i32), c_void]),
     "smd_q_sample_lab": (C.c_int, [C.POINTER(QSampleLabArgs), C.POINTER(c_i32), c_void]),
     "smd_loss_grad_lab": (C.c_int, [c_void, c_void, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void,

@@ -496,7 +496,7 @@ def test_stable_and_lab_headers_partition_the_exports():
     lab = both - stable
     assert lab == {"smd_set_tuning", "smd_engine_debug_snapshot_bytes", "smd_engine_debug_snapshots", "smd_engine_debug_tensor",
                    "smd_probe_clock", "smd_probe_l2_warm", "smd_probe_tr_read", "smd_probe_stream_create_cu_mask", "smd_probe_stream_destroy",
-                   "smd_wgrad_lab_launch", "smd_gemm_nt_lab", "smd_layernorm_fwd_lab",
+                   "smd_wgrad_lab_launch", "smd_gemm_nt_lab", "smd_gemm_e4m3_nt_lab", "smd_layernorm_fwd_lab",
                    "smd_reverse_step_lab", "smd_q_sample_lab", "smd_loss_grad_lab"}
     assert {"smd_engine_sample_step_part", "smd_engine_forward_train", "smd_engine_backward_from", "smd_build_id"} <= stable
     assert both == set(lib._SIGS)                                                   # the ctypes table covers exactly the two headers
