@@ -278,6 +278,53 @@ typedef struct smd_multistep_plan {
 int smd_engine_multistep_step(smd_engine* e, const smd_sample_io* io, const smd_multistep_plan* plan, float* x0_prev, int part,
                               void* stream);
 
+/* One iteration of an EXPONENTIAL ADAMS walk down a sub-sequence of the timesteps: the third-order multistep predictor in
+ * lambda = log(alpha / sigma) on the clamped data prediction, optionally with a corrector that costs no network evaluation (no
+ * counterpart in the reference).  The multistep step with three history terms; the table keeps the row
+ * layout of smd_multistep_plan and fills its spare columns:
+ *   coef[t] = (sqrt(1/ap_t), sqrt(1-ap_t)/sqrt(ap_t), A0, b, unused, clip, sqrt(ap_s), sqrt(1-ap_s), A1, A2, A3, 0)
+ *   x0 = clamp(coef0 x - coef1 eps_hat, -clip, clip) (rounded once);  x' = A0 x0 + A1 h1 + A2 h2 + A3 h3 + b x;  infill as there.
+ * hist is one fp32 ring [3][B][S][C] per chain, owned by the caller: iteration j (plan[t].iteration) reads h_i, the x0 of iteration
+ * j - i, from slot (j - i) mod 3, and stores its own x0 (before the infill blend) into slot j mod 3.  A history whose coefficient
+ * is an exact 0 is not read, so a walk does not depend on what the ring held before it; with A2 = A3 = 0 the result is
+ * smd_engine_multistep_step's, bit for bit.  The corrector is folded into A0 .. A3 on the host (schedule.adams_coefficient_table),
+ * so predictor and predictor-corrector are this one call.  Everything else -- the infill draws, the bf16 network input, the
+ * collection row, metrics_partial[t], the last workgroup's store of next_t, the no-op for t outside [0, T) or off the walk (the
+ * ring untouched too), `part` and its refusal under option "fp32", the checks -- is as for smd_engine_multistep_step; hist must be
+ * non-null and, for data_channels % 4 == 0, 16-byte aligned. */
+int smd_engine_adams_step(smd_engine* e, const smd_sample_io* io, const smd_multistep_plan* plan, float* hist, int part, void* stream);
+
+/* The fused update of smd_engine_adams_step alone, on a caller's state, network output, ring, tables and timestep (per-element
+ * tests; a host that runs its own network).  The struct mirrors AdamsStepArgs (csrc/smd_kernels.h) field for field; a field left
+ * 0 / NULL means what it means there: x_bf16 NULL = no bf16 copy, t_advance NULL = *t_ptr is not advanced (else arrive must be a
+ * zeroed counter), collection NULL = nothing collected.  hist is the ring [3][B][S][C].  No arithmetic of its own.  The checks are
+ * the launcher's (null state / eps_hat / tables / t_ptr / hist, T <= 0, infill samples without masks, t_advance without arrive,
+ * for C % 4 == 0 every fp32 array 16-byte aligned, the ring included) plus: a pointer not aligned to its element, infill draws
+ * without masks, Cp < C.  Errors return < 0 with smd_last_error() set and launch nothing. */
+typedef struct smd_adams_step_args {
+  float* x;
+  float* hist;
+  const float* eps_hat;
+  int32_t B, S, C, Cp, T;
+  const float* coef;
+  const int32_t* plan;
+  const int32_t* t_ptr;
+  int32_t* t_advance;
+  uint32_t* arrive;
+  uint32_t seed_lo, seed_hi;
+  const uint32_t* key_ptr;
+  uint32_t sample_offset;
+  const float* infill_samples;
+  const float* infill_masks;
+  const float* infill_z_in;
+  const uint32_t* tf_infill_keys;
+  int64_t tf_n_total;
+  smd_bf16* x_bf16;
+  float* metrics_partial;
+  float* collection;
+} smd_adams_step_args;
+int smd_adams_step(const smd_adams_step_args* a, void* stream);
+
 /* One iteration of a walk that evaluates the variational bound of Ho et al. 2020 (eq. 5) term by term on held-out examples (no
  * counterpart in the reference).  At t = *t_ptr:
  *   smd_bound_noise   x_t = sqrt(ap_t) x0 + sqrt(1-ap_t) eps  -> x_t (fp32) and the engine's bf16 network input

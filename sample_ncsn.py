@@ -3,7 +3,8 @@
 interpolation (--interpolate) for DDPM checkpoints, writing {sampling_dir}/ncsn/{generated,
 collection,real}.pkl in the reference's layout (sample_ncsn.py:368-471).  --ddim_steps=K walks K of the
 schedule's timesteps with the strided (DDIM) sampler instead of all of them, in all three modes.  --ddim_order=2
---ddim_spacing=logsnr makes that walk the second-order multistep solver DPM-Solver++(2M) on a lambda-uniform grid.  --compute_bound
+--ddim_spacing=logsnr makes that walk the second-order multistep solver DPM-Solver++(2M) on a lambda-uniform grid, --ddim_solver=adams3 /
+adams3_pc a third-order exponential Adams solver on it.  --compute_bound
 evaluates the per-timestep variational bound on the eval examples first (--bound_only: and stops there).
 
 Multi-GPU sampling is embarrassingly parallel: under torch.distributed.run each rank generates a
@@ -101,7 +102,7 @@ def generate_samples(FLAGS, model, rng, sample_shape, num_samples, sigmas, sampl
         epsilon=FLAGS.ld_epsilon, steps=FLAGS.ld_steps, denoise=FLAGS.denoise, sample_offset=sample_offset,
         use_graph=FLAGS.graph, global_num_samples=global_num_samples, ddim_steps=FLAGS.ddim_steps, ddim_eta=FLAGS.ddim_eta,
         ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS), ddim_timesteps=walk,
-        analytic=analytic)
+        analytic=analytic, ddim_solver=FLAGS.ddim_solver)
     torch.cuda.synchronize()
     log.info("Generated samples in %f seconds", time.time() - t0)
     return generated, collection, ld_metrics
@@ -130,7 +131,8 @@ def infill_samples(FLAGS, model, rng, samples, masks, sigmas, sample_offset=0, g
         generated, collection, ld_metrics = ncsn.strided_dynamics(
             ld_rng, model, sigmas, init, FLAGS.ddim_steps, FLAGS.ddim_eta, True, infill_samples=samples, infill_masks=masks,
             use_graph=FLAGS.graph, sample_offset=sample_offset, global_num_samples=global_num_samples, order=FLAGS.ddim_order,
-            spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS), timesteps=walk, analytic=analytic)
+            spacing=FLAGS.ddim_spacing, prediction=_prediction(FLAGS), timesteps=walk, analytic=analytic,
+            solver=FLAGS.ddim_solver)
         return generated, collection, ncsn.collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = ncsn.diffusion_dynamics(
         ld_rng, model, sigmas, init, FLAGS.ld_epsilon, FLAGS.ld_steps, FLAGS.denoise, True,
@@ -158,13 +160,13 @@ def diffusion_stochastic_encoder(samples, sigmas, rng, device="cuda:0", sample_o
 
 def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl, dev, use_graph=True, points=9, ddim_steps=0,
                         ddim_eta=0.0, ddim_encode=False, ddim_order=1, ddim_spacing="uniform", prediction="eps", walk=None,
-                        analytic=None):
+                        analytic=None, ddim_solver="default"):
     """sample_ncsn.py:425-435 + diffusion_decoder (:269-310) for this rank's rows [lo, hi): goals = roll(starts, 1); both are
     encoded with the same key (the same noise); every one of the 9 interpolated latents is decoded with the SAME
     ld_rng = split(PRNGKey(sample_seed), 3)[1].  Returns (generated (9, n, ...), collection (9, 41, n, ...), collated metrics).
     ``ddim_steps`` > 0: the points are decoded with the strided sampler; with ``ddim_encode`` starts and goals are encoded by its
     deterministic inversion (ncsn.ddim_encode) instead of the single re-noising.  ``ddim_order`` / ``ddim_spacing``: the solver
-    and the grid of the decoding walks (ncsn.strided_dynamics); ``prediction``: what the network's output means, for the
+    and the grid of the decoding walks (ncsn.strided_dynamics), ``ddim_solver`` its ``solver``; ``prediction``: what the network's output means, for the
     inversion and every decoding walk."""
     from smd_amd import ncsn
     num = len(real)
@@ -183,7 +185,7 @@ def interpolate_samples(model, sigmas, real, lo, hi, rng, sample_seed, rng_impl,
         if ddim_steps:
             g, c, ld = ncsn.strided_dynamics(ld_rng, model, sigmas, z, ddim_steps, ddim_eta, use_graph=use_graph, sample_offset=lo,
                                              global_num_samples=num, order=ddim_order, spacing=ddim_spacing, prediction=prediction,
-                                             timesteps=walk, analytic=analytic)
+                                             timesteps=walk, analytic=analytic, solver=ddim_solver)
         else:
             g, c, ld = ncsn.diffusion_dynamics(ld_rng, model, sigmas, z, use_graph=use_graph, sample_offset=lo, global_num_samples=num,
                                                prediction=prediction)
@@ -281,10 +283,11 @@ def check_cluster_flags(FLAGS):
 
 
 def check_ddim_flags(FLAGS, walk=None):
-    """the refusals of --ddim_steps / --ddim_eta / --ddim_encode / --ddim_order / --ddim_spacing, before the GPU is touched;
+    """the refusals of --ddim_steps / --ddim_eta / --ddim_encode / --ddim_order / --ddim_spacing / --ddim_solver, before the GPU is touched;
     ``walk``: the recorded walk of a distilled checkpoint (resolve_distill_walk), whose length --ddim_steps then is"""
     used = [f"--{n}" for n in ("ddim_steps", "ddim_eta", "ddim_encode") if FLAGS.is_present(n) and getattr(FLAGS, n)]
-    used += [f"--{n}" for n, off in (("ddim_order", 1), ("ddim_spacing", "uniform")) if FLAGS.is_present(n) and getattr(FLAGS, n) != off]
+    used += [f"--{n}" for n, off in (("ddim_order", 1), ("ddim_spacing", "uniform"), ("ddim_solver", "default"))
+             if FLAGS.is_present(n) and getattr(FLAGS, n) != off]
     if used and FLAGS.sampling != "ddpm":
         raise SystemExit(f"{', '.join(used)}: the strided sampler walks a DDPM schedule, it needs --sampling=ddpm (got --sampling={FLAGS.sampling})")
     steps = FLAGS.ddim_steps
@@ -310,6 +313,24 @@ def check_ddim_flags(FLAGS, walk=None):
         log.warning("--ddim_order=2 --ddim_spacing=uniform: on a grid that is uniform in t the second-order update is LESS accurate "
                     "than --ddim_order=1 at the same --ddim_steps (history weight up to 3.7; DESIGN.md section 18, the table): "
                     "use --ddim_spacing=logsnr")
+    solver = FLAGS.ddim_solver
+    if solver != "default":
+        flag = f"--ddim_solver={solver}"
+        if not steps:
+            raise SystemExit(f"{flag} belongs to the strided sampler: give --ddim_steps (or a distilled checkpoint, which records its walk)")
+        if order == 2:
+            raise SystemExit(f"{flag} with --ddim_order=2: these are two solvers; leave --ddim_order at 1")
+        if FLAGS.ddim_eta != 0:
+            raise SystemExit(f"{flag} is a deterministic solver: it needs --ddim_eta=0 (got --ddim_eta={FLAGS.ddim_eta})")
+        if FLAGS.ddim_encode:
+            raise SystemExit(f"{flag} with --ddim_encode: the inversion is first order, so encoding and decoding would not be the "
+                             "same solver; use --ddim_solver=default or the stochastic encoder")
+        if FLAGS.analytic_variance != "none":
+            raise SystemExit(f"{flag} with --analytic_variance={FLAGS.analytic_variance}: the solver is deterministic, it has no "
+                             "noise term to give a variance to")
+        if spacing == "uniform" and walk is None:
+            log.warning("%s --ddim_spacing=uniform: on a grid that is uniform in t every higher-order update is LESS accurate than "
+                        "--ddim_order=1 at the same --ddim_steps (DESIGN.md section 29, the table): use --ddim_spacing=logsnr", flag)
 
 
 def check_bound_flags(FLAGS):
@@ -608,7 +629,8 @@ def main(argv):
                                                                 dev, FLAGS.graph, ddim_steps=FLAGS.ddim_steps,
                                                                 ddim_eta=FLAGS.ddim_eta, ddim_encode=FLAGS.ddim_encode,
                                                                 ddim_order=FLAGS.ddim_order, ddim_spacing=FLAGS.ddim_spacing,
-                                                                prediction=FLAGS.prediction, walk=walk, analytic=analytic)
+                                                                prediction=FLAGS.prediction, walk=walk, analytic=analytic,
+                                                                ddim_solver=FLAGS.ddim_solver)
     else:                                                                   # :437-439
         generated, collection, ld_metrics = generate_samples(FLAGS, model, rng, shape, hi - lo, sigmas, sample_offset=lo,
                                                              global_num_samples=num, walk=walk, analytic=analytic)

@@ -253,6 +253,13 @@ int smd_engine_multistep_step(smd_engine* e, const smd_sample_io* io, const smd_
   p.coef = plan->coef; p.plan = plan->plan; p.T = plan->T;
   return e->impl.multistep_step(sample_io(io), p, x0_prev, S(stream), part);
 }
+int smd_engine_adams_step(smd_engine* e, const smd_sample_io* io, const smd_multistep_plan* plan, float* hist, int part, void* stream) {
+  NEED(e);
+  SMD_ARG_CHECK(io && plan, "adams_step: null io / plan");
+  MultistepPlan p;
+  p.coef = plan->coef; p.plan = plan->plan; p.T = plan->T;
+  return e->impl.adams_step(sample_io(io), p, hist, S(stream), part);
+}
 int smd_engine_bound_step(smd_engine* e, const smd_bound_io* io, void* stream) {
   NEED(e);
   SMD_ARG_CHECK(io, "bound_step: null io");
@@ -711,6 +718,24 @@ int smd_reverse_step_lab(const smd_reverse_step_args* p, int32_t* form_out, void
   const int rc = launch_reverse_step(a, S(stream), form);
   if (rc == 0 && form_out) { form_out[0] = form[0]; form_out[1] = form[1]; }
   return rc;
+}
+
+int smd_adams_step(const smd_adams_step_args* p, void* stream) {
+  SMD_ARG_CHECK(p, "smd_adams_step: null arguments");
+  SMD_ARG_CHECK(al4(p->x) && al4(p->hist) && al4(p->eps_hat) && al4(p->coef) && al4(p->plan) && al4(p->t_ptr) && al4(p->t_advance) &&
+                    al4(p->arrive) && al4(p->key_ptr) && al4(p->infill_samples) && al4(p->infill_masks) && al4(p->infill_z_in) &&
+                    al4(p->tf_infill_keys) && al4(p->metrics_partial) && al4(p->collection) && al2(p->x_bf16),
+                "smd_adams_step: a pointer is not aligned to its element");
+  SMD_ARG_CHECK(p->Cp >= p->C, "smd_adams_step: Cp=%d is below C=%d", p->Cp, p->C);
+  SMD_ARG_CHECK(p->infill_masks || !(p->infill_z_in || p->tf_infill_keys), "smd_adams_step: infill draws without infill masks");
+  AdamsStepArgs a;
+  a.x = p->x; a.hist = p->hist; a.eps_hat = p->eps_hat; a.B = p->B; a.S = p->S; a.C = p->C; a.Cp = p->Cp; a.T = p->T;
+  a.coef = p->coef; a.plan = p->plan; a.t_ptr = p->t_ptr; a.t_advance = p->t_advance; a.arrive = p->arrive;
+  a.key = RngKey{p->seed_lo, p->seed_hi}; a.key_ptr = p->key_ptr; a.sample_offset = p->sample_offset;
+  a.infill_samples = p->infill_samples; a.infill_masks = p->infill_masks; a.infill_z_in = p->infill_z_in;
+  a.tf_infill_keys = p->tf_infill_keys; a.tf_n_total = p->tf_n_total; a.x_bf16 = B(p->x_bf16);
+  a.metrics_partial = p->metrics_partial; a.collection = p->collection;
+  return launch_adams_step(a, S(stream));
 }
 
 int smd_q_sample_lab(const smd_q_sample_args* p, int32_t* form_out, void* stream) {

@@ -719,6 +719,148 @@ __global__ __launch_bounds__(128 * RG) void multistep_step_kernel(MultistepStepA
   if (a.t_advance && threadIdx.x == 0) last_arriver_store(a.arrive, a.t_advance, next_t);
 }
 
+// ------------------------------------------------------------------ exponential Adams step (third order, free corrector)
+// The multistep step with three history terms instead of one: the predictor integrates the Lagrange
+// interpolant of the last three clamped x0 exactly in lambda, and the corrector -- the previous step redone with the evaluation
+// just made -- is folded into the same coefficients on the host, so one kernel serves both.  coef[t] = (sqrt_recip, sqrt_m1, A0,
+// b, -, clip, sqrt_as, sqrt_1m_as, A1, A2, A3, 0), plan[t] as for the strided step:
+//   x0 = clamp(sqrt_recip x - sqrt_m1 eps_hat, -clip, clip);  x' = A0 x0 + A1 h1 + A2 h2 + A3 h3 + b x;  infill at the level of next_t.
+// The history is a ring hist[3][B][S][C]: iteration j reads h_i = x0 of iteration j - i from slot (j - i) mod 3 and stores its
+// own x0 (before the infill blend) into slot j mod 3.  That is h3's slot, and every thread reads and writes its own elements
+// only, so the load of h3 in program order before the store is all the ordering it takes.
+// A history whose coefficient is an exact zero is not read (a workgroup-uniform branch), so a ring left full of NaNs by an
+// earlier walk cannot reach the state.  The h2 and h3 terms are then not added either; the h1 term goes through its fma with a
+// zero operand, exactly as multistep_step_kernel's does: with A2 = A3 = 0 the result has that kernel's bits, signed zeros included.
+template <int VEC, int RG>
+__global__ __launch_bounds__(128 * RG) void adams_step_kernel(AdamsStepArgs a) {
+  __shared__ float part[RG > 1 ? RG : 1][2][128 * VEC];
+  const int b = blockIdx.x;
+  const int ct = threadIdx.x & 127, rg = threadIdx.x >> 7;
+  const int t = *a.t_ptr;
+  if (t < 0 || t >= a.T) return;          // the walk's terminator (or a bad timestep): a no-op, t is not advanced either
+  const int4 pl = *reinterpret_cast<const int4*>(a.plan + (size_t)t * 4);
+  const int next_t = pl.x, iter = pl.y;
+  if (iter < 0) return;
+  const float* cf = a.coef + (size_t)t * SMD_MULTISTEP_COLUMNS;
+  const float sqrt_recip = cf[0], sqrt_m1 = cf[1], ca0 = cf[2], cb = cf[3], clip = cf[5];
+  const float sqrt_as = cf[6], sqrt_1m_as = cf[7], ca1 = cf[8], ca2 = cf[9], ca3 = cf[10];
+  const bool use1 = ca1 != 0.0f, use2 = ca2 != 0.0f, use3 = ca3 != 0.0f;
+  const size_t ring = (size_t)a.B * a.S * a.C;                // one slot of the ring
+  float* const own = a.hist + (size_t)(iter % 3) * ring;      // written by this iteration; holds x0 of iteration j - 3
+  const float* const hs1 = a.hist + (size_t)((iter + 2) % 3) * ring;
+  const float* const hs2 = a.hist + (size_t)((iter + 1) % 3) * ring;
+  const bool next_live = next_t >= 0 && next_t < a.T;       // the state being produced is still a noisy level
+  int slot = a.collection ? pl.z : -1;
+  if (slot > 40) slot = -1;               // the collection has 41 rows; out-of-range scatters are dropped
+  const uint32_t bglob = (uint32_t)b + a.sample_offset;
+  const size_t sample_base = (size_t)b * a.S * a.C;
+  const uint64_t tf_base = (uint64_t)bglob * a.S * a.C;       // this sample's first element in the global jax array
+  const uint32_t key_lo = a.key_ptr ? a.key_ptr[0] : a.key.seed_lo, key_hi = a.key_ptr ? a.key_ptr[1] : a.key.seed_hi;
+  TfKey tf_ik{0, 0};
+  tf_ik = tf_key_row(a.tf_infill_keys, iter);
+  float m_eps = 0.f, m_step = 0.f, m_z = 0.f;
+  for (int cb0 = 0; cb0 < a.C; cb0 += 128 * VEC) {          // uniform trip count: the LDS combine below has barriers
+    const int col0 = cb0 + ct * VEC;
+    const bool live = col0 < a.C;
+    float acc_e[VEC], acc_s[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc_e[v] = acc_s[v] = 0.f;
+    for (int s = rg; live && s < a.S; s += RG) {
+      const int e = s * a.C + col0;
+      const size_t idx = sample_base + e;
+      float x[VEC], eh[VEC], h1[VEC], h2[VEC], h3[VEC], x0[VEC], nx[VEC];
+      ldv<VEC>(a.x + idx, x);
+      ldv<VEC>(a.eps_hat + idx, eh);
+      if (use1) {
+        ldv<VEC>(hs1 + idx, h1);
+      } else {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) h1[v] = 0.f;
+      }
+      if (use2) ldv<VEC>(hs2 + idx, h2);
+      if (use3) ldv<VEC>(own + idx, h3);                          // before this thread's store to the same elements below
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        // x0 rounded once, as in strided_step_kernel: p + perr is sqrt_m1 * eps_hat exactly
+        const float p = sqrt_m1 * eh[v];
+        const float perr = __builtin_fmaf(sqrt_m1, eh[v], -p);
+        float recon = __builtin_fmaf(sqrt_recip, x[v], -p) - perr;
+        recon = fminf(fmaxf(recon, -clip), clip);                 // clip = inf: no clamp
+        x0[v] = recon;
+        float acc = cb * x[v];
+        if (use3) acc = __builtin_fmaf(ca3, h3[v], acc);
+        if (use2) acc = __builtin_fmaf(ca2, h2[v], acc);
+        nx[v] = __builtin_fmaf(ca0, recon, __builtin_fmaf(ca1, h1[v], acc));
+      }
+      if (a.infill_masks) {
+        float im[VEC], is[VEC], iz[VEC];
+        ldv<VEC>(a.infill_masks + idx, im);
+        ldv<VEC>(a.infill_samples + idx, is);
+        if (next_live) {
+          if (a.infill_z_in) {
+            ldv<VEC>(a.infill_z_in + idx, iz);
+          } else if (a.tf_infill_keys) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) iz[v] = jax_normal_from_bits(jax_bits_at(tf_ik, tf_base + e + v, (uint64_t)a.tf_n_total));
+          } else {
+            philox_normals<VEC>(iz, e, bglob, SMD_STREAM_INFILL, (uint32_t)t, key_lo, key_hi);
+          }
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          // the known region at the noise level of the state being PRODUCED (next_t), the clean samples at the end
+          const float y = next_live ? __builtin_fmaf(sqrt_as, is[v], sqrt_1m_as * iz[v]) : is[v];
+          nx[v] = nx[v] * (1.0f - im[v]) + y * im[v];
+        }
+      }
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        const float st = x[v] - nx[v];
+        acc_e[v] += eh[v] * eh[v];
+        acc_s[v] += st * st;
+      }
+      stv<VEC>(a.x + idx, nx);
+      stv<VEC>(own + idx, x0);                                    // the ring's newest entry: this thread's own elements
+      if (slot >= 0) stv<VEC>(a.collection + ((size_t)slot * a.B) * a.S * a.C + idx, nx);
+      if (a.x_bf16) stv_bf16<VEC>(a.x_bf16 + ((size_t)b * a.S + s) * a.Cp + col0, nx);
+    }
+    if constexpr (RG > 1) {
+      __syncthreads();
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        part[rg][0][ct * VEC + v] = acc_e[v]; part[rg][1][ct * VEC + v] = acc_s[v];
+      }
+      __syncthreads();
+      if (rg == 0) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          float se = 0.f, ss = 0.f;
+#pragma unroll
+          for (int g2 = 0; g2 < RG; ++g2) {
+            se += part[g2][0][ct * VEC + v]; ss += part[g2][1][ct * VEC + v];
+          }
+          acc_e[v] = se; acc_s[v] = ss;
+        }
+      }
+    }
+    // the norms of multistep_step_kernel: the noise is identically zero, so its sum of squares is
+    if (rg == 0 && live)
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      if (a.S > 1) {
+        m_eps += norm_of(acc_e[v]);
+        m_step += norm_of(acc_s[v]);
+        m_z += norm_of(0.f);
+      } else {
+        m_eps += acc_e[v]; m_step += acc_s[v];
+      }
+    }
+  }
+  if (a.metrics_partial) store_metrics(a.metrics_partial, t, a.B, b, a.S, m_eps, m_step, m_z);
+  // *t_advance = plan[t].next_t by the LAST workgroup to get here, as in strided_step_kernel
+  if (a.t_advance && threadIdx.x == 0) last_arriver_store(a.arrive, a.t_advance, next_t);
+}
+
 __global__ void advance_t_kernel(int* t_ptr) { *t_ptr -= 1; }
 __global__ void set_t_kernel(int* t_ptr, int v) { *t_ptr = v; }
 
@@ -945,17 +1087,20 @@ int launch_param_mse_loss_grad(const float* pred, const float* eps, const float*
 }
 
 namespace {
-// The argument checks of the three sampler steps, in the order their launchers have always made them.  `name` heads every
+// The argument checks of the four sampler steps, in the order their launchers have always made them.  `name` heads every
 // message; vec receives the vector path's choice.
 template <typename Args>
 int check_step_args(const Args& a, const char* name, bool& vec) {
   constexpr bool reverse = std::is_same<Args, ReverseStepArgs>::value, multistep = std::is_same<Args, MultistepStepArgs>::value;
+  constexpr bool adams = std::is_same<Args, AdamsStepArgs>::value, history = multistep || adams;
   bool plan = true, threefry = a.tf_infill_keys != nullptr;
   uintptr_t f32 = (uintptr_t)a.x | (uintptr_t)a.eps_hat | (uintptr_t)a.infill_samples | (uintptr_t)a.infill_masks |
                   (uintptr_t)a.infill_z_in | (uintptr_t)a.collection;
   if constexpr (!reverse) plan = a.plan != nullptr;
   if constexpr (multistep) {
     f32 |= (uintptr_t)a.x0_prev;
+  } else if constexpr (adams) {
+    f32 |= (uintptr_t)a.hist;
   } else {
     f32 |= (uintptr_t)a.z_in;
     threefry = threefry || a.tf_noise_keys;
@@ -963,6 +1108,8 @@ int check_step_args(const Args& a, const char* name, bool& vec) {
   SMD_ARG_CHECK(a.x && a.eps_hat && a.coef && plan && a.t_ptr, "%s: null pointer", name);
   if constexpr (multistep)
     SMD_ARG_CHECK(a.x0_prev, "%s: null history (x0_prev: one float32 array of the state's shape per chain)", name);
+  if constexpr (adams)
+    SMD_ARG_CHECK(a.hist, "%s: null history (hist: one float32 ring of three arrays of the state's shape per chain)", name);
   SMD_ARG_CHECK(a.B > 0 && a.S > 0 && a.C > 0 && (!a.x_bf16 || a.Cp >= a.C), "%s: bad shape", name);
   SMD_ARG_CHECK((a.infill_masks != nullptr) == (a.infill_samples != nullptr), "%s: infill needs samples and masks", name);
   if constexpr (reverse) SMD_ARG_CHECK(!a.collection || a.slot_table, "%s: collection needs slot_table", name);
@@ -975,7 +1122,7 @@ int check_step_args(const Args& a, const char* name, bool& vec) {
   if (vec)
     SMD_ARG_CHECK(al16(f32) && ((uintptr_t)a.x_bf16 & 7) == 0,
                   "%s: C=%d takes 16-byte loads: state, %seps_hat, %sinfill arrays and collection must be 16-byte aligned", name, a.C,
-                  multistep ? "history, " : "", multistep ? "" : "draws, ");
+                  history ? "history, " : "", history ? "" : "draws, ");
   return 0;
 }
 }  // namespace
@@ -1001,6 +1148,14 @@ int launch_multistep_step(const MultistepStepArgs& a, hipStream_t st) {
   bool vec;
   if (const int rc = check_step_args(a, "multistep_step", vec)) return rc;
   SMD_LAUNCH_VEC_RG(multistep_step_kernel, vec, a, st);
+  SMD_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_adams_step(const AdamsStepArgs& a, hipStream_t st) {
+  bool vec;
+  if (const int rc = check_step_args(a, "adams_step", vec)) return rc;
+  SMD_LAUNCH_VEC_RG(adams_step_kernel, vec, a, st);
   SMD_LAUNCH_CHECK();
   return 0;
 }

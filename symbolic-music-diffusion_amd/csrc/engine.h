@@ -177,6 +177,8 @@ class SmdEngine {
   int strided_step(const SampleStepIO& io, const StridePlan& plan, hipStream_t st, int part = 0);
   // eps-net forward + fused multistep (DPM-Solver++(2M)) step; x0_prev: the chain's history array (io.z_in and the noise keys unused)
   int multistep_step(const SampleStepIO& io, const MultistepPlan& plan, float* x0_prev, hipStream_t st, int part = 0);
+  // eps-net forward + fused exponential Adams step; hist: the chain's ring [3][B][S][C] of clamped x0
+  int adams_step(const SampleStepIO& io, const MultistepPlan& plan, float* hist, hipStream_t st, int part = 0);
   // one iteration of the variational-bound walk: noise an example to level t, eps-net forward at table row t, the three sums
   int bound_step(const BoundStepIO& io, hipStream_t st);
   // one iteration of the analytic-variance estimator walk: noise an example to level t, eps-net forward at table row t, the

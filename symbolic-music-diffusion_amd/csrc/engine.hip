@@ -1519,3 +1519,26 @@ int SmdEngine::multistep_step(const SampleStepIO& io, const MultistepPlan& plan,
   a.t_advance = io.t_ptr; a.arrive = W.step_arrive;      // *t_ptr = plan[t].next_t by the step's last workgroup
   return launch_multistep_step(a, st);
 }
+
+int SmdEngine::adams_step(const SampleStepIO& io, const MultistepPlan& plan, float* hist, hipStream_t st, int part) {
+  SMD_ARG_CHECK(io.x && io.t_ptr, "adams_step: null state / t pointer");
+  SMD_ARG_CHECK(plan.coef && plan.plan, "adams_step: null coefficient table / plan");
+  SMD_ARG_CHECK(hist, "adams_step: null history (hist)");
+  SMD_ARG_CHECK(plan.T == d_.num_timesteps, "adams_step: the plan has T=%d rows, the engine %d timesteps", plan.T, d_.num_timesteps);
+  SMD_ARG_CHECK(!training_ && coef_ && film_tables_, "adams_step: bind an inference workspace and the schedule tables first");
+  SMD_ARG_CHECK(part >= 0 && part <= 2, "adams_step: part=%d (0 whole step, 1 stem, 2 output stage + Adams update)", part);
+  SMD_ARG_CHECK(!(fp32 && part != 0), "adams_step: part=%d is not available under fp32 (no two-chain pipeline): walk one chain with part 0", part);
+  RC(run_network(io.t_ptr, st, part, io.x));
+  if (part == 1) return 0;
+  AdamsStepArgs a;
+  a.x = io.x; a.hist = hist; a.eps_hat = W.pred;
+  a.B = batch_; a.S = d_.seq_len; a.C = d_.data_channels; a.Cp = Cp_; a.T = plan.T;
+  a.coef = plan.coef; a.plan = plan.plan; a.t_ptr = io.t_ptr; a.key = RngKey{io.seed_lo, io.seed_hi};
+  a.sample_offset = io.sample_offset;
+  a.infill_samples = io.infill_samples; a.infill_masks = io.infill_masks; a.infill_z_in = io.infill_z_in;
+  a.tf_infill_keys = io.tf_infill_keys; a.tf_n_total = io.tf_n_total;
+  a.key_ptr = io.key_ptr;
+  a.x_bf16 = W.x_bf16; a.metrics_partial = io.metrics_partial; a.collection = io.collection;
+  a.t_advance = io.t_ptr; a.arrive = W.step_arrive;      // *t_ptr = plan[t].next_t by the step's last workgroup
+  return launch_adams_step(a, st);
+}

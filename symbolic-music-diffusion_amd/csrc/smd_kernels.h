@@ -377,6 +377,33 @@ struct MultistepStepArgs {
   float* collection = nullptr;        // [41][B][S][C] or null, row plan[t].slot
 };
 int launch_multistep_step(const MultistepStepArgs& a, hipStream_t st);
+
+// fused exponential Adams step (third order, the free corrector folded into the coefficients): the multistep step with a ring of
+// three histories.  The table keeps the multistep row layout (SMD_MULTISTEP_COLUMNS) and fills its spare columns.
+struct AdamsStepArgs {
+  float* x = nullptr;                 // [B][S][C] state, updated in place
+  float* hist = nullptr;              // [3][B][S][C] ring of clamped x0: iteration j reads x0 of j - i from slot (j - i) mod 3 where
+                                      // A_i != 0 and always writes its own into slot j mod 3
+  const float* eps_hat = nullptr;     // [B][S][C]
+  int B = 0, S = 0, C = 0, Cp = 0, T = 0;
+  const float* coef = nullptr;        // [T][12]: sqrt_recip, sqrt_m1, A0, b, (unused), clip, sqrt_as, sqrt_1m_as, A1, A2, A3, 0
+  const int32_t* plan = nullptr;      // [T][4]: next_t, iteration, slot, 0; iteration < 0 = not on the walk (a no-op)
+  const int* t_ptr = nullptr;         // device timestep; t outside [0, T) makes the launch a no-op
+  int* t_advance = nullptr;           // non-null: the last workgroup stores plan[t].next_t here (normally == t_ptr)
+  unsigned* arrive = nullptr;         // arrival counter for t_advance: zero before the first launch, reset by the kernel
+  RngKey key{0, 0};                   // Philox key of the infill draws
+  const uint32_t* key_ptr = nullptr;  // device-resident Philox key [2] (overrides `key`)
+  uint32_t sample_offset = 0;
+  const float* infill_samples = nullptr;  // [B][S][C] or null
+  const float* infill_masks = nullptr;
+  const float* infill_z_in = nullptr;
+  const uint32_t* tf_infill_keys = nullptr;  // jax.random key table [iterations][2], row plan[t].iteration
+  int64_t tf_n_total = 0;
+  bf16_t* x_bf16 = nullptr;           // [B*S][Cp] next network input (zero padded)
+  float* metrics_partial = nullptr;   // [T][B][3], row t
+  float* collection = nullptr;        // [41][B][S][C] or null, row plan[t].slot
+};
+int launch_adams_step(const AdamsStepArgs& a, hipStream_t st);
 int launch_advance_t(int* t_ptr, hipStream_t st);   // *t_ptr -= 1
 int launch_set_t(int* t_ptr, int v, hipStream_t st);   // *t_ptr = v (restart of a walk on the sampler's own stream)
 

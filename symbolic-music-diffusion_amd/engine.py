@@ -535,6 +535,21 @@ class Engine:
             _lib.check(self.L.smd_engine_multistep_step(self.h, C.byref(io), C.byref(plan), x0_prev.data_ptr(), int(part), _stream()),
                        "multistep_step")
 
+    def adams_step(self, io: "_lib.SampleIO", plan: "_lib.MultistepPlan", hist: torch.Tensor, part: int = 0) -> None:
+        """One iteration of an exponential Adams walk: the multistep step with the chain's ring ``hist`` of
+        three histories (fp32, (3, *the state's shape); include/smd_hip.h smd_engine_adams_step); ``part`` as in sample_step."""
+        want = (3, self.batch, *self.cfg.sample_shape)
+        index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        if (hist.dtype != torch.float32 or not hist.is_contiguous() or not hist.is_cuda or hist.device.index != index
+                or tuple(hist.shape) != want):
+            raise ValueError(f"adams_step: hist must be a contiguous float32 tensor of shape {want} on {self.device}, got "
+                             f"{hist.dtype} {tuple(hist.shape)} on {hist.device}")
+        self._sync_fp8_weights()
+        self._join_pending()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.smd_engine_adams_step(self.h, C.byref(io), C.byref(plan), hist.data_ptr(), int(part), _stream()),
+                       "adams_step")
+
     def bound_step(self, io: "_lib.BoundIO") -> None:
         """One iteration of the variational-bound walk: noise the examples to the level of the device timestep, eps-net
         forward at that table row, the three per-example sums (include/smd_hip.h smd_engine_bound_step)."""

@@ -278,6 +278,10 @@ ENGINE_FLAGS: List[FlagDef] = [
        "update DPM-Solver++(2M) of Lu et al. 2022 (deterministic: --ddim_eta=0; DESIGN.md section 18)."),
     _D("ddim_spacing", "enum", "uniform", "--ddim_steps: the timesteps are evenly spaced in t (uniform) or in "
        "lambda = log(sqrt(ap) / sqrt(1 - ap)) snapped to timesteps (logsnr: at most --ddim_steps of them).", ("uniform", "logsnr")),
+    _D("ddim_solver", "enum", "default", "--ddim_steps: default = the update --ddim_order names; adams3 = the third-order exponential "
+       "Adams predictor in lambda on the clamped x0; adams3_pc = the same with a corrector that reuses every network evaluation "
+       "to redo the previous step (no extra evaluations).  Deterministic (--ddim_eta=0), --ddim_order=1 left alone, meant for "
+       "--ddim_spacing=logsnr (DESIGN.md section 29).", ("default", "adams3", "adams3_pc")),
     _D("analytic_variance", "enum", "none", "sample_ncsn --ddim_steps: give the noise of every iteration the optimal reverse variance of "
        "Bao et al. 2022 (Analytic-DPM) instead of sigma_eta^2, from an estimate of E[eps_hat^2] per timestep: none, scalar (one "
        "variance per iteration) or element (one per latent element; DESIGN.md section 28).  With --compute_bound (scalar only) "

@@ -106,6 +106,15 @@ class MultistepPlan(C.Structure):
     _fields_ = [("coef", c_void), ("plan", c_void), ("T", c_i32)]
 
 
+class AdamsStepArgs(C.Structure):
+    """smd_adams_step_args of include/smd_hip.h"""
+    _fields_ = [("x", c_void), ("hist", c_void), ("eps_hat", c_void), ("B", c_i32), ("S", c_i32), ("C", c_i32), ("Cp", c_i32),
+                ("T", c_i32), ("coef", c_void), ("plan", c_void), ("t_ptr", c_void), ("t_advance", c_void), ("arrive", c_void),
+                ("seed_lo", c_u32), ("seed_hi", c_u32), ("key_ptr", c_void), ("sample_offset", c_u32),
+                ("infill_samples", c_void), ("infill_masks", c_void), ("infill_z_in", c_void), ("tf_infill_keys", c_void),
+                ("tf_n_total", c_i64), ("x_bf16", c_void), ("metrics_partial", c_void), ("collection", c_void)]
+
+
 class LangevinIO(C.Structure):
     _fields_ = [("x", c_void), ("grad", c_void), ("alpha", C.c_float), ("noise_coef", C.c_float), ("z_in", c_void),
                 ("seed_lo", c_u32), ("seed_hi", c_u32), ("step", c_u32), ("sample_offset", c_u32), ("use_threefry", c_i32),
@@ -169,6 +178,8 @@ _SIGS = {
     "smd_engine_sample_step_part": (C.c_int, [c_void, C.POINTER(SampleIO), C.c_int, c_void]),
     "smd_engine_strided_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(StridePlan), C.c_int, c_void]),
     "smd_engine_multistep_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(MultistepPlan), c_void, C.c_int, c_void]),
+    "smd_engine_adams_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(MultistepPlan), c_void, C.c_int, c_void]),
+    "smd_adams_step": (C.c_int, [C.POINTER(AdamsStepArgs), c_void]),
     "smd_engine_bound_step": (C.c_int, [c_void, C.POINTER(BoundIO), c_void]),
     "smd_engine_moment_step": (C.c_int, [c_void, C.POINTER(MomentIO), c_void]),
     "smd_engine_analytic_step": (C.c_int, [c_void, C.POINTER(SampleIO), C.POINTER(StridePlan), C.POINTER(SigmaTable), C.c_int, c_void]),

@@ -894,7 +894,7 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
                   collect: bool, infill: bool = False, infill_samples=None, infill_masks=None, noises: Optional[Callable] = None,
                   infill_noises: Optional[Callable] = None, use_graph: bool = True, one_chain: bool = False, sample_offset: int = 0,
                   global_num_samples: Optional[int] = None, multistep: bool = False, prediction="eps",
-                  sig_table: Optional[np.ndarray] = None):
+                  sig_table: Optional[np.ndarray] = None, adams: bool = False):
     """A table-driven walk over the timesteps ``order`` (smd_engine_strided_step) in the arrangement of diffusion_dynamics:
     eager launches with explicit draws, else one graph-replayed chain, else (B >= 128, bf16 / fp8) the pipelined pair.  Its
     cached graphs and persistent buffers live in their own ``slot`` of the model's sampler cache, beside diffusion_dynamics'
@@ -902,7 +902,9 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
     history tensor of its state's shape and steps with smd_engine_multistep_step; the first iteration does not read the
     history, so a reused buffer needs no reset.  ``sig_table``: float32 [iterations][...sample shape], the per-element noise scale
     of smd_engine_analytic_step, which then takes the step (column 4 of ``coef`` is its 0/1 switch); the table lives with the
-    entry's device tables, so ``walk_key`` must name its contents.  Returns (state, collection or None, metrics_partial (T, B, 3) indexed by t)."""
+    entry's device tables, so ``walk_key`` must name its contents.  ``adams``: ``coef`` is an exponential Adams table ([T][12],
+    schedule.adams_coefficient_table), every chain carries one ring of three histories and steps with smd_engine_adams_step; no
+    iteration reads a ring slot that its own walk has not written, so a reused ring needs no reset either.  Returns (state, collection or None, metrics_partial (T, B, 3) indexed by t)."""
     eng = model.engine
     dev = eng.device
     init = torch.as_tensor(init).to(dev, torch.float32).contiguous()
@@ -965,13 +967,13 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
             entry["inf_m"].copy_(inf_m)
     else:
         coef_d, plan_d = torch.from_numpy(coef).to(dev), torch.from_numpy(plan).to(dev)
-        sp = _lib.MultistepPlan() if multistep else _lib.StridePlan()
+        sp = _lib.MultistepPlan() if multistep or adams else _lib.StridePlan()
         sp.coef, sp.plan, sp.T = coef_d.data_ptr(), plan_d.data_ptr(), nT
         if graphed:
             cache.pop(slot, None)
         entry = dict(key=ckey, sig=sig, x=x, nk_d=nk_d, ik_d=ik_d, inf_s=inf_s, inf_m=inf_m, coef_d=coef_d, plan_d=plan_d, plan=sp)
         if sig_table is not None:
-            if multistep or tuple(sig_table.shape) != (len(order), *init.shape[1:]) or sig_table.dtype != np.float32:
+            if multistep or adams or tuple(sig_table.shape) != (len(order), *init.shape[1:]) or sig_table.dtype != np.float32:
                 raise ValueError(f"sig_table: float32 {(len(order), *init.shape[1:])} for the strided step, got {sig_table.dtype} {sig_table.shape}")
             entry["sig_d"] = torch.from_numpy(np.ascontiguousarray(sig_table)).to(dev)
             st_ = _lib.SigmaTable()
@@ -994,7 +996,8 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
             ch["t_ptr"].fill_(order[0])
         else:
             ch = dict(eng=e, x=x[lo:hi], metrics=torch.zeros((nT, h, 3), dtype=torch.float32, device=dev),
-                      hist=torch.zeros((h, *init.shape[1:]), dtype=torch.float32, device=dev) if multistep else None,
+                      hist=torch.zeros((3, h, *init.shape[1:]) if adams else (h, *init.shape[1:]), dtype=torch.float32, device=dev)
+                      if multistep or adams else None,
                       coll=torch.zeros((COLLECTION_STEPS + 1, h, *init.shape[1:]), dtype=torch.float32, device=dev) if collect else None,
                       t_ptr=torch.tensor([order[0]], dtype=torch.int32, device=dev),
                       key=torch.zeros(2, dtype=torch.int32, device=dev))
@@ -1018,7 +1021,9 @@ def _strided_walk(slot: str, rng, model: Model, betas, init, order: List[int], c
             ch["coll"][0] = start[lo:hi]
         e.load_state(ch["x"])
 
-    if multistep:
+    if adams:
+        step = lambda ch, part=0: ch["eng"].adams_step(ch["io"], sp, ch["hist"], part)
+    elif multistep:
         step = lambda ch, part=0: ch["eng"].multistep_step(ch["io"], sp, ch["hist"], part)
     elif sig_table is not None:
         sgt = entry["sig_table"]
@@ -1072,7 +1077,7 @@ def _walk_ld_metrics(model: Model, betas, taus, mp):
 def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, infill=False, infill_samples=None,
                      infill_masks=None, *, noises: Optional[Callable] = None, infill_noises: Optional[Callable] = None,
                      use_graph: bool = True, sample_offset: int = 0, global_num_samples: Optional[int] = None, order: int = 1,
-                     spacing: str = "uniform", prediction="eps", timesteps=None, analytic=None):
+                     spacing: str = "uniform", prediction="eps", timesteps=None, analytic=None, solver: str = "default"):
     """The generalised non-Markovian sampler of Song et al. 2021 (DDIM) on ``steps`` evenly spaced timesteps of the schedule
     (schedule.stride_timesteps) instead of all of them: ``steps`` network evaluations from the same checkpoint.  ``eta`` scales
     the noise of every iteration (0: deterministic, 1: the DDPM posterior's variance).  Returns (state, collection (41, ...),
@@ -1096,7 +1101,13 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
     E[eps_hat^2] per ITERATION, [K] or [K][...sample shape] (``estimate_score_moments``).  "scalar" uses its mean per iteration:
     sqrt(sig2) goes into the strided table's sigma column and smd_engine_strided_step walks as ever.  "element" walks with
     smd_engine_analytic_step on a [K][...] table, in the cache slot "analytic".  Order 1 only.  A digest of the variances is
-    part of the cache key: a reused entry keeps its device tables."""
+    part of the cache key: a reused entry keeps its device tables.
+    ``solver`` = "adams3" / "adams3_pc": the third-order exponential Adams predictor on the same clamped x0, alone or with the
+    corrector that reuses each evaluation to redo the previous step (``schedule.adams_coefficient_table``)
+    instead of the update ``order`` names.  Deterministic: ``order`` stays 1, ``eta`` 0, no ``analytic``.  It walks with
+    smd_engine_adams_step, a ring of three histories per chain, in the cache slot "adams", keyed by (iterations, solver, spacing) and
+    the timesteps themselves; it is a solver for the lambda grid (``spacing`` = "logsnr"), on the uniform one it is worse than
+    DDIM.  "default" is everything above, untouched."""
     nT = len(betas)
     pk = () if _sched.prediction_kind(prediction) == 0 else (("prediction", _sched.prediction_kind(prediction)),)
     if order not in (1, 2):
@@ -1105,6 +1116,15 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
         raise ValueError(f"spacing={spacing!r}: 'uniform' (in t) or 'logsnr' (in lambda)")
     if order == 2 and float(eta) != 0.0:
         raise ValueError(f"order=2 is a deterministic solver: eta must be 0, got {eta}")
+    if solver != "default":
+        if solver not in _sched.ADAMS_SOLVERS:
+            raise ValueError(f"solver={solver!r}: 'default' or one of {_sched.ADAMS_SOLVERS}")
+        if order != 1:
+            raise ValueError(f"solver={solver!r} is a solver of its own: leave order at 1, got {order}")
+        if float(eta) != 0.0:
+            raise ValueError(f"solver={solver!r} is a deterministic solver: eta must be 0, got {eta}")
+        if analytic is not None and analytic[0] != "none":
+            raise ValueError(f"solver={solver!r} is a deterministic solver: it has no noise term to give an analytic variance to")
     if timesteps is not None:
         taus = np.asarray([int(t) for t in timesteps], dtype=np.int64)
         if len(taus) == 0 or taus[0] >= nT or taus[-1] < 0 or np.any(np.diff(taus) >= 0):
@@ -1121,7 +1141,11 @@ def strided_dynamics(rng: PRNGKey, model: Model, betas, init, steps, eta=0.0, in
     kw = dict(collect=True, infill=infill, infill_samples=infill_samples, infill_masks=infill_masks, noises=noises,
               infill_noises=infill_noises, use_graph=use_graph, sample_offset=sample_offset, global_num_samples=global_num_samples,
               prediction=prediction)
-    if analytic is not None and analytic[0] != "none":
+    if solver != "default":
+        coef, plan = _sched.adams_coefficient_table(betas, taus, solver == "adams3_pc", prediction=prediction)
+        x, collection, mp = _strided_walk("adams", rng, model, betas, init, walk, coef, plan,
+                                          ("adams", len(walk), solver, spacing, tuple(walk)) + pk, adams=True, **kw)
+    elif analytic is not None and analytic[0] != "none":
         mode, g = analytic
         if mode not in ("scalar", "element"):
             raise ValueError(f"analytic: mode {mode!r} is not 'scalar' or 'element'")
@@ -1378,14 +1402,15 @@ def estimate_score_moments(model: Model, betas, x0, timesteps, draws: int = 1, r
 def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400, sampling="ald", epsilon=1e-3,
            steps=100, denoise=True, *, sample_offset: int = 0, use_graph: bool = True,
            global_num_samples: Optional[int] = None, ddim_steps: int = 0, ddim_eta: float = 0.0, ddim_order: int = 1,
-           ddim_spacing: str = "uniform", prediction="eps", ddim_timesteps=None, analytic=None):
+           ddim_spacing: str = "uniform", prediction="eps", ddim_timesteps=None, analytic=None, ddim_solver: str = "default"):
     """train_ncsn.py:499-551.  'ddpm': N(0,1) init + diffusion_dynamics.  'ald' / 'cas': uniform(-sqrt(12)/2, sqrt(12)/2)
     init (:542-547) + annealed / consistent Langevin dynamics with the score network ``scorenet``.  The reference unpacks
     three values from every sampler although consistent_langevin_dynamics returns two (a ValueError upstream); here 'cas'
     returns a two-entry collection [init, final state].  ``ddim_steps`` > 0 ('ddpm' only): the same initialisation, then the
     strided walk ``strided_dynamics(..., ddim_steps, ddim_eta, order=ddim_order, spacing=ddim_spacing)`` instead of every timestep.
     ``prediction`` "x0" / "v" ('ddpm' only): what the network's output means.  ``ddim_timesteps``: an
-    explicit descending walk for the strided sampler (a distilled student's, section 27) instead of ``ddim_steps`` evenly spaced ones."""
+    explicit descending walk for the strided sampler (a distilled student's, section 27) instead of ``ddim_steps`` evenly spaced ones.
+    ``ddim_solver``: ``strided_dynamics``' ``solver`` ("adams3" / "adams3_pc", section 29); it needs ``ddim_steps`` or a walk."""
     if ddim_timesteps is not None and not ddim_steps:
         ddim_steps = len(ddim_timesteps)
     if sampling not in ("ddpm", "ald", "cas"):
@@ -1394,6 +1419,8 @@ def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400
         raise ValueError(f"prediction={prediction!r} is a DDPM option: the Langevin samplers ('ald', 'cas') take a score network")
     if ddim_steps and sampling != "ddpm":
         raise ValueError("ddim_steps is a DDPM option: sampling must be 'ddpm'")
+    if ddim_solver != "default" and not ddim_steps:
+        raise ValueError(f"ddim_solver={ddim_solver!r} belongs to the strided sampler: give ddim_steps or ddim_timesteps")
     init_rng, ld_rng = split(rng)                                                    # :536
     eng = scorenet.engine
     if tuple(sample_shape) != eng.cfg.sample_shape:
@@ -1432,7 +1459,7 @@ def sample(scorenet: Model, sigmas, rng: PRNGKey, sample_shape, num_samples=2400
                                                              sample_offset=sample_offset, use_graph=use_graph,
                                                              global_num_samples=global_num_samples, order=ddim_order,
                                                              spacing=ddim_spacing, prediction=prediction, timesteps=ddim_timesteps,
-                                                             analytic=analytic)
+                                                             analytic=analytic, solver=ddim_solver)
         return generated, collection, collate_sampling_metrics(ld_metrics.cpu().numpy())
     generated, collection, ld_metrics = diffusion_dynamics(ld_rng, scorenet, sigmas, init, epsilon, steps, denoise,
                                                            False, sample_offset=sample_offset, use_graph=use_graph,

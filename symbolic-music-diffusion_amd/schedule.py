@@ -260,6 +260,119 @@ def multistep_coefficient_table(betas: np.ndarray, taus, order: int, clip: float
     return coef, plan
 
 
+# ------------------------------------------------------------------ third-order exponential Adams walks
+ADAMS_SOLVERS = ("adams3", "adams3_pc")
+_ADAMS_SERIES_BELOW = 0.5     # H under which the moments come from their series instead of the recurrence
+
+
+def _exp_moments(H: float, n: int) -> np.ndarray:
+    """J_k = Int_0^H e^(u - H) u^k du for k < n, float64.  J_0 = -expm1(-H) and J_k = H^k - k J_{k-1}; the recurrence subtracts
+    two numbers of size H^k to leave one of size H^(k+1) / (k + 1), so below H = 0.5 every J_k comes from its own alternating
+    series J_k = k! H^(k+1) sum_m (-H)^m / (m + k + 1)! instead (terms fall at least as fast as 2^-m there)."""
+    H = float(H)
+    J = np.empty(n, dtype=np.float64)
+    if H < _ADAMS_SERIES_BELOW:
+        for k in range(n):
+            term = H ** (k + 1) / (k + 1)                    # m = 0: k! H^(k+1) / (k + 1)!
+            total, m = 0.0, 0
+            while abs(term) > 1e-19 * abs(total) or m == 0:
+                total += term
+                m += 1
+                term *= -H / (m + k + 1)
+            J[k] = total
+        return J
+    J[0] = -np.expm1(-H)
+    for k in range(1, n):
+        J[k] = H ** k - k * J[k - 1]
+    return J
+
+
+def exp_lagrange_weights(lam_a: float, lam_b: float, nodes) -> np.ndarray:
+    """W_i = Int_{lam_a}^{lam_b} e^(l - lam_b) L_i(l) dl, float64, L_i the Lagrange basis on ``nodes`` (distinct lambdas, at most a
+    handful): the weights of an exponential integrator that replaces x0(l) by its interpolant on the nodes (section 29).  With
+    u = l - lam_a the basis is expanded in powers of u and integrated against the moments of ``_exp_moments``."""
+    nodes = np.asarray(nodes, dtype=np.float64).reshape(-1)
+    q = len(nodes)
+    H = float(lam_b) - float(lam_a)
+    if q < 1 or not H > 0 or not np.isfinite(H):
+        raise ValueError(f"exp_lagrange_weights: {q} nodes on an interval of length {H}")
+    u = nodes - float(lam_a)
+    J = _exp_moments(H, q)
+    W = np.empty(q, dtype=np.float64)
+    for i in range(q):
+        others = np.delete(u, i)
+        poly = np.poly(others) / np.prod(u[i] - others) if q > 1 else np.ones(1)      # highest power first
+        W[i] = float(np.dot(poly[::-1], J))
+    return W
+
+
+def adams_coefficients(betas: np.ndarray, taus, corrector: bool) -> dict:
+    """float64 coefficients of the third-order exponential Adams walk down ``taus`` (section 29), one entry per iteration:
+    x_s = b x_t + A0 x0_j + A1 x0_{j-1} + A2 x0_{j-2} + A3 x0_{j-3}, the corrector (``corrector``: redo the previous step with the
+    evaluation just made, then predict) folded in.  Also the unfolded weights for the tests: ``wp`` [K][3] of the predictor on
+    the nodes lambda of taus[j], taus[j-1], taus[j-2], ``wc`` [K][3] of the corrector on taus[j], taus[j-1], taus[j-2] over the
+    previous step (zero rows where there is none), ``alpha_t`` / ``alpha_s``, ``b`` and ``h``.  Iteration j has min(3, j + 1) nodes;
+    the last is first order on ap_s := 1 (b = 0, h = inf, weight 1: it returns x0).  Unused coefficients are exact +0."""
+    taus = np.asarray(taus, dtype=np.int64)
+    co = strided_coefficients(betas, taus, 0.0)
+    ap = alphas_cumprod(betas).astype(np.float64)
+    lam = half_logsnr(betas)[taus]
+    n = len(taus)
+    alpha_t, alpha_s, b = np.sqrt(ap[taus]), co["sqrt_as"], co["b"]
+    h = np.full(n, np.inf)
+    h[:-1] = lam[1:] - lam[:-1]
+    wp, wc = np.zeros((n, 3)), np.zeros((n, 3))
+    for j in range(n):
+        if j == n - 1:
+            wp[j, 0] = 1.0
+        else:
+            p = min(3, j + 1)
+            wp[j, :p] = exp_lagrange_weights(lam[j], lam[j + 1], lam[j::-1][:p])
+        if corrector and 1 <= j < n - 1:                       # b = 0 on the last iteration: nothing of the corrector survives
+            q = min(3, j + 1)
+            wc[j, :q] = exp_lagrange_weights(lam[j - 1], lam[j], lam[j::-1][:q])
+    A = np.zeros((n, 4))
+    for j in range(n):
+        A[j, :3] = alpha_s[j] * wp[j]
+        if corrector and 1 <= j < n - 1:
+            g = b[j] * alpha_t[j]
+            q = min(3, j + 1)
+            A[j, 0] += g * wc[j, 0]
+            A[j, 1] += g * (wc[j, 1] - wp[j - 1, 0])
+            if q > 2:
+                A[j, 2] += g * (wc[j, 2] - wp[j - 1, 1])
+            if j >= 3:
+                A[j, 3] = -g * wp[j - 1, 2]
+    return dict(A0=A[:, 0], A1=A[:, 1], A2=A[:, 2], A3=A[:, 3], b=b, h=h, wp=wp, wc=wc, alpha_t=alpha_t, alpha_s=alpha_s,
+                sqrt_as=co["sqrt_as"], sqrt_1m_as=co["sqrt_1m_as"])
+
+
+def adams_coefficient_table(betas: np.ndarray, taus, corrector: bool, clip: float = 1.0, prediction="eps"):
+    """Tables of the exponential Adams sampler for the descending timesteps ``taus``: float32 [T][12] -- the eight columns of
+    ``strided_coefficient_table`` at eta = 0 with A0 in place of a, then A1, A2, A3 (``adams_coefficients``, rounded once) and a
+    zero -- and that function's int32 [T][4] plan unchanged.  The four A columns depend on the schedule, the walk and the solver
+    only and take per-iteration Python (milliseconds: as much as several iterations of a warm walk), so the last few are kept:
+    a sampler that is called again with the same walk pays for them once."""
+    taus = [int(t) for t in taus]
+    key = (np.asarray(betas, dtype=np.float32).tobytes(), tuple(taus), bool(corrector))
+    A = _ADAMS_A_CACHE.get(key)
+    if A is None:
+        co = adams_coefficients(betas, taus, corrector)
+        A = np.stack([co[f"A{k}"] for k in range(4)], axis=1)
+        if len(_ADAMS_A_CACHE) >= 16:
+            _ADAMS_A_CACHE.pop(next(iter(_ADAMS_A_CACHE)))
+        _ADAMS_A_CACHE[key] = A
+    base, plan = strided_coefficient_table(betas, taus, 0.0, clip, prediction)
+    coef = np.zeros((len(betas), MULTISTEP_COLUMNS), dtype=np.float32)
+    coef[:, :8] = base
+    coef[taus, 2] = A[:, 0]
+    coef[taus, 8:11] = A[:, 1:]
+    return coef, plan
+
+
+_ADAMS_A_CACHE: dict = {}     # (betas bytes, walk, corrector) -> float64 [K][4], at most 16 entries, oldest dropped first
+
+
 # ------------------------------------------------------------------ progressive distillation (DESIGN.md section 27)
 DISTILL_COLUMNS = 16      # floats per row of the distillation table: one 64-byte row per student step
 DISTILL_WEIGHTINGS = ("truncated_snr", "none")
